@@ -29,6 +29,11 @@ sharding, gather, per-rank timing, reductions, JSON) on CPU with the solve repla
                      members) on a bounded sample of the same workload, on this box's host cores (rank 0, N=1 only)
   next_rows        = SURVEY 8(f) rows measured beside the headline, behind the timed region, never part of `value` (N=1 only):
                      kinodyn_refinement = row N1, one batch of 1024 through landing_kinodyn_solve_batch (tools/bench_kd_solve.py)
+
+--dump-outputs DIR writes what the LAST timed step handed its caller, rank 0's shard, as DIR/<name>.npy (float64): x, f, lam_g,
+status, iters, kkt of landing_solve_batch, one row per member.  The inputs are seeded, so two builds run with the same flags can
+be compared output for output.  Above DUMP_LIMIT_BYTES a fixed seeded sample of the members is written instead, with their
+indices in DIR/rows.npy.
 """
 import argparse
 import importlib
@@ -49,6 +54,7 @@ HBM_PEAK_GBPS = 8000.0       # MI355X_MICROARCH.md
 SURVEY_8D_KKT_FLOPS = 4.4e6  # block-tridiagonal factor+solve per interior-point iteration at N=40
 SURVEY_8D_CALLBACK_FLOPS = 0.14e6
 PMC_FILE = os.path.join(ROOT, "profiles", "r06_pmc_ipm.json")      # default of --pmc-file
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files together
 
 
 def kernel_source_sha():
@@ -139,6 +145,26 @@ def reference_generated_c_leg(np):
     return out
 
 
+def write_outputs(dirpath, arrays, np, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array (first axis = batch member) as dirpath/<name>.npy in float64.  When they would exceed `limit`
+    bytes, only a fixed seeded sample of the members (the same rows of every array), listed in dirpath/rows.npy."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    B = {v.shape[0] for v in arrays.values()}
+    assert len(B) == 1, "outputs disagree on the batch size"
+    B = B.pop()
+    per_row = sum(v[:1].nbytes for v in arrays.values())
+    if B * per_row > limit:
+        keep = max(1, (limit - 8 * B) // per_row)        # the index file counts too (at most B entries)
+        rows = np.sort(np.random.default_rng(0).choice(B, size=keep, replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+        B = keep
+    os.makedirs(dirpath, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirpath, k + ".npy"), np.ascontiguousarray(v))
+    return {"dir": dirpath, "files": sorted(k + ".npy" for k in arrays), "members": int(B), "bytes": int(sum(v.nbytes for v in arrays.values()))}
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -171,10 +197,13 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo only with --dry (CPU launcher test)")
     ap.add_argument("--no-extras", action="store_true", help="skip the PCIe-inclusive and two-batches-in-flight legs (profiling runs: only the headline launches)")
     ap.add_argument("--dry", action="store_true", help="no GPU work: exercise the multi-rank path with a stub solve")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs (rank 0: x, f, lam_g, status, iters, kkt) as DIR/<name>.npy")
     ap.add_argument("--force-dist", action="store_true", help="run the collective path (process group, RCCL gather, reductions) at world size 1 too: GPU smoke test of the multi-GPU code on a 1-GPU box")
     a = ap.parse_args()
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if a.backend == "gloo" and not a.dry:
         raise SystemExit("--backend gloo is the CPU launcher test and needs --dry: the product has no CPU path")
 
@@ -247,7 +276,7 @@ def main():
 
     def solve(dp, dx0):
         if a.dry:     # stub: "solution" = the initial guess, everything converged
-            x.copy_(dx0); st.zero_(); it.fill_(1)
+            x.copy_(dx0); st.zero_(); it.fill_(1); f.zero_(); lam.zero_(); kkt.zero_()
             return
         lib.solve_device(B, dp.data_ptr(), dx0.data_ptr(), opts, x.data_ptr(), f.data_ptr(), lam.data_ptr(), st.data_ptr(),
                          it.data_ptr(), kkt.data_ptr(), stream)
@@ -291,6 +320,10 @@ def main():
         step_ms.append(1e3 * (time.perf_counter() - ts))
     sync()
     elapsed = time.perf_counter() - t0
+    # what the last timed step returned, copied out before the legs below reuse the output buffers
+    last_out = None
+    if a.dump_outputs and rank == 0:
+        last_out = {k: v.cpu().numpy() for k, v in (("x", x), ("f", f), ("lam_g", lam), ("status", st), ("iters", it), ("kkt", kkt))}
     el = torch.tensor([elapsed], device=dev, dtype=torch.float64)
     per_rank = None
     if multi:      # per-GPU time spread (inter-GPU load imbalance is reported, not balanced)
@@ -427,6 +460,8 @@ def main():
 
             if world == 1 and not a.no_extras:
                 out["next_rows"] = {"kinodyn_refinement": measure_kinodyn(np, torch, local)}
+        if last_out is not None:
+            out["dumped_outputs"] = write_outputs(a.dump_outputs, last_out, np)
         print(json.dumps(out), flush=True)
     if multi:
         dist.barrier()

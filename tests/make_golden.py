@@ -3,7 +3,7 @@
 
 Sources (all under /root/reference, never copied into the repo):
   * oracle/_ref/liblanding_ref.so  = optimizations/landing/codegen_casadi/landingCtrller_IPOPT.c
-    compiled by oracle/Makefile; called through its CasADi external ABI -> n20_eval.npz,
+    compiled by oracle/Makefile; called through its CasADi external ABI -> n20_eval.npz, n20_ref_seeded.npz,
     n20_patterns.npz (casadi_s4/casadi_s5 via nlp_*_sparsity_out).
   * optimizations/landing/test_scripts/1.5msDrop30Pitch.mat (X_star, U_star) -> n20_golden_1p5ms30pitch.npz
   * optimizations/landing/data/*.mat (stored N=40 SRBM-CCC solutions)        -> n40_golden.npz
@@ -25,6 +25,20 @@ lc_problem = importlib.import_module("landing-controller_amd.problem")
 lc_const = importlib.import_module("landing-controller_amd.constants")
 REF = "/root/reference/optimizations/landing"
 OUT = os.path.join(ROOT, "tests", "golden")
+
+
+def ref_seeded(R):
+    """n20_ref_seeded.npz: the reference's outputs on the seeded random draws of tests/test_oracle.py (seed 7, lam_f 1.3)"""
+    rng = np.random.default_rng(7)
+    out = {}
+    for i in range(3):
+        x = rng.normal(size=R.nx) * 0.7
+        p = rng.uniform(0.3, 2.0, size=R.np_)
+        lam = rng.normal(size=R.ng)
+        _, _, gx, gp = R.grad(x, p, 1.3, lam)
+        for k, v in dict(x=x, p=p, lam_g=lam, g=R.g(x, p), jac=R.jac_g(x, p)[1], hess=R.hess_l(x, p, 1.3, lam), grad_gamma_x=gx, grad_gamma_p=gp).items():
+            out[f"c{i}_{k}"] = np.asarray(v)
+    np.savez_compressed(os.path.join(OUT, "n20_ref_seeded.npz"), **out)
 
 
 def realistic_p20(q_init, qd_init, q_term_ref, QN, mu, l_leg_max, f_max, q_min_z, q_term_min_z, dt=0.03):
@@ -90,6 +104,7 @@ def main():
         for k, v in dict(x=x, p=p, lam_g=lam, lam_f=lam_f, f=f, grad_f=gf, g=g, jac=jac, hess=hess, grad_gamma_x=gx, grad_gamma_p=gp).items():
             out[f"c{i}_{k}"] = np.asarray(v)
     np.savez_compressed(os.path.join(OUT, "n20_eval.npz"), **out)
+    ref_seeded(R)
 
     # ---- N=40 stored solutions (feasibility goldens) ----------------------
     files = ["attitude_tilt_None", "pitch_0_vX", "pitch_30_vX", "pitch_45_vX", "pitch_60_vX", "pitch_45_vY", "vZ_-3_roll", "vZ_-3_vX", "vZ_-3_vY"]

@@ -44,6 +44,52 @@ def test_mismatched_world_size_is_refused():
 
 
 def test_no_gpu_means_loud_failure_not_a_cpu_number():
-    r = _run(["--steps", "1", "--warmup", "0", "--batch", "4"])
+    # no device visible to the child, also on a machine that has one
+    r = _run(["--steps", "1", "--warmup", "0", "--batch", "4"], env_extra={"HIP_VISIBLE_DEVICES": "-1", "CUDA_VISIBLE_DEVICES": "-1"})
     assert r.returncode != 0
     assert not _json_lines(r.stdout)
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs: the stub's outputs of the last timed step (x = that step's x0) as float npy files, the same from run to run"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import importlib
+    problem = importlib.import_module("landing-controller_amd.problem")
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("run%d" % run)
+        r = _run(["--dry", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--batch", "8", "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = _json_lines(r.stdout)[0]
+        assert j["steps"] == 3 and len(j["ms_by_step_rank0"]) == 3 and j["ms_per_step"] > 0
+        assert j["dumped_outputs"]["files"] == sorted(n + ".npy" for n in ("x", "f", "lam_g", "status", "iters", "kkt"))
+        dumps.append({n: np.load(str(d / n)) for n in j["dumped_outputs"]["files"]})
+    for n, v in dumps[0].items():
+        assert v.dtype in (np.float32, np.float64) and v.shape[0] == 8, n
+        assert np.array_equal(v, dumps[1][n]), n
+    _, X0, _, _ = problem.make_batch(8, 40, 0.6, seed=20211 + 1000 * 2)      # the last timed step's batch (step 2)
+    assert np.array_equal(dumps[0]["x.npy"], X0)
+    assert dumps[0]["status.npy"].max() == 0 and dumps[0]["iters.npy"].min() == 1
+
+
+def test_dump_outputs_samples_members_above_the_size_limit(tmp_path):
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(3)
+    arrays = {"x": rng.normal(size=(100, 50)), "status": rng.integers(0, 3, size=100).astype(np.int32)}
+    limit = 100 * 51 * 8 // 4
+    info = bench.write_outputs(str(tmp_path), arrays, np, limit=limit)
+    assert info["bytes"] <= limit and "rows.npy" in info["files"]
+    rows = np.load(str(tmp_path / "rows.npy")).astype(int)
+    x, st = np.load(str(tmp_path / "x.npy")), np.load(str(tmp_path / "status.npy"))
+    assert len(rows) == x.shape[0] == st.shape[0] > 0 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(x, arrays["x"][rows]) and np.array_equal(st, arrays["status"][rows])
+    again = tmp_path / "again"
+    bench.write_outputs(str(again), arrays, np, limit=limit)
+    assert np.array_equal(np.load(str(again / "rows.npy")), np.load(str(tmp_path / "rows.npy")))
+    info = bench.write_outputs(str(tmp_path / "all"), arrays, np)
+    assert "rows.npy" not in info["files"] and info["members"] == 100

@@ -3,6 +3,7 @@ landing_eval_hess_rc_batch (extended pattern: casadi_s4 + 18 N diagonals) and th
 grad_gamma_p, against the oracle -- whose own entries are pinned by finite differences of its gradient here."""
 import importlib
 import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -72,12 +73,17 @@ def _check(lib, N, B, seed):
         lib.eval_host(X, P, lf, lam, want=("hess",))
 
 
-@pytest.mark.skipif(not os.path.exists(EMU), reason="host emulation library not built (make -C landing-controller_amd/csrc emu)")
-def test_hess_rc_emulated_matches_oracle():
-    lib = capi.LandingLib(6, device=0, lib_path=EMU, run_cost=RC)
+@pytest.fixture(scope="module")
+def emu():
+    subprocess.run(["make", "-C", os.path.join(os.path.dirname(os.path.abspath(capi.__file__)), "csrc"), "emu"], check=True, capture_output=True)
+    return EMU
+
+
+def test_hess_rc_emulated_matches_oracle(emu):
+    lib = capi.LandingLib(6, device=0, lib_path=emu, run_cost=RC)
     _check(lib, 6, 3, 5)
     # without a running cost the extended pattern carries the casadi_s4 values and zeros
-    lib0 = capi.LandingLib(6, device=0, lib_path=EMU); O0 = Oracle(6)
+    lib0 = capi.LandingLib(6, device=0, lib_path=emu); O0 = Oracle(6)
     X, P, lam, lf = _inputs(6, 2, 9)
     h = lib0.hess_rc_host(X, P, lf, lam)
     for b in range(2):

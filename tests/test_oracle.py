@@ -53,21 +53,26 @@ def test_callbacks_match_reference_fixture(O20, case):
 
 
 def test_against_reference_library_when_present(oracle_mod, O20):
-    """Direct comparison with oracle/_ref (the reference's own generated C) on fresh seeds."""
+    """The reference's own generated C on seeded random draws: its outputs stored in tests/golden/n20_ref_seeded.npz
+    (tests/make_golden.py) and, when oracle/_ref was built, the live library on the same draws."""
+    d = np.load(os.path.join(GOLDEN, "n20_ref_seeded.npz"))
     try:
         R = oracle_mod.RefOracle()
     except FileNotFoundError:
-        pytest.skip("oracle/_ref not built (reference sources absent)")
-    rng = np.random.default_rng(7)
-    for _ in range(3):
-        x = rng.normal(size=732) * 0.7
-        p = rng.uniform(0.3, 2.0, size=354)
-        lam = rng.normal(size=2092)
-        assert np.max(np.abs(O20.g(x, p) - R.g(x, p))) <= TOL
-        assert np.max(np.abs(O20.jac_g(x, p)[1] - R.jac_g(x, p)[1])) <= TOL
-        assert np.max(np.abs(O20.hess_l(x, p, 1.3, lam) - R.hess_l(x, p, 1.3, lam))) <= 10 * TOL
-        a, b = O20.grad(x, p, 1.3, lam), R.grad(x, p, 1.3, lam)
-        assert np.max(np.abs(a[2] - b[2])) <= 10 * TOL and np.max(np.abs(a[3] - b[3])) <= 100 * TOL
+        R = None
+    for i in range(3):
+        c = lambda k: d[f"c{i}_{k}"]
+        x, p, lam = c("x"), c("p"), c("lam_g")
+        refs = [(c("g"), c("jac"), c("hess"), c("grad_gamma_x"), c("grad_gamma_p"))]
+        if R is not None:
+            b = R.grad(x, p, 1.3, lam)
+            refs.append((R.g(x, p), R.jac_g(x, p)[1], R.hess_l(x, p, 1.3, lam), b[2], b[3]))
+        a = O20.grad(x, p, 1.3, lam)
+        for g, jac, hess, gx, gp in refs:
+            assert np.max(np.abs(O20.g(x, p) - g)) <= TOL
+            assert np.max(np.abs(O20.jac_g(x, p)[1] - jac)) <= TOL
+            assert np.max(np.abs(O20.hess_l(x, p, 1.3, lam) - hess)) <= 10 * TOL
+            assert np.max(np.abs(a[2] - gx)) <= 10 * TOL and np.max(np.abs(a[3] - gp)) <= 100 * TOL
 
 
 def test_golden_trajectory_known_answer(O20):
