@@ -22,6 +22,7 @@
 #include "layout.hpp"
 #include "srbm_stage.hpp"
 #include "eval_kernels.hip"
+#include "ipm_core.hpp"
 #include "solver_kernels.hip"
 #include "vbl_kernels.hip"
 #include "rbd_kernels.hip"

@@ -6,7 +6,8 @@
 //   x = [X (12 x (N+1)); jpos (12 x N); U (24 x N: c; f_grf)],  rows g in the script's order (rbd_kernels.hip, kd_stage_rows).
 // What is solved here is the same primal-dual interior-point iteration as the SRBM solver's (solver_kernels.hip): slack + bound
 // multiplier pair on every inequality row, fraction-to-the-boundary rule, filter line search, monotone barrier update, inertia correction
-// by delta_w -- on this NLP's stage structure:
+// by delta_w.  The scalar control rules, the elastic-row arithmetic of the feasibility phase and the slack initialisation are the ones of
+// ipm_core.hpp, which both solvers call; this file adds the stage linear algebra of this NLP's stage structure:
 //   state   sigma_k = (X_k, c_k)            24      (X_0 and c_0 are fixed by the script's initial conditions, :89-91)
 //   control u_k     = (f_k, jpos_k, c_k+1)  36      (24 in the last interval: there is no c_N)
 //   dynamics X_k+1 = X_k + dt (...)  (the Euler defects :125-128 are linear in X_k+1 with unit coefficient), c_k+1 = part of u_k
@@ -26,6 +27,7 @@
 #include <math.h>
 
 #include "../../include/landing_nlp.h"
+#include "ipm_core.hpp"
 
 namespace landing {
 
@@ -52,24 +54,15 @@ __device__ __constant__ int KD_ROW2X[12] = {9, 10, 11, 6, 7, 8, 0, 1, 2, 3, 4, 5
 #else
 #define KD_PHASE __device__ __noinline__
 #endif
-struct KdState {
-  double mu, delta_last, th_max, c_pr, c_co, c_cm, c_ys, c_zs, c_nz, e_pr, e_du, e_co;
-  double tau, a_pr, a_du, th0, ph0, dphi, alpha, s_corr, delta, ft, fval, omt;
+struct KdState : IpmCtl {      // (the control fields both solvers keep: ipm_core.hpp)
+  double fval;
   double filt_th[KD_FILT], filt_ph[KD_FILT];
-  int nfilt, it, status, done, need_reg_streak, first_failed, cutstreak, force_step, wd_count, last_mu_it;
-  int accepted, armijo_step, fact_ok, skipped_zero, attempt, flag, ls_done, need_corr, fallback, nfact, ntrial, nreset;
-  int last_reset_it, ncrawl, clip_k_cur, fresh, reg_it;
+  int done, nfact, ntrial;
+  int reg_it;       // iteration of the last regularised factorisation (KD_DELTA_JUMP)
   int pending;      // the inertia correction of this iteration continues in the next launch (landing_kd_iter_kernel, KD_TRIES_PER_ROUND)
   int stage;        // 1: landing_kd_head_kernel has prepared this iteration (error test passed, barrier parameter, delta_w of the first attempt): landing_kd_condense_kernel and
                     // landing_kd_iter_kernel act on it; 0: nothing to do for them this round (finished, restarted, or resumed through `pending`)
-  int stag, full_prev; double e_prev;      // stag_relief (landing_nlp.h): full steps of the last barrier problem that did not halve the error
-  // feasibility (restoration) phase, round 5 -- the scheme of landing_ipm_kernel (solver_kernels.hip, landing_nlp.h feas_phase / feas_jam / feas_stat):
-  // feas = 1 while the elastic problem is being solved, lim = iteration limit in force, fjam / fstat / v1_ref = the two rules' counters
-  int feas, feas_used, lim, fjam, fstat, polished; double v1_ref, c_rn, f_vmax, f_v1;
-  // round 6 (landing_nlp.h feas_max / feas_back / feas_ret_push / feas_delta_dec / feas_resume): entries into the phase, stalled flag, hard iteration limit, "record the
-  // entry violation" flag; violation at the entry (1-norm, equality rows included), 1-norm residual of the equality rows at x, adapted regularisation factor of the phase
-  int n_feas, stalled, hard_lim, want_entry; double th_entry, f_theq, fdc;
-  double prof[8]; long long tp;      // development aid: wall_clock64 ticks (100 MHz) per phase, summed over the iterations: grad | mu | backward | forward | dual | line search | accept
+  double prof[8];   // development aid: wall_clock64 ticks (100 MHz) per phase, summed over the iterations: grad | mu | backward | forward | dual | line search | accept
 };
 
 struct KdMem {
@@ -240,102 +233,21 @@ KD_PHASE void kd_member_eval_g(const KdNlpParams& P, const RbdModel& M, int N, c
 #define KD_PROF(slot) do { if (threadIdx.x == 0) { const long long n_ = (long long)wall_clock64(); KSH.ks.prof[slot] += (double)(n_ - KSH.ks.tp); KSH.ks.tp = n_; } } while (0)
 
 // ---- condensation of interval k -------------------------------------------------------------------------------------------------
-// Round 6: split in two.  (a) kd_condense_rows -- the inequality rows' part J_I' Sigma J_I and J_I' rho of EVERY interval of every member that iterates this round,
-// one workgroup per (member, interval) in landing_kd_condense_kernel between the head and the iteration kernel: it does not depend on the Riccati recursion, and
-// inside the backward sweep its three chunks per stage (loads of 62 KB of J behind one chunk of matrix-core work) were 15 % of a batch of law main and 18 % of a round
-// of the lock-step tail, where one member's chain is all there is (tools/dev/gpu_r06p.sh: builds that run the loop 1 / 2 / 3 times).  (b) kd_assemble_stage -- inside the
-// sweep: M = (H + delta_w I) + [that part], m, [A^ | b], every load of a thread in flight together.  Same sums in the same order as the fused form of rounds 4-5:
-// bit-identical iterates.
-#ifndef KD_COND_UNROLL
-#define KD_COND_UNROLL 44
-#endif
+// Round 6: split in two.  (a) kd_condense_rows_sparse -- the inequality rows' part J_I' Sigma J_I and J_I' rho of EVERY interval of every member that iterates this
+// round, one workgroup per (member, interval) in landing_kd_condense_kernel between the head and the iteration kernel: it does not depend on the Riccati recursion, and
+// inside the backward sweep its three chunks per stage were 15 % of a batch of law main and 18 % of a round of the lock-step tail, where one member's chain is all there
+// is (tools/dev/gpu_r06p.sh: builds that run the loop 1 / 2 / 3 times).  (b) kd_assemble_stage -- inside the sweep: M = (H + delta_w I) + [that part], m, [A^ | b],
+// every load of a thread in flight together.
 #ifndef KD_COND_WGS
 #define KD_COND_WGS 3      // (168 registers: at 4 the chunk loop spills -- 35 against 19 ms of kernel time per batch, tools/dev/gpu_r06t.sh)
-#endif
-#ifndef KD_COND_DENSE
-#define KD_COND_DENSE 0      // 1: the matrix-core form (kd_condense_rows); 0: over the structural non-zeros (kd_condense_rows_sparse)
 #endif
 #ifndef KD_COND_GRID
 #define KD_COND_GRID 2048
 #endif
-struct KdCondLds {
-  double Jc[KD_JC_ROWS * KD_JC_S];     // chunk of the interval's inequality rows (v columns, zero padded to 64)
-  double sgc[KD_JC_ROWS], rhc[KD_JC_ROWS];
-};
-__shared__ KdCondLds KCS;
 
-// (a) J_I' Sigma J_I and m = J_I' rho over the inequality rows 12 .. nr-1 of interval k, in chunks of KD_JC_ROWS rows staged in LDS; the product runs on the fp64
-// matrix cores: wave w owns row tile w of M (16 rows), four column tiles; the loads of the next chunk are in flight while the matrix cores work on this one
-#if KD_COND_DENSE
-#error "the matrix-core form of the condensation reads dense Jacobian blocks: the solver keeps them in compact form since round 6 (rbd_kernels.hip KD_JCS)"
-#endif
-__device__ __forceinline__ void kd_condense_rows(const KdMem& M, int N, int k) {
-  KdCondLds& S = KCS;
-  const int tid = threadIdx.x;
-  const bool last = k == N - 1;
-  const int nv = last ? 48 : KD_NV, nr = last ? KD_ROWS_LAST : KD_ROWS;
-  // (global address space: global_load, not flat_load -- a flat load also counts on the LDS counter, so every wait for an LDS read would wait for the
-  // prefetched rows as well: solver_kernels.hip landing_gptr)
-  const landing_gptr Jk = (landing_gptr)(M.J + (size_t)k * KD_ROWS * KD_NW);
-  const landing_gptr Gsig = (landing_gptr)M.sig, Grho = (landing_gptr)M.rho;
-  const int g0 = KD_BND + k * KD_ROWS;
-  const int wave = tid >> 6, l = tid & 63, lj = l & 15, lk = l >> 4;
-  f64x4 acc[4];
-  for (int t = 0; t < 4; ++t) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
-  double macc = 0.0;
-  constexpr int NE = (KD_JC_ROWS * 64 + KD_THREADS - 1) / KD_THREADS;
-  double pre[NE], pre_sg = 0.0, pre_rh = 0.0;
-  auto fetch = [&](int r0) {
-#pragma unroll
-    for (int q = 0; q < NE; ++q) {
-      const int e = tid + q * KD_THREADS, rr = e >> 6, c = e & 63, r = r0 + rr;
-      const bool in = rr < KD_JC_ROWS && r < nr && c < nv;
-      const double v = Jk[(in ? r : 12) * KD_NW + kd_v2w(in ? c : 0)];      // unconditional load (clamped): all NE loads are issued together
-      pre[q] = in ? v : 0.0;
-    }
-    { const int r = r0 + tid; const bool in = tid < KD_JC_ROWS && r < nr; const double a = Gsig[g0 + (in ? r : 12)], b = Grho[g0 + (in ? r : 12)]; pre_sg = in ? a : 0.0; pre_rh = in ? b : 0.0; }
-  };
-  fetch(12);
-#ifdef KD_DEV_COND_REPS      // timing probe (tools/dev): the chunk loop KD_DEV_COND_REPS times, the last pass counts -- same results, the difference of two builds is the loop's cost
-  for (int rep_ = 0; rep_ < KD_DEV_COND_REPS; ++rep_) {
-  if (rep_ > 0) { for (int t = 0; t < 4; ++t) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0}; macc = 0.0; __syncthreads(); fetch(12); }
-#endif
-  for (int r0 = 12; r0 < nr; r0 += KD_JC_ROWS) {
-#pragma unroll
-    for (int q = 0; q < NE; ++q) { const int e = tid + q * KD_THREADS, rr = e >> 6, c = e & 63; if (rr < KD_JC_ROWS) S.Jc[rr * KD_JC_S + c] = pre[q]; }
-    if (tid < KD_JC_ROWS) { S.sgc[tid] = pre_sg; S.rhc[tid] = pre_rh; }
-    __syncthreads();
-    if (r0 + KD_JC_ROWS < nr) fetch(r0 + KD_JC_ROWS);      // (uniform)
-    for (int t = 0; t < 4; ++t)
-      acc[t] = mfma_tile<KD_JC_ROWS / 4>(acc[t], [&](int i, int kk) { return S.Jc[kk * KD_JC_S + 16 * wave + i] * S.sgc[kk]; },
-                                         [&](int kk, int j) { return S.Jc[kk * KD_JC_S + 16 * t + j]; });
-#if defined(__HIP_DEVICE_COMPILE__)
-    for (int t = 0; t < 4; ++t) asm volatile("" : "+v"(acc[t]));
-#endif
-    if (tid < nv) {
-#pragma unroll KD_COND_UNROLL
-      for (int kk = 0; kk < KD_JC_ROWS; ++kk) macc += S.Jc[kk * KD_JC_S + tid] * S.rhc[kk];      // (one wave; unrolled: the 88 LDS reads are issued ahead of the chain of sums, whose order stays)
-    }
-    __syncthreads();
-  }
-#ifdef KD_DEV_COND_REPS
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("" : "+v"(macc));
-#endif
-  }
-#endif
-  double* gk = M.gc + (size_t)k * KD_GC;
-  for (int t = 0; t < 4; ++t)
-    for (int r = 0; r < 4; ++r) {
-      const int a = 16 * wave + lk + 4 * r, b = 16 * t + lj;
-      if (a < nv && b < nv) gk[a * KD_NV + b] = acc[t][r];
-    }
-  if (tid < nv) gk[KD_NV * KD_NV + tid] = macc;
-}
-
-// (a') the same over the structural non-zeros of the block (KdJPat / KdCPat): the entries of the block into LDS (529 gathers), then one lane per destination of the
-// 60 x 60 array (upper triangle, mirrored on the way out) and per right-hand side.  Entries of the array that no row couples are never written: the workspace starts
-// cleared.  (The dense form above on the matrix cores: 0.51 ms per round of the full batch, this one: see DESIGN.md 4.8b.)
+// (a) J_I' Sigma J_I and m = J_I' rho over the structural non-zeros of the block (KdJPat / KdCPat): the entries of the block into LDS (529 gathers), then one lane per
+// destination of the 60 x 60 array (upper triangle, mirrored on the way out) and per right-hand side.  Entries of the array that no row couples are never written: the
+// workspace starts cleared.  (Rounds 4-6 had a dense form on the matrix cores over the dense blocks: 0.51 ms per round of the full batch, this one: see DESIGN.md 4.8b.)
 struct KdCondSparseLds { double val[KD_JP_NNZ]; double sg[KD_JP_ROWS], rh[KD_JP_ROWS]; };
 __shared__ KdCondSparseLds KCP;
 __device__ __forceinline__ void kd_condense_rows_sparse(const KdMem& M, int N, int k, const KdJPat* __restrict__ jp, const KdCPat* __restrict__ cp) {
@@ -631,7 +543,7 @@ KD_PHASE void kd_forward(const KdMem& M, int N, const double* lbm, const KdJPat*
   static_assert(2 * NREC <= KD_NV * KD_MS, "two records fit the stage array");
   double nxt[NQ];
   auto fetch = [&](int k) {
-    const landing_gptr rec = (landing_gptr)(M.rec + (size_t)(k < N ? k : N - 1) * KD_REC);      // (global_load: see kd_condense_rows)
+    const landing_gptr rec = (landing_gptr)(M.rec + (size_t)(k < N ? k : N - 1) * KD_REC);      // (global_load: a flat load would also count on the LDS counter, ipm_core.hpp landing_gptr)
 #pragma unroll
     for (int q = 0; q < NQ; ++q) { const int e = tid + q * KD_THREADS; nxt[q] = rec[e < NREC ? e : NREC - 1]; }
   };
@@ -775,89 +687,21 @@ KD_PHASE void kd_point_pass(const KdMem& M, int ng, const double* lbm, const dou
   KD_BEGIN_SYNCED() S.ks.c_pr = v[0]; S.ks.c_co = v[1]; S.ks.c_cm = v[2]; S.ks.c_ys = v[3]; S.ks.c_zs = v[4]; S.ks.c_nz = fmax(v[5], 1.0); KD_END();
 }
 
-// the same for the elastic problem of the feasibility phase (solver_kernels.hip, el_step): every inequality row lb <= s <= ub becomes
-// a = s - lb + n >= 0, n >= 0 (b = ub + q - s >= 0, q >= 0) at the price rho_pen (n + q); the row enters the condensed system with sigma = z / D.
-// Also leaves the violation of the inequality rows at x (max norm, 1-norm) and |z + w - rho_pen|_inf in K
+// the same for the elastic problem of the feasibility phase (ipm_core.hpp el_point_row); also leaves the violation of the inequality rows at x
+// (max norm, 1-norm) and |z + w - rho_pen|_inf in K
 KD_PHASE void kd_feas_point_pass(const KdMem& M, int ng, const double* lbm, const double* ubm, double mu_, double frho) {
-  KdLds& S = KSH;
-  const int tid = threadIdx.x, NT = blockDim.x;
-  const double INF = INFINITY;
-  double pr = 0.0, co = 0.0, cm = 0.0, rn = 0.0, ys = 0.0, zs = 0.0, nz = 0.0, vmax = 0.0, v1 = 0.0, teq = 0.0;
-  for (int r = tid; r < ng; r += NT) {
-    const double lb = lbm[r], ub = ubm[r];
+  ElAcc e{};
+  for (int r = threadIdx.x; r < ng; r += blockDim.x) {
     double sg = 0.0, rh = 0.0;
-    if (r >= 24) {
-      const double g = M.g[r];
-      ys += fabs(M.y[r]);
-      if (lb == ub) { pr = fmax(pr, fabs(g - lb)); teq += fabs(g - lb); }
-      else {
-        const double s = M.s[r], v = fmax(fmax(lb - g, g - ub), 0.0);
-        pr = fmax(pr, fabs(g - s)); vmax = fmax(vmax, v); v1 += v;
-        if (lb > -INF) {
-          const double n = M.en[r], a = s - lb + n, z = M.zL[r], w = M.wn[r], D = a + z * n / w;
-          const double c = (mu_ - a * z - z * (mu_ - n * w + n * (z + w - frho)) / w) / D;
-          co = fmax(co, fmax(a * z, n * w)); cm = fmax(cm, fmax(fabs(a * z - mu_), fabs(n * w - mu_))); rn = fmax(rn, fabs(z + w - frho));
-          sg += z / D; rh -= z + c; zs += z; nz += 1.0;
-        }
-        if (ub < INF) {
-          const double q = M.ep[r], b = ub + q - s, z = M.zU[r], w = M.wp[r], D = b + z * q / w;
-          const double c = (mu_ - b * z - z * (mu_ - q * w + q * (z + w - frho)) / w) / D;
-          co = fmax(co, fmax(b * z, q * w)); cm = fmax(cm, fmax(fabs(b * z - mu_), fabs(q * w - mu_))); rn = fmax(rn, fabs(z + w - frho));
-          sg += z / D; rh += z + c; zs += z; nz += 1.0;
-        }
-        rh += sg * (g - s);
-      }
-    }
+    if (r >= 24) el_point_row(e, M, r, lbm[r], ubm[r], mu_, frho, sg, rh);
     M.sig[r] = sg; M.rho[r] = rh;
   }
-  double v[6] = {pr, co, cm, ys, zs, nz}; const int op[6] = {RMAX, RMAX, RMAX, RSUM, RSUM, RSUM};
-  block_reduce<6>(v, op, S.red);
-  double u[4] = {rn, vmax, v1, teq}; const int op4[4] = {RMAX, RMAX, RSUM, RSUM};
-  block_reduce<4>(u, op4, S.red);
-  KD_BEGIN_SYNCED()
-    S.ks.c_pr = v[0]; S.ks.c_co = v[1]; S.ks.c_cm = v[2]; S.ks.c_ys = v[3]; S.ks.c_zs = v[4]; S.ks.c_nz = fmax(v[5], 1.0); S.ks.c_rn = u[0]; S.ks.f_vmax = u[1]; S.ks.f_v1 = u[2]; S.ks.f_theq = u[3];
-    if (S.ks.want_entry) { S.ks.th_entry = u[2] + u[3]; S.ks.want_entry = 0; }      // first pass of a phase: the violation it starts from
-  KD_END();
+  el_point_finish(KSH.ks, e, KSH.red);
 }
 
-KD_PHASE void kd_init_slacks(const KdMem& M, int ng, const double* lbm, const double* ubm, const landing_solver_opts& o) {
-  const double INF = INFINITY;
-  for (int r = threadIdx.x; r < ng; r += blockDim.x) {
-    const double lb = lbm[r], ub = ubm[r];
-    double sv = 0.0, zl = 0.0, zu = 0.0;
-    if (r >= 24 && lb != ub) {
-      const bool hL = lb > -INF, hU = ub < INF;
-      sv = M.g[r];
-      double pl, pu;
-      if (hL && hU) { pl = fmin(o.bound_push * fmax(1.0, fabs(lb)), o.bound_frac * (ub - lb)); pu = fmin(o.bound_push * fmax(1.0, fabs(ub)), o.bound_frac * (ub - lb)); }
-      else { pl = o.bound_push * fmax(1.0, hL ? fabs(lb) : 0.0); pu = o.bound_push * fmax(1.0, hU ? fabs(ub) : 0.0); }
-      if (hL) sv = fmax(sv, lb + pl);
-      if (hU) sv = fmin(sv, ub - pu);
-      zl = hL ? 1.0 : 0.0; zu = hU ? 1.0 : 0.0;
-    }
-    M.s[r] = sv; M.zL[r] = zl; M.zU[r] = zu; M.y[r] = zu - zl;
-  }
-  __syncthreads();
-}
-
-// ... at the point a feasibility phase hands back (landing_nlp.h feas_ret_push, round 6): slacks pushed only feas_ret_push off their bounds, multipliers mu / distance
-KD_PHASE void kd_init_slacks_return(const KdMem& M, int ng, const double* lbm, const double* ubm, const landing_solver_opts& o, double mu_) {
-  const double INF = INFINITY, push = o.feas_ret_push;
-  for (int r = threadIdx.x; r < ng; r += blockDim.x) {
-    const double lb = lbm[r], ub = ubm[r];
-    double sv = 0.0, zl = 0.0, zu = 0.0;
-    if (r >= 24 && lb != ub) {
-      const bool hL = lb > -INF, hU = ub < INF;
-      sv = M.g[r];
-      double pl, pu;
-      if (hL && hU) { pl = fmin(push * fmax(1.0, fabs(lb)), push * (ub - lb)); pu = fmin(push * fmax(1.0, fabs(ub)), push * (ub - lb)); }
-      else { pl = push * fmax(1.0, hL ? fabs(lb) : 0.0); pu = push * fmax(1.0, hU ? fabs(ub) : 0.0); }
-      if (hL) sv = fmax(sv, lb + pl);
-      if (hU) sv = fmin(sv, ub - pu);
-      zl = hL ? fmin(fmax(mu_ / (sv - lb), 1e-8), 1e3) : 0.0; zu = hU ? fmin(fmax(mu_ / (ub - sv), 1e-8), 1e3) : 0.0;
-    }
-    M.s[r] = sv; M.zL[r] = zl; M.zU[r] = zu; M.y[r] = zu - zl;
-  }
+// slacks pushed into the interior; back: at the point a feasibility phase hands back (ipm_core.hpp ipm_init_row)
+KD_PHASE void kd_init_slacks(const KdMem& M, int ng, const double* lbm, const double* ubm, const landing_solver_opts& o, bool back, double mu_) {
+  for (int r = threadIdx.x; r < ng; r += blockDim.x) { const double lb = lbm[r], ub = ubm[r]; ipm_init_row(M, r, r >= 24 && lb != ub, lb, ub, o, back, mu_); }
   __syncthreads();
 }
 
@@ -881,17 +725,12 @@ __global__ void __launch_bounds__(KD_THREADS) landing_kd_init_kernel(KdSolveArgs
   __syncthreads();
   kd_member_eval_g(A.P, *A.model, N, M.x, M.g, M.wbuf);
   __syncthreads();
-  kd_init_slacks(M, ng, lbm, ubm, o);
+  kd_init_slacks(M, ng, lbm, ubm, o, false, 0.0);
   KdState& K = KSH.ks;
   if (tid == 0) {
-    K.mu = o.mu_init; K.delta_last = 0.0; K.th_max = 0.0; K.c_pr = K.c_co = K.c_cm = K.c_ys = K.c_zs = 0.0; K.c_nz = 1.0;
-    K.e_pr = K.e_du = K.e_co = 0.0; K.tau = 0.0; K.a_pr = K.a_du = 0.0; K.th0 = K.ph0 = K.dphi = K.alpha = K.s_corr = K.delta = K.ft = K.fval = 0.0; K.omt = -1.0;
-    K.nfilt = 0; K.it = 0; K.status = LANDING_MAX_ITER; K.done = 0; K.need_reg_streak = 0; K.first_failed = 0; K.cutstreak = 0; K.force_step = 0;
-    K.wd_count = 0; K.last_mu_it = 0; K.accepted = 0; K.armijo_step = 0; K.fact_ok = 0; K.skipped_zero = 0; K.attempt = 0; K.flag = 0; K.ls_done = 0;
-    K.need_corr = 0; K.fallback = 0; K.nfact = 0; K.ntrial = 0; K.nreset = 0; K.last_reset_it = 0; K.ncrawl = 0; K.clip_k_cur = o.clip_k; K.fresh = 0; K.reg_it = -1000; K.pending = 0; K.stage = 0; K.stag = 0; K.full_prev = 0; K.e_prev = 1e300;
-    K.feas = 0; K.feas_used = 0; K.lim = o.max_iter; K.fjam = 0; K.fstat = 0; K.polished = 0; K.v1_ref = 0.0; K.c_rn = 0.0; K.f_vmax = 0.0; K.f_v1 = 0.0;
-    K.n_feas = 0; K.stalled = 0; K.want_entry = 0; K.th_entry = 0.0; K.f_theq = 0.0; K.hard_lim = o.max_iter > 0 ? 3 * o.max_iter : 0; K.fdc = o.feas_delta_dec > 0.0 ? o.feas_delta_dec : o.delta_dec;
-    for (int i = 0; i < 8; ++i) K.prof[i] = 0.0; K.tp = 0;
+    ipm_init(K, o);
+    K.fval = 0.0; K.done = 0; K.nfact = 0; K.ntrial = 0; K.reg_it = -1000; K.pending = 0; K.stage = 0;
+    for (int i = 0; i < 8; ++i) K.prof[i] = 0.0;
   }
   __syncthreads();
   kd_point_pass(M, ng, lbm, ubm, K.mu);
@@ -917,9 +756,7 @@ __global__ void __launch_bounds__(KD_THREADS) landing_kd_init_kernel(KdSolveArgs
 }
 
 // ---- one interior-point iteration of one member (J and H blocks of the current (x, y) are in the workspace) ---------------------------
-#ifndef KD_DELTA_JUMP
-#define KD_DELTA_JUMP 12     // (round 5; 0 = off: rounds 3-4)
-#endif
+constexpr int KD_DELTA_JUMP = 12;      // (round 5, profiles/r05_ab_experiments.txt: the delta_w continuation of landing_kd_iter_kernel)
 #ifndef KD_TRIES_PER_ROUND
 #define KD_TRIES_PER_ROUND 2      // (round 5: 3 with the matrix-core elimination, 0.7 instead of 1.8 ms per attempt -- 1.23 -> 1.07 s per batch of 1024; round 4: 1.  With the
                                   // portfolio and the delta_w continuation 2: the tail rounds wait for their slowest member's attempts -- 0.408 -> 0.394 s, 1 attempt 0.411)
@@ -944,7 +781,6 @@ __global__ void __launch_bounds__(KD_THREADS, 2) landing_kd_head_kernel(KdSolveA
   const landing_solver_opts& o = kd_opts_of(A, m);
   const double* lbm = A.lb + (size_t)pm * ng; const double* ubm = A.ub + (size_t)pm * ng;
   const double* cost = A.cost + (size_t)pm * 24;
-  const double INF = INFINITY;
   KdLds& S = KSH;
   KdState& K = S.ks;
   if (tid == 0) { K = *M.st; K.tp = (long long)wall_clock64(); }
@@ -968,90 +804,19 @@ __global__ void __launch_bounds__(KD_THREADS, 2) landing_kd_head_kernel(KdSolveA
       for (int i = tid; i < nx; i += NT) { const bool fixed = i < 12 || (i >= oU && i < oU + 12); if (!fixed) du = fmax(du, fabs(M.gx[i])); }
       du = block_reduce1(du, RMAX, S.red);
       KD_BEGIN_SYNCED()
-        const double pr = K.c_pr, co = K.c_co;
-        if (K.feas) du = fmax(du, K.c_rn);      // the elastic problem has the extra stationarity rows rho_pen - z - w = 0
-        K.e_pr = pr; K.e_du = du; K.e_co = co;
-        if (o.stag_relief > 0) {      // as in landing_ipm_kernel: the proximal term turns the last Newton steps into a linear iteration (one member of the
-          const double E = fmax(pr, du);      // bench batch: 400 full steps from pr 1.5e-5 to 1e-6, a quarter of the batch's wall time)
-          K.stag = (!K.feas && K.mu <= o.tol / 10.0 * 1.0000001 && K.full_prev && E > 0.5 * K.e_prev) ? K.stag + 1 : 0;
-          K.e_prev = E;
-        }
-        K.flag = 0;      // 0: iterate, 1: stop, 2: restart, 3: back from the feasibility phase, 4: into the feasibility phase
-        bool give_up = false;
-        if (K.feas) {
-          // feasibility phase (landing_nlp.h): a feasible point (or an elastic KKT point with negligible violation) restarts the solve from here, an elastic
-          // KKT point with positive violation is the certificate of local infeasibility; a violation that has been stationary for feas_stat iterations with
-          // the equality rows at 1e-3 is not (LANDING_STALLED, round 6)
-          const bool conv = fmax(du, fmax(pr, co)) <= o.tol;
-          if (!(du < 1e300) || !(pr < 1e300) || !(co < 1e300)) { K.status = LANDING_NUMERICAL; K.flag = 1; }
-          else if (K.f_vmax <= 1e-9 && pr <= o.tol) K.flag = 3;
-          else if (conv && K.f_v1 > o.feas_cert) { K.status = LANDING_INFEASIBLE; K.flag = 1; }
-          else if (conv) K.flag = 3;
-          else if (o.feas_back > 0.0 && !K.feas_used && K.f_v1 + K.f_theq <= o.feas_back * K.th_entry) K.flag = 3;      // the violation has come down: back to the interior-point iteration (IPOPT's restoration phase)
-          else if (o.feas_stat > 0) {
-            const double v1 = K.f_v1;
-            if (K.fstat < 0 || !(fabs(v1 - K.v1_ref) <= 0.05 * K.v1_ref)) { K.v1_ref = v1; K.fstat = 0; } else K.fstat++;
-            if (K.fstat >= o.feas_stat && K.mu <= 1e-4 && pr <= 1e-3) {      // round 6 (landing_nlp.h): a stationary violation is not a certificate -- the regularisation is dropped once
-              if (v1 <= o.feas_cert) K.flag = 3;                             // (a stationary point is then a few Newton steps from the elastic KKT point, status 3 above); after that LANDING_STALLED
-              else if (o.feas_polish > 0.0 && !K.polished) { K.polished = 1; K.fstat = -1; K.delta_last = o.feas_polish / (o.feas_delta_dec > 0.0 ? o.feas_delta_dec : o.delta_dec); K.need_reg_streak = 2; }
-              else if (o.feas_resume && !K.stalled) { K.stalled = 1; K.feas_used = 1; K.flag = 3; }      // the interior-point iteration resumes from this point, once
-              else { K.status = LANDING_STALLED; K.flag = 1; }
-            }
-          }
-          if (K.flag == 0 && K.it >= K.lim) { K.status = K.stalled ? LANDING_STALLED : LANDING_MAX_ITER; K.flag = 1; }
-          if (K.flag == 3) {
-            K.feas = 0; K.lim = K.it + (o.max_iter > 1 ? o.max_iter : 1); if (K.lim > K.hard_lim) K.lim = K.hard_lim; K.status = LANDING_MAX_ITER;
-            K.mu = (o.feas_ret_push > 0.0 && o.feas_ret_mu > 0.0) ? o.feas_ret_mu : o.mu_init; K.fjam = 0; K.nfilt = 0; K.delta_last = 0.0; K.need_reg_streak = 0; K.wd_count = 0; K.th_max = 0.0; K.nreset = 0; K.last_reset_it = K.it; K.ncrawl = 0;
-            K.cutstreak = 0; K.force_step = 0;
-            K.it = K.it + 1;
-          }
-        }
-        else if (!(du < 1e300) || !(pr < 1e300) || !(co < 1e300)) { K.status = LANDING_NUMERICAL; give_up = true; }
-        else if (fmax(du, fmax(pr, co)) <= o.tol) { K.status = LANDING_CONVERGED; K.flag = 1; }
-        else if (K.it >= K.lim) { K.status = LANDING_MAX_ITER; give_up = true; }
-        else if (du > o.reset_du && K.nreset >= o.max_resets && o.max_resets > 0) { K.status = LANDING_NUMERICAL; give_up = true; }      // jammed again: give up
-        else if (o.feas_jam > 0 && K.fjam >= o.feas_jam && pr > 1e-3 && o.feas_phase) { K.status = LANDING_MAX_ITER; give_up = true; if (K.feas_used) K.stalled = 1; }      // jammed line search (landing_nlp.h); no entry left: status 4
-        else {
-          // restart rules of the SRBM solver (solver_kernels.hip, landing_nlp.h fresh_restart): a jammed iterate (multipliers blown up), a first
-          // barrier problem that crawls, a later one that has wandered off -> slacks, multipliers, barrier parameter and filter are re-initialised,
-          // at the current x or (after a jam) at the caller's initial guess with the step rule clip_k = 2
-          const int it = K.it, nreset = K.nreset; const double mu = K.mu;
-          const bool jam = du > o.reset_du && nreset < o.max_resets;
-          const bool stalled = o.restart_period > 0 && it - K.last_reset_it >= o.restart_period && mu >= o.mu_init && nreset < o.max_resets && K.ncrawl < ((o.fresh_restart & 4) ? 2 : 1);
-          const bool overreg = o.reset_delta > 0.0 && K.delta_last > o.reset_delta && nreset < o.max_resets;
-          const bool lost = (o.fresh_restart & 8) && o.restart_period > 0 && mu < o.mu_init && pr > 1e-3 && nreset < o.max_resets &&
-                            ((it - K.last_mu_it >= 2 * o.restart_period && it - K.last_reset_it >= o.restart_period) || K.wd_count >= 3);
-          if (jam || stalled || overreg || lost) {
-            K.flag = 2;
-            K.last_reset_it = it;
-            if (stalled) K.ncrawl++;
-            K.nreset = nreset + 1;
-            K.fresh = (((o.fresh_restart & 2) && nreset + 1 == 2) || ((o.fresh_restart & 1) && nreset + 1 == 1 && !stalled && !lost)) ? 1 : 0;
-            if (K.fresh) { if (K.clip_k_cur > 1) K.clip_k_cur = 2; K.th_max = 0.0; }
-            K.mu = o.mu_init; K.nfilt = 0; K.delta_last = 0.0; K.need_reg_streak = 0; K.wd_count = 0; K.cutstreak = 0; K.force_step = 0;
-            K.it = it + 1;
-          }
-        }
-        if (give_up) {      // the solve would end here as NUMERICAL / MAX_ITER: enter the feasibility phase once
-          if (K.stalled) K.status = LANDING_STALLED;
-          if (o.feas_phase && !K.feas_used && o.max_iter > 0 && K.it < K.hard_lim) {
-            K.flag = 4;
-            K.feas = 1; K.n_feas++; K.feas_used = K.n_feas >= o.feas_max ? 1 : 0; K.status = LANDING_MAX_ITER; K.lim = K.it + o.max_iter; if (K.lim > K.hard_lim) K.lim = K.hard_lim; K.fstat = -1;
-            K.fjam = 0; K.want_entry = 1; K.fdc = o.feas_delta_dec > 0.0 ? o.feas_delta_dec : o.delta_dec;
-            K.mu = o.mu_init; K.nfilt = 0; K.th_max = 0.0; K.delta_last = 0.0; K.need_reg_streak = 0; K.cutstreak = 0; K.force_step = 0; K.wd_count = 0;
-            K.it = K.it + 1;
-          } else K.flag = 1;
-        }
+        ipm_errors(K, o, du);
+        K.flag = ipm_decide(K, o, false);      // (a failed factorisation hands over through c_pr = INF: landing_kd_iter_kernel)
+        if (K.flag == ACT_RESET) { K.cutstreak = 0; K.force_step = 0; }      // (this solver's restart also disarms the watchdog)
       KD_END();
     }
-    if (K.flag == 1) {
+    if (K.flag == ACT_STOP) {
       if (tid == 0) {
         K.done = 1; *M.st = K; A.done[m] = 1;
         if (A.win && K.status == LANDING_CONVERGED) atomicMin(&A.win[pm], m);      // (relatives that converge in the same round: the lowest index, whatever the order)
       }
       return;
     }
-    if (K.flag == 2) {      // restart: the next round of launches evaluates the derivatives at the re-initialised point
+    if (K.flag == ACT_RESET) {      // restart: the next round of launches evaluates the derivatives at the re-initialised point
       if (K.fresh) {
         for (int i = tid; i < nx; i += NT) {
           double v = A.x0[(size_t)pm * nx + i];
@@ -1062,20 +827,20 @@ __global__ void __launch_bounds__(KD_THREADS, 2) landing_kd_head_kernel(KdSolveA
         kd_member_eval_g(A.P, *A.model, N, M.x, M.g, M.wbuf);
         __syncthreads();
       }
-      kd_init_slacks(M, ng, lbm, ubm, o);
+      kd_init_slacks(M, ng, lbm, ubm, o, false, 0.0);
       kd_point_pass(M, ng, lbm, ubm, K.mu);
       if (tid == 0) { *M.st = K; atomicAdd(A.n_active, 1); A.dlist_next[atomicAdd(A.n_dnext, 1)] = m; }
       return;
     }
-    if (K.flag == 3) {      // a feasible point (or negligible violation): the interior-point solve restarts from it; derivatives at the new multipliers next round
+    if (K.flag == ACT_BACK) {      // a feasible point (or negligible violation): the interior-point solve restarts from it; derivatives at the new multipliers next round
       for (int r = tid + 24; r < ng; r += NT) if (lbm[r] == ubm[r]) M.y[r] = 0.0;
       __syncthreads();
-      if (o.feas_ret_push > 0.0) kd_init_slacks_return(M, ng, lbm, ubm, o, K.mu); else kd_init_slacks(M, ng, lbm, ubm, o);
+      kd_init_slacks(M, ng, lbm, ubm, o, o.feas_ret_push > 0.0, K.mu);
       kd_point_pass(M, ng, lbm, ubm, K.mu);
       if (tid == 0) { *M.st = K; A.done[m] = 0; atomicAdd(A.n_active, 1); A.dlist_next[atomicAdd(A.n_dnext, 1)] = m; }
       return;
     }
-    if (K.flag == 4) {      // into the feasibility phase from the current point (from the caller's initial guess when the iterate is not finite)
+    if (K.flag == ACT_FEAS) {      // into the feasibility phase from the current point (from the caller's initial guess when the iterate is not finite)
       double big = 0.0;
       for (int i = tid; i < nx; i += NT) { const double v = fabs(M.x[i]); big = fmax(big, v < 1e6 ? v : 1e300); }
       big = block_reduce1(big, RMAX, S.red);
@@ -1089,18 +854,7 @@ __global__ void __launch_bounds__(KD_THREADS, 2) landing_kd_head_kernel(KdSolveA
       __syncthreads();
       kd_member_eval_g(A.P, *A.model, N, M.x, M.g, M.wbuf);
       __syncthreads();
-      {
-        const double frho = o.feas_rho, mu0 = o.mu_init;
-        for (int r = tid + 24; r < ng; r += NT) {
-          const double lb = lbm[r], ub = ubm[r], g = M.g[r];
-          if (lb == ub) { M.y[r] = 0.0; continue; }
-          // slack on the row value; violation variables sized so that both distances start at a comfortable value
-          double zl = 0.0, zu = 0.0, n0 = 0.0, q0 = 0.0, wl = 0.0, wu = 0.0;
-          if (lb > -INF) { const double v = lb - g; n0 = fmax(v, 0.0) + fmax(1e-2, 0.1 * fabs(v)); zl = fmin(mu0 / (g - lb + n0), 0.5 * frho); wl = frho - zl; }
-          if (ub < INF) { const double v = g - ub; q0 = fmax(v, 0.0) + fmax(1e-2, 0.1 * fabs(v)); zu = fmin(mu0 / (ub + q0 - g), 0.5 * frho); wu = frho - zu; }
-          M.s[r] = g; M.en[r] = n0; M.ep[r] = q0; M.zL[r] = zl; M.zU[r] = zu; M.wn[r] = wl; M.wp[r] = wu; M.y[r] = zu - zl;
-        }
-      }
+      for (int r = tid + 24; r < ng; r += NT) el_init_row(M, r, lbm[r], ubm[r], o.mu_init, o.feas_rho);
       __syncthreads();
       kd_feas_point_pass(M, ng, lbm, ubm, K.mu, o.feas_rho);
       if (tid == 0) { *M.st = K; A.done[m] = 0; atomicAdd(A.n_active, 1); A.dlist_next[atomicAdd(A.n_dnext, 1)] = m; }
@@ -1108,31 +862,15 @@ __global__ void __launch_bounds__(KD_THREADS, 2) landing_kd_head_kernel(KdSolveA
     }
     // ---------------------------------------------------------------- barrier parameter (monotone)
     for (;;) {
-      KD_BEGIN()
-        double sd = 1.0, sc = 1.0;
-        if (o.barrier_smax > 0.0) {
-          sd = fmax(o.barrier_smax, (K.c_ys + K.c_zs) / ((double)(ng - 24) + K.c_nz)) / o.barrier_smax;
-          sc = fmax(o.barrier_smax, K.c_zs / K.c_nz) / o.barrier_smax;
-        }
-        const double mu = K.mu;
-        if (fmax(K.e_du / sd, fmax(K.c_pr, K.c_cm / sc)) <= o.kappa_eps * mu && mu > o.tol / 10.0) {
-          K.mu = fmax(o.tol / 10.0, fmin(o.kappa_mu * mu, pow(mu, o.theta_mu)));
-          K.nfilt = 0; K.last_mu_it = K.it; K.wd_count = 0;
-          K.flag = 1;
-        } else { K.flag = 0; K.tau = fmax(o.tau_min, 1.0 - mu); }
-      KD_END();
+      KD_BEGIN() K.flag = ipm_barrier_update(K, o, ng - 24) ? 1 : 0; KD_END();
       if (!K.flag) break;
       if (K.feas) kd_feas_point_pass(M, ng, lbm, ubm, K.mu, o.feas_rho); else kd_point_pass(M, ng, lbm, ubm, K.mu);
     }
     KD_PROF(1);
     // ================================================================ Riccati factorisation with inertia correction (IPOPT's schedule)
     KD_BEGIN()
-      const double dl = K.delta_last;
-      K.delta = (K.need_reg_streak >= 2 && dl > 0.0) ? fmax(1e-20, dl * ((K.feas && o.feas_delta_dec > 0.0) ? K.fdc : o.delta_dec)) : 0.0;      // (inside the phase the regularisation falls faster, adapted: landing_nlp.h feas_delta_dec)
-      { double fl = K.feas ? 0.0 : o.delta_floor;    // proximal term (the cost is terminal only: landing_nlp.h delta_floor; off in the feasibility phase)
-        if (o.stag_relief > 0 && K.stag >= o.stag_relief) { for (int e = K.stag - o.stag_relief; e >= 0 && fl >= 1e-12; --e) fl *= 0.1; if (fl < 1e-12) fl = 0.0; }
-        K.delta = fmax(K.delta, fl); }
-      K.skipped_zero = K.delta > 0.0; K.fact_ok = 0; K.attempt = 0; K.flag = 1; K.nfact++;
+      ipm_first_delta(K, o, ipm_delta_dec(K, o), K.feas ? 0.0 : o.delta_floor);      // (proximal term: the cost is terminal only, landing_nlp.h delta_floor; off in the feasibility phase)
+      K.nfact++;
       K.stage = 1;
       *M.st = K;
       A.cond_list[atomicAdd(A.n_cond, 1)] = m;      // (the order of the list is the order the hardware ran the workgroups in: every entry is independent work)
@@ -1148,11 +886,7 @@ __global__ void __launch_bounds__(KD_THREADS, KD_COND_WGS) landing_kd_condense_k
   for (int w = blockIdx.x; w < total; w += gridDim.x) {
     const int m = A.cond_list[w / N], k = w % N;
     const KdMem M = kd_carve(N, A.ws + (size_t)m * A.ws_stride);
-#if KD_COND_DENSE
-    kd_condense_rows(M, N, k);
-#else
     kd_condense_rows_sparse(M, N, k, A.jpat, A.cpat);
-#endif
     __syncthreads();
   }
 }
@@ -1179,24 +913,11 @@ __global__ void __launch_bounds__(KD_THREADS, 2) landing_kd_iter_kernel(KdSolveA
   for (;;) {
     const bool ok = kd_backward(M, N, cost, K.delta);
     KD_BEGIN()
-      K.fact_ok = ok ? 1 : 0;
-      if (K.attempt == 0) K.first_failed = (K.skipped_zero && !ok) ? 1 : 0;
-      K.attempt++;
-      K.flag = 0;
-      if (!ok && K.attempt < 60) {
-        double d = K.delta; const double dl = K.delta_last;
-        const bool adapt = K.feas && o.feas_delta_dec > 0.0;
-        if (d == 0.0) d = (dl == 0.0) ? o.delta_init : fmax(1e-20, dl * (adapt ? K.fdc : o.delta_dec));
-        else if (adapt && K.attempt == 1 && d < dl) d = dl;      // inside the phase: the regularisation of the last iteration is the best guess of what this one needs
-#if KD_DELTA_JUMP > 0
-        // the first failure at the proximal floor is IPOPT's failure at delta = 0: continue from the last successful regularisation (if that was at
-        // most KD_DELTA_JUMP iterations ago), not fourfold from the floor -- a member that needs delta ~ 1e2 .. 1e4 in its first barrier problem
-        // re-probes the floor every ninth iteration (need_reg_streak) and spent up to eight attempts = three rounds of the lock-step loop on the way back
-        else if (K.attempt == 1 && dl * o.delta_dec > d * o.delta_inc && K.it - K.reg_it <= KD_DELTA_JUMP) d = dl * o.delta_dec;
-#endif
-        else d *= (dl == 0.0 ? o.delta_inc_first : o.delta_inc);
-        if (!(d > 1e40)) { K.delta = d; K.flag = 1; K.nfact++; }
-      }
+      // the first failure at the proximal floor is IPOPT's failure at delta = 0: continue from the last successful regularisation (if that was at
+      // most KD_DELTA_JUMP iterations ago), not fourfold from the floor -- a member that needs delta ~ 1e2 .. 1e4 in its first barrier problem
+      // re-probes the floor every ninth iteration (need_reg_streak) and spent up to eight attempts = three rounds of the lock-step loop on the way back
+      K.flag = ipm_next_delta(K, o, ok, K.it - K.reg_it <= KD_DELTA_JUMP ? K.delta_last * o.delta_dec : 0.0) ? 1 : 0;
+      if (K.flag) K.nfact++;
     KD_END();
     if (!K.flag) break;
     if (++tries >= KD_TRIES_PER_ROUND) {
@@ -1213,12 +934,7 @@ __global__ void __launch_bounds__(KD_THREADS, 2) landing_kd_iter_kernel(KdSolveA
     if (tid == 0) { K.status = K.stalled ? LANDING_STALLED : LANDING_NUMERICAL; K.done = 1; *M.st = K; A.done[m] = 1; }
     return;
   }
-  KD_BEGIN()
-    const bool adapt = K.feas && o.feas_delta_dec > 0.0;
-    if (adapt) K.fdc = K.attempt <= 1 ? fmax(o.feas_delta_dec, K.fdc * K.fdc) : fmin(0.7, sqrt(K.fdc));      // (attempt counts the factorisations of this iteration)
-    if (K.delta > (K.feas ? 0.0 : o.delta_floor)) { K.delta_last = K.delta; K.reg_it = K.it; K.need_reg_streak++; } else K.need_reg_streak = 0;
-    if (K.need_reg_streak > 8) K.need_reg_streak = adapt ? 2 : 0;      // (no probe of delta_w = 0 inside the phase: the elastic problem has no objective)
-  KD_END();
+  KD_BEGIN() if (ipm_commit_delta(K, o, K.feas ? 0.0 : o.delta_floor)) K.reg_it = K.it; KD_END();      // (a regularisation is one above the proximal floor)
   KD_PROF(2);
   kd_forward(M, N, lbm, A.jpat);
   KD_PROF(3);
@@ -1340,29 +1056,7 @@ __global__ void __launch_bounds__(KD_THREADS, 2) landing_kd_iter_kernel(KdSolveA
     }
     if (tid < 12 && !feas) { const double d = M.xt[12 * N + tid] - cost[12 + tid]; ft = cost[tid] * d * d; }
     { double v[3] = {tht, bt, ft}; const int op[3] = {RSUM, RSUM, RSUM}; block_reduce<3>(v, op, S.red); tht = v[0]; bt = v[1]; ft = v[2]; }
-    KD_BEGIN_SYNCED()
-      K.ntrial++;
-      const double th_min = 1e-4, th_floor = o.theta_floor * o.tol;
-      const double th0 = K.th0, ph0 = K.ph0, dphi = K.dphi;
-      const int nfilt = K.nfilt;
-      const double pht = ft + mu * bt;
-      bool ok_f = (tht <= K.th_max) && (pht < 1e300) && (pht > -1e300) && (tht < 1e300);
-      for (int e = 0; e < nfilt && ok_f; ++e) if (tht >= fmax(K.filt_th[e], th_floor) && pht >= K.filt_ph[e]) ok_f = false;
-      const bool switching = (dphi < 0.0) && (th0 <= th_min) && (alpha * pow(-dphi, 2.3) > 1.0 * pow(th0, 1.1));
-      bool accepted = false, done = false;
-      if (ok_f) {
-        if (switching) { if (pht <= ph0 + 1e-8 * alpha * dphi) { accepted = true; K.armijo_step = 1; } }
-        else if (tht <= fmax((1.0 - 1e-5) * th0, th_floor) || pht <= ph0 - 1e-8 * th0) accepted = true;
-      }
-      if (K.force_step && ok_f) { accepted = true; K.nfilt = 0; done = true; }      // watchdog: the step to the boundary is taken (it must still pass theta_max and the filter entries)
-      if (accepted) done = true;
-      K.need_corr = 0;
-      if (!done) {
-        if (o.slack_corr > 0.0 && !K.feas && alpha == K.a_pr && tht >= th0) { K.need_corr = 1; K.ft = ft; }
-        else { K.alpha = alpha * 0.5; if (!(K.alpha > 1e-10)) done = true; }
-      }
-      K.accepted = accepted ? 1 : 0; K.ls_done = done ? 1 : 0;
-    KD_END();
+    KD_BEGIN_SYNCED() K.ntrial++; ipm_ls_test(K, o, tht, ft, bt, K.filt_th, K.filt_ph); KD_END();
     if (K.need_corr) {
       // slack correction (landing_nlp.h): the rejected first trial point once more with the inequality slacks moved to g(x_trial)
       double tht2 = 0.0, bt2 = 0.0;
@@ -1377,36 +1071,10 @@ __global__ void __launch_bounds__(KD_THREADS, 2) landing_kd_iter_kernel(KdSolveA
         bt2 -= log((lb > -INF ? s - lb : 1.0) * (ub < INF ? ub - s : 1.0));
       }
       { double v[2] = {tht2, bt2}; const int op[2] = {RSUM, RSUM}; block_reduce<2>(v, op, S.red); tht2 = v[0]; bt2 = v[1]; }
-      KD_BEGIN_SYNCED()
-        const double th_floor = o.theta_floor * o.tol, th0 = K.th0, ph0 = K.ph0;
-        const int nfilt = K.nfilt;
-        const double pht2 = K.ft + mu * bt2;
-        bool ok2 = (tht2 <= K.th_max) && (pht2 < 1e300) && (pht2 > -1e300);
-        for (int e = 0; e < nfilt && ok2; ++e) if (tht2 >= fmax(K.filt_th[e], th_floor) && pht2 >= K.filt_ph[e]) ok2 = false;
-        if (ok2 && (tht2 <= fmax((1.0 - 1e-5) * th0, th_floor) || pht2 <= ph0 - 1e-8 * th0)) { K.accepted = 1; K.s_corr = o.slack_corr; K.ls_done = 1; }
-        else { K.alpha = alpha * 0.5; if (!(K.alpha > 1e-10)) K.ls_done = 1; }
-      KD_END();
+      KD_BEGIN_SYNCED() ipm_ls_corr_test(K, o, tht2, bt2, K.filt_th, K.filt_ph); KD_END();
     }
   }
-  KD_BEGIN()
-    const double a_pr = K.a_pr;
-    K.force_step = 0;
-    if (o.watchdog > 0 && !K.feas) {
-      if (K.accepted && K.alpha <= 0.0625 * a_pr) { if (++K.cutstreak >= o.watchdog) { K.force_step = 1; K.cutstreak = 0; K.wd_count++; } }
-      else K.cutstreak = 0;
-    }
-    K.fallback = 0;
-    if (!K.accepted) { K.nfilt = 0; K.alpha = fmin(a_pr, o.alpha_fallback); K.fallback = 1; }
-    else if (!K.armijo_step) {
-      int nfilt = K.nfilt;
-      if (nfilt == KD_FILT) { for (int e = 0; e + 1 < KD_FILT; ++e) { K.filt_th[e] = K.filt_th[e + 1]; K.filt_ph[e] = K.filt_ph[e + 1]; } nfilt = KD_FILT - 1; }
-      K.filt_th[nfilt] = (1.0 - 1e-5) * K.th0; K.filt_ph[nfilt] = K.ph0 - 1e-8 * K.th0;
-      K.nfilt = nfilt + 1;
-    }
-    if (o.dual_step_cap > 0.0) K.a_du = fmin(K.a_du, o.dual_step_cap * K.alpha);
-    K.full_prev = (K.accepted && K.alpha == 1.0 && K.a_du == 1.0 && K.attempt <= 1) ? 1 : 0;
-    if (o.feas_jam > 0) K.fjam = (!K.feas && K.alpha < 1e-2) ? K.fjam + 1 : (K.fjam > 2 ? K.fjam - 2 : 0);
-  KD_END();
+  KD_BEGIN() ipm_ls_end(K, o, K.filt_th, K.filt_ph, KD_FILT); KD_END();
   if (K.fallback) {
     const double alpha = K.alpha;
     for (int i = tid; i < nx; i += NT) M.xt[i] = M.x[i] + alpha * M.dx[i];

@@ -17,6 +17,7 @@
 #include <math.h>
 
 #include "../../include/landing_nlp.h"
+#include "ipm_core.hpp"
 
 // inlining policy of the solver's phase functions (development switches; the defaults are what the product build uses).
 // Measured round 3, A/B on one box: with every phase inlined into landing_ipm_kernel the callee-saved-register traffic disappears
@@ -111,54 +112,6 @@ struct SolveArgs {
   const int* order;      // dispatch order: workgroup b solves member order[b] (hard-first, see landing_order_kernel); nullptr = identity
 };
 
-// ---- block-wide reductions through LDS (deterministic order), K values at once ----------------------
-enum { RSUM = 0, RMAX = 1, RMIN = 2 };
-__device__ __forceinline__ double red_op(double a, double b, int op) { return op == RSUM ? a + b : (op == RMAX ? fmax(a, b) : fmin(a, b)); }
-template <int K>
-__device__ __forceinline__ void block_reduce(double (&v)[K], const int (&op)[K], double* red) {
-  const int tid = threadIdx.x, nwave = (blockDim.x + 63) >> 6;
-  for (int i = 0; i < K; ++i) {
-#pragma unroll
-    for (int mask = 32; mask >= 1; mask >>= 1) v[i] = red_op(v[i], __shfl_xor(v[i], mask), op[i]);   // butterfly: every lane gets the wave result
-  }
-  if ((tid & 63) == 0) for (int i = 0; i < K; ++i) red[(tid >> 6) * K + i] = v[i];
-  __syncthreads();
-  for (int i = 0; i < K; ++i) {
-    double r = red[i];
-    for (int w = 1; w < nwave; ++w) r = red_op(r, red[w * K + i], op[i]);
-    v[i] = r;
-  }
-  __syncthreads();
-}
-__device__ __forceinline__ double block_reduce1(double v, int op, double* red) {
-  double a[1] = {v}; const int o[1] = {op};
-  block_reduce<1>(a, o, red);
-  return a[0];
-}
-
-// The four largest of a set of values spread over the block (clip_k rule of the primal step length): every thread keeps
-// a sorted quadruple t[0] >= .. >= t[3]; the merge is a max-type operation, hence independent of the order.
-__device__ __forceinline__ void top4_push(double (&t)[4], double v) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { const double hi = fmax(t[i], v); v = fmin(t[i], v); t[i] = hi; }
-}
-__device__ __forceinline__ void block_top4(double (&t)[4], double* red) {
-  const int tid = threadIdx.x, nwave = (blockDim.x + 63) >> 6;
-#pragma unroll
-  for (int mask = 32; mask >= 1; mask >>= 1) {
-    double o[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] = __shfl_xor(t[i], mask);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) top4_push(t, o[i]);
-  }
-  if ((tid & 63) == 0) for (int i = 0; i < 4; ++i) red[(tid >> 6) * 4 + i] = t[i];
-  __syncthreads();
-  for (int i = 0; i < 4; ++i) t[i] = red[i];
-  for (int w = 1; w < nwave; ++w) for (int i = 0; i < 4; ++i) top4_push(t, red[w * 4 + i]);
-  __syncthreads();
-}
-
 struct MemberMem {
   double *x, *xt, *dx, *gx;
   double *g, *gt, *s, *ds, *zL, *zU, *y, *yn, *sig, *rho;
@@ -178,33 +131,12 @@ __device__ __forceinline__ MemberMem carve(const Layout& L, double* w) {
   return M;
 }
 
-// Scalar state of the interior-point loop, kept in LDS (S.ks) and never in registers across phases.  Every thread reads it in
-// place; ONLY thread 0 writes it, inside KS_BEGIN / KS_END blocks that are fenced by barriers on both sides -- so the scalar
-// control logic of the solver (error test, restarts, barrier update, regularisation schedule, filter, watchdog) runs once per
-// workgroup instead of 256 times, and no value is live across a phase.  Round 2 held these ~45 scalars in VGPRs: the kernel body
-// alone carried 767 static scratch (private-segment) accesses around its calls, executed every iteration by all 256 threads
+// Scalar state of the interior-point loop, kept in LDS (S.ks: the fields both solvers keep, ipm_core.hpp IpmCtl) and never in registers
+// across phases.  Every thread reads it in place; ONLY thread 0 writes it, inside KS_BEGIN / KS_END blocks that are fenced by barriers on
+// both sides -- so the scalar control logic of the solver (error test, restarts, barrier update, regularisation schedule, filter, watchdog)
+// runs once per workgroup instead of 256 times, and no value is live across a phase.  Round 2 held these ~45 scalars in VGPRs: the kernel
+// body alone carried 767 static scratch (private-segment) accesses around its calls, executed every iteration by all 256 threads
 // (VERDICT r2 item 8); now 233, none of them on the per-iteration path of the row passes.
-struct IpmState {
-  double mu, delta_last, th_max, c_pr, c_co, c_cm, c_ys, c_zs, c_nz, e_pr, e_du, e_co;
-  double tau, omt, a_pr, a_du, th0, ph0, dphi, alpha, s_corr, delta, ft;
-  long long tp;
-  int nfilt, it, status, need_reg_streak, nreset, last_reset_it, ncrawl, clip_k_cur, last_mu_it, cutstreak, wd_count, first_failed, force_step;
-  int clip_now, accepted, armijo_step, fact_ok, skipped_zero, attempt;
-  int jamrun, stag, full_prev;      // jam_clip / stag_relief (landing_nlp.h): iterations in a row with a tiny step to the boundary; full steps of the last barrier problem that did not halve the error
-  double e_prev;
-  int action, flag, fresh, ls_done, need_corr, fallback;
-  // feasibility (restoration) phase, landing_nlp.h: 1 while the elastic problem is being solved; lim = iteration limit in force
-  int feas, feas_used, lim, fact_failed;
-  int fjam, fstat; double v1_ref;      // feas_jam / feas_stat (landing_nlp.h): leaky count of iterations with a tiny accepted step; iterations with a stationary violation, its reference value
-  double c_rn, f_vmax, f_v1;      // |z + w - rho|_inf of the elastic rows; max-norm and 1-norm violation of the inequality rows at x
-  // round 6 (landing_nlp.h: feas_max, feas_back, feas_resume, feas_polish): entries into the phase so far; 1 once a stalled phase has handed its point back (or the
-  // line search jammed with no entry left); 1 once the regularisation was dropped at a stationary violation; violation at the entry point (1-norm, equality rows
-  // included) and 1-norm residual of the equality rows at x; iteration count nothing runs beyond; 1: the entry pass of the phase has to record th_entry
-  int n_feas, stalled, polished, hard_lim, want_entry; double th_entry, f_theq;
-  double fdc;      // factor between the regularisation of the last iteration and the first one tried in this one inside the phase (feas_delta_dec, adapted: squared after an
-                   // iteration whose first factorisation succeeded, square root (<= 0.7) after one that needed more)
-};
-enum { ACT_GO = 0, ACT_STOP = 1, ACT_RESET = 2, ACT_FEAS = 3, ACT_BACK = 4 };
 
 // LDS of one member
 constexpr int FWD_DXL_NMAX = 64;   // horizons up to this keep a copy of dx in LDS for row_products: 36 N + 12 doubles in [P | A1 | A^]
@@ -245,7 +177,10 @@ struct Lds {
   // that every row pass used to stream (6 of ~30 array passes per iteration)
   double bnd_lb[36 + 2 * 104], bnd_ub[36 + 2 * 104];
   MemberMem M; Layout L; const double* p; int prof_on;
-  IpmState ks;
+  IpmCtl ks;
+  // control fields of this solver alone (written like ks): clip_k rule in force; jam_clip (landing_nlp.h): iterations in a row with a tiny step
+  // to the boundary; what the stop test decided (ACT_*); no regularisation made the last step computable
+  int clip_now, jamrun, action, fact_failed;
   unsigned long long atab_mid[ATAB_LTMAX * SOLVER_THREADS];      // (behind everything the tables address: their offsets are 16 bits)
   unsigned long long acomb_mid[SOLVER_THREADS];
 };
@@ -274,7 +209,6 @@ __host__ __device__ inline unsigned long long acomb_pack(int n, int s0, int d, b
 // fp64 matrix-core tile: D(16x16) = C + A(16 x 4KT) B(4KT x 16) with v_mfma_f64_16x16x4_f64.  Operand layout
 // (cdna_hip_programming.md section 3): lane l supplies A[i = l&15][k = l>>4] and B[k = l>>4][j = l&15]; the accumulator holds
 // D[row = (l>>4) + 4r][col = l&15], r = 0..3.  fa(i,k) / fb(k,j) fetch operands (LDS, zero outside the matrix).
-typedef double f64x4 __attribute__((vector_size(32)));
 template <int KT, class FA, class FB>
 __device__ __forceinline__ f64x4 mfma_tile(f64x4 c, FA fa, FB fb) {
   const int l = threadIdx.x & 63, ij = l & 15, kq = l >> 4;
@@ -372,11 +306,6 @@ __device__ __noinline__ void gauss_jordan_wave(const double* G, const double* ga
 // thread).  Rounds 1-4 cut the term list into 256 equal chunks, one per thread, and a destination whose terms straddled chunk borders
 // was finished from per-thread carries in thread order; now a destination is summed by one thread, which restarts the partial sum
 // where those borders were (`bnd`), so every sum keeps its association.
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef const double __attribute__((address_space(1)))* landing_gptr;    // global address space: global_load, not flat_load
-#else                                                                     // (a flat load also ties up the LDS counter)
-typedef const double* landing_gptr;
-#endif
 constexpr int ASM_SEG_LEN[7] = {NZ_JU - NZ_JX, NZ_JUN - NZ_JU, NZ_HX - NZ_JUN, NZ_HU - NZ_HX, NZ_HUN - NZ_HU, NZ_TOT - NZ_HUN, RUNC};
 constexpr int ASM_SEG_POS[7] = {NZ_JX, NZ_JU, NZ_JUN, NZ_HX, NZ_HU, NZ_HUN, NZ_TOT};
 static_assert(NZ_JUN - NZ_JU <= SOLVER_THREADS && 2 * 104 <= SOLVER_THREADS, "one load per thread and segment");
@@ -1103,23 +1032,6 @@ __device__ __noinline__ double rc_f(const double* x) {                 // runnin
   return f;
 }
 
-// ---- feasibility (restoration) phase: one side of an elastic inequality row ------------------------------------------------------
-// The row  lb <= s  becomes  a = s - lb + n >= 0,  n >= 0  with the price rho_pen * n  (upper side: b = ub + q - s, q >= 0); multipliers
-// z (of a >= 0) and w (of n >= 0), stationarity  rho_pen - z - w = 0.  Eliminating (dn, dw) from the primal-dual Newton system leaves
-//   dz = c - sd * (z / D) ds,   D = a + z n / w,   c = (mu - a z - z (mu - n w + n (z + w - rho_pen)) / w) / D
-// (sd = +1 lower side, -1 upper side: d(dist) = sd ds + dn), i.e. the row enters the condensed system with sigma = z / D exactly like
-// a plain slack row with sigma = z / d -- condensation, Riccati sweep and forward sweep are those of the normal iteration.
-struct ElStep { double dz, dw, dn, da; };
-__device__ __forceinline__ ElStep el_step(double sd, double a, double n, double z, double w, double mu, double rho_pen, double ds) {
-  ElStep e;
-  const double D = a + z * n / w, rn = z + w - rho_pen;
-  e.dz = (mu - a * z - z * (mu - n * w + n * rn) / w - sd * z * ds) / D;
-  e.dw = -e.dz - rn;
-  e.dn = (mu - n * w - n * e.dw) / w;
-  e.da = sd * ds + e.dn;
-  return e;
-}
-
 // Workgroups per CU the register budget is sized for.  Measured on MI355X (N = 40, end of round 1, IPRA off): 2 per CU
 // (256 VGPRs) beats 3 (168) at batch 1024 -- 5220 vs 4760 NLPs/s -- and ties beyond (2048: 5410 vs 5330, 8192: 7080 vs
 // 7050); 4 per CU (128 VGPRs, and the 46 KB of LDS would only fit three) is far behind.  Every phase is latency-bound:
@@ -1219,50 +1131,16 @@ __global__ void __launch_bounds__(SOLVER_THREADS, LANDING_MIN_WAVES) landing_ipm
   __syncthreads();
   member_eval_g_rare(L, M.x, p, M.g);
   __syncthreads();
-  auto init_slacks = [&]() {     // slack pushed into the interior (IPOPT bound_push/frac), z = 1, y = z_U - z_L, y_dyn = 0
-    for (int r = lane; r < ng; r += NT) {
-      const double lb = S.bnd_lb[bidx(r)], ub = S.bnd_ub[bidx(r)];
-      double sv = 0.0, zl = 0.0, zu = 0.0;
-      if (r >= 12 && lb != ub) {
-        const bool hL = lb > -INF, hU = ub < INF;
-        sv = M.g[r];
-        double pl, pu;
-        if (hL && hU) { pl = fmin(o.bound_push * fmax(1.0, fabs(lb)), o.bound_frac * (ub - lb)); pu = fmin(o.bound_push * fmax(1.0, fabs(ub)), o.bound_frac * (ub - lb)); }
-        else { pl = o.bound_push * fmax(1.0, hL ? fabs(lb) : 0.0); pu = o.bound_push * fmax(1.0, hU ? fabs(ub) : 0.0); }
-        if (hL) sv = fmax(sv, lb + pl);
-        if (hU) sv = fmin(sv, ub - pu);
-        zl = hL ? 1.0 : 0.0; zu = hU ? 1.0 : 0.0;
-      }
-      M.s[r] = sv; M.zL[r] = zl; M.zU[r] = zu; M.y[r] = zu - zl;
-    }
+  // slacks pushed into the interior, z = 1, y = z_U - z_L, y_dyn = 0; back: at the point a feasibility phase hands back (ipm_init_row)
+  auto init_slacks = [&](bool back, double mu_) {
+    for (int r = lane; r < ng; r += NT) { const double lb = S.bnd_lb[bidx(r)], ub = S.bnd_ub[bidx(r)]; ipm_init_row(M, r, r >= 12 && lb != ub, lb, ub, o, back, mu_); }
     __syncthreads();
   };
-  // ... at the point a feasibility phase hands back (landing_nlp.h, feas_ret_push): slacks pushed only feas_ret_push off their bounds, bound multipliers
-  // mu / distance -- what the phase gained in feasibility is kept
-  auto init_slacks_return = [&](double mu_) {
-    const double push = o.feas_ret_push;
-    for (int r = lane; r < ng; r += NT) {
-      const double lb = S.bnd_lb[bidx(r)], ub = S.bnd_ub[bidx(r)];
-      double sv = 0.0, zl = 0.0, zu = 0.0;
-      if (r >= 12 && lb != ub) {
-        const bool hL = lb > -INF, hU = ub < INF;
-        sv = M.g[r];
-        double pl, pu;
-        if (hL && hU) { pl = fmin(push * fmax(1.0, fabs(lb)), push * (ub - lb)); pu = fmin(push * fmax(1.0, fabs(ub)), push * (ub - lb)); }
-        else { pl = push * fmax(1.0, hL ? fabs(lb) : 0.0); pu = push * fmax(1.0, hU ? fabs(ub) : 0.0); }
-        if (hL) sv = fmax(sv, lb + pl);
-        if (hU) sv = fmin(sv, ub - pu);
-        zl = hL ? fmin(fmax(mu_ / (sv - lb), 1e-8), 1e3) : 0.0; zu = hU ? fmin(fmax(mu_ / (ub - sv), 1e-8), 1e3) : 0.0;
-      }
-      M.s[r] = sv; M.zL[r] = zl; M.zU[r] = zu; M.y[r] = zu - zl;
-    }
-    __syncthreads();
-  };
-  init_slacks();
+  init_slacks(false, 0.0);
   // primal / complementarity errors, Sigma and rho of the CURRENT point for barrier parameter mu_ (one pass over the
   // rows; the accept pass below produces the same quantities for the next iterate, so this runs only at the start,
   // after a multiplier reset and when mu changes)
-  IpmState& K = S.ks;
+  IpmCtl& K = S.ks;
   // K is written by thread 0 only, between barriers (all other threads only read it, after the closing barrier)
 #define KS_BEGIN() __syncthreads(); if (lane == 0) {
 #define KS_BEGIN_SYNCED() if (lane == 0) {      /* directly behind a barrier (block_reduce / block_top4 end with one) */
@@ -1280,43 +1158,13 @@ __global__ void __launch_bounds__(SOLVER_THREADS, LANDING_MIN_WAVES) landing_ipm
   // the same for the elastic problem of the feasibility phase (plain row loops: the phase is rare); also leaves the violation of the
   // inequality rows at x (max norm, 1-norm) and |z + w - rho_pen|_inf in K
   auto feas_point_pass = [&](double mu_) {
-    const double frho = o.feas_rho;
-    double pr = 0.0, co = 0.0, cm = 0.0, rn = 0.0, ys = 0.0, zs = 0.0, nz = 0.0, vmax = 0.0, v1 = 0.0, teq = 0.0;
+    ElAcc e{};
     for (int r = lane; r < ng; r += NT) {
-      const double lb = S.bnd_lb[bidx(r)], ub = S.bnd_ub[bidx(r)];
       double sg = 0.0, rh = 0.0;
-      if (r >= 12) {
-        const double g = r_g[r];
-        ys += fabs(r_y[r]);
-        if (lb == ub) { pr = fmax(pr, fabs(g - lb)); teq += fabs(g - lb); }
-        else {
-          const double s = r_s[r], v = fmax(fmax(lb - g, g - ub), 0.0);
-          pr = fmax(pr, fabs(g - s)); vmax = fmax(vmax, v); v1 += v;
-          if (lb > -INF) {
-            const double n = M.en[r], a = s - lb + n, z = r_zL[r], w = M.wn[r], D = a + z * n / w;
-            const double c = (mu_ - a * z - z * (mu_ - n * w + n * (z + w - frho)) / w) / D;
-            co = fmax(co, fmax(a * z, n * w)); cm = fmax(cm, fmax(fabs(a * z - mu_), fabs(n * w - mu_))); rn = fmax(rn, fabs(z + w - frho));
-            sg += z / D; rh -= z + c; zs += z; nz += 1.0;
-          }
-          if (ub < INF) {
-            const double q = M.ep[r], b = ub + q - s, z = r_zU[r], w = M.wp[r], D = b + z * q / w;
-            const double c = (mu_ - b * z - z * (mu_ - q * w + q * (z + w - frho)) / w) / D;
-            co = fmax(co, fmax(b * z, q * w)); cm = fmax(cm, fmax(fabs(b * z - mu_), fabs(q * w - mu_))); rn = fmax(rn, fabs(z + w - frho));
-            sg += z / D; rh += z + c; zs += z; nz += 1.0;
-          }
-          rh += sg * (g - s);
-        }
-      }
+      if (r >= 12) el_point_row(e, M, r, S.bnd_lb[bidx(r)], S.bnd_ub[bidx(r)], mu_, o.feas_rho, sg, rh);
       r_sig[r] = sg; r_rho[r] = rh;
     }
-    double v[6] = {pr, co, cm, ys, zs, nz}; const int op[6] = {RMAX, RMAX, RMAX, RSUM, RSUM, RSUM};
-    block_reduce<6>(v, op, S.red);
-    double u[4] = {rn, vmax, v1, teq}; const int op4[4] = {RMAX, RMAX, RSUM, RSUM};
-    block_reduce<4>(u, op4, S.red);
-    KS_BEGIN_SYNCED()
-      K.c_pr = v[0]; K.c_co = v[1]; K.c_cm = v[2]; K.c_ys = v[3]; K.c_zs = v[4]; K.c_nz = fmax(v[5], 1.0); K.c_rn = u[0]; K.f_vmax = u[1]; K.f_v1 = u[2]; K.f_theq = u[3];
-      if (K.want_entry) { K.th_entry = u[2] + u[3]; K.want_entry = 0; }      // first pass of a phase: the violation it starts from
-    KS_END();
+    el_point_finish(K, e, S.red);
   };
   auto point_pass = [&](double mu_) {
     if (K.feas) { feas_point_pass(mu_); return; }
@@ -1352,15 +1200,9 @@ __global__ void __launch_bounds__(SOLVER_THREADS, LANDING_MIN_WAVES) landing_ipm
   };
 
   if (lane == 0) {
+    ipm_init(K, o);
     K.tp = A.prof ? (long long)wall_clock64() : 0;
-    K.mu = o.mu_init; K.delta_last = 0.0; K.th_max = 0.0;
-    K.c_pr = 0.0; K.c_co = 0.0; K.c_cm = 0.0; K.c_ys = 0.0; K.c_zs = 0.0; K.c_nz = 1.0;
-    K.nfilt = 0; K.it = 0; K.status = LANDING_MAX_ITER; K.need_reg_streak = 0; K.nreset = 0; K.first_failed = 0;
-    K.last_reset_it = 0; K.ncrawl = 0; K.clip_k_cur = o.clip_k; K.last_mu_it = 0; K.cutstreak = 0; K.wd_count = 0; K.force_step = 0;
-    K.e_pr = 0; K.e_du = 0; K.e_co = 0;
-    K.jamrun = 0; K.stag = 0; K.full_prev = 0; K.e_prev = 1e300;
-    K.feas = 0; K.feas_used = 0; K.fact_failed = 0; K.lim = o.max_iter; K.fjam = 0; K.fstat = 0; K.v1_ref = 0.0; K.c_rn = 0.0; K.f_vmax = 0.0; K.f_v1 = 0.0;
-    K.n_feas = 0; K.stalled = 0; K.polished = 0; K.want_entry = 0; K.th_entry = 0.0; K.f_theq = 0.0; K.hard_lim = o.max_iter > 0 ? 3 * o.max_iter : 0; K.fdc = o.feas_delta_dec > 0.0 ? o.feas_delta_dec : o.delta_dec;
+    S.clip_now = 0; S.jamrun = 0; S.fact_failed = 0;
   }
   __syncthreads();
   // the lane = stage phases are called by the lanes that have work only: the callee-saved registers an out-of-line function touches
@@ -1384,94 +1226,17 @@ __global__ void __launch_bounds__(SOLVER_THREADS, LANDING_MIN_WAVES) landing_ipm
       double du = 0.0;
       for (int i = lane + 12; i < nx; i += NT) du = fmax(du, fabs(M.gx[i]));
       du = block_reduce1(du, RMAX, S.red);
-      KS_BEGIN_SYNCED()      // ---- what happens with this iterate: stop, restart, or another iteration
-        const double pr = K.c_pr, co = K.c_co, mu = K.mu;
-        const int it = K.it, nreset = K.nreset;
-        if (K.feas) du = fmax(du, K.c_rn);      // the elastic problem has the extra stationarity rows rho_pen - z - w = 0
-        K.e_pr = pr; K.e_du = du; K.e_co = co;
+      KS_BEGIN_SYNCED()      // ---- what happens with this iterate: stop, restart, into / out of the feasibility phase, or another iteration
+        ipm_errors(K, o, du);
 #if !defined(__HIP_DEVICE_COMPILE__) && defined(LANDING_EMU_TRACE)
-        if (getenv("LO_TRACE")) fprintf(stderr, "it %4d pr %9.2e du %9.2e co %9.2e mu %8.1e dlast %8.1e nreset %d nfilt %d feas %d fdc %.3f\n", it, pr, du, co, mu, K.delta_last, nreset, K.nfilt, K.feas, K.fdc);
+        if (getenv("LO_TRACE")) fprintf(stderr, "it %4d pr %9.2e du %9.2e co %9.2e mu %8.1e dlast %8.1e nreset %d nfilt %d feas %d fdc %.3f\n", K.it, K.e_pr, K.e_du, K.e_co, K.mu, K.delta_last, K.nreset, K.nfilt, K.feas, K.fdc);
 #endif
-        if (o.stag_relief > 0) {      // full Newton steps in the last barrier problem that do not halve the error: the proximal term is what holds them back
-          const double E = fmax(pr, du);
-          K.stag = (!K.feas && mu <= o.tol / 10.0 * 1.0000001 && K.full_prev && E > 0.5 * K.e_prev) ? K.stag + 1 : 0;
-          K.e_prev = E;
-        }
-        int act = ACT_GO;
-        bool give_up = false;
-        if (K.feas) {
-          // feasibility phase: a feasible point (or an elastic KKT point with negligible violation) restarts the solve from here, an elastic
-          // KKT point with positive violation is the certificate of local infeasibility
-          const bool conv = fmax(du, fmax(pr, co)) <= o.tol;
-          if (!(du < 1e300) || !(pr < 1e300) || !(co < 1e300)) { K.status = LANDING_NUMERICAL; act = ACT_STOP; }
-          else if (K.f_vmax <= 1e-9 && pr <= o.tol) act = ACT_BACK;
-          else if (conv && K.f_v1 > o.feas_cert) { K.status = LANDING_INFEASIBLE; act = ACT_STOP; }      // KKT point of the elastic problem with positive violation: the certificate
-          else if (conv) act = ACT_BACK;
-          else if (o.feas_back > 0.0 && !K.feas_used && K.f_v1 + K.f_theq <= o.feas_back * K.th_entry) act = ACT_BACK;      // the violation has come down: IPOPT leaves its restoration phase here
-          else if (o.feas_stat > 0) {      // stationary violation (landing_nlp.h): NOT a certificate
-            const double v1 = K.f_v1;
-            if (K.fstat < 0 || !(fabs(v1 - K.v1_ref) <= 0.05 * K.v1_ref)) { K.v1_ref = v1; K.fstat = 0; } else K.fstat++;
-            if (K.fstat >= o.feas_stat && mu <= 1e-4 && pr <= 1e-3) {
-              if (v1 <= o.feas_cert) act = ACT_BACK;
-              else if (o.feas_polish > 0.0 && !K.polished) {      // once: the regularisation drops -- a stationary point is then a few Newton steps from the elastic KKT point
-                K.polished = 1; K.fstat = -1; K.delta_last = o.feas_polish / (o.feas_delta_dec > 0.0 ? o.feas_delta_dec : o.delta_dec); K.need_reg_streak = 2;
-              }
-              else if (o.feas_resume && !K.stalled) { K.stalled = 1; K.feas_used = 1; act = ACT_BACK; }      // the interior-point iteration resumes from this point, once
-              else { K.status = LANDING_STALLED; act = ACT_STOP; }
-            }
-          }
-          if (act == ACT_GO && it >= K.lim) act = ACT_STOP;
-          if (act == ACT_BACK) {
-            K.feas = 0; K.lim = it + (o.max_iter > 1 ? o.max_iter : 1); if (K.lim > K.hard_lim) K.lim = K.hard_lim; K.status = LANDING_MAX_ITER;
-            K.mu = (o.feas_ret_push > 0.0 && o.feas_ret_mu > 0.0) ? o.feas_ret_mu : o.mu_init; K.fjam = 0; K.nfilt = 0; K.delta_last = 0.0; K.need_reg_streak = 0; K.wd_count = 0; K.th_max = 0.0; K.nreset = 0; K.last_reset_it = it; K.ncrawl = 0;
-            K.cutstreak = 0; K.force_step = 0;
-            K.it = it + 1;
-          }
-        }
-        else if (K.fact_failed) { K.status = LANDING_NUMERICAL; K.fact_failed = 0; give_up = true; }      // no regularisation made the last step computable
-        else if (!(du < 1e300) || !(pr < 1e300) || !(co < 1e300)) { K.status = LANDING_NUMERICAL; give_up = true; }
-        else if (fmax(du, fmax(pr, co)) <= o.tol) { K.status = LANDING_CONVERGED; act = ACT_STOP; }
-        else if (it >= K.lim) give_up = true;      // (>=: K.it runs ahead of a limit set from a max_iter < 1)
-        else if (du > o.reset_du && nreset >= o.max_resets && o.max_resets > 0) { K.status = LANDING_NUMERICAL; give_up = true; }   // jammed again: give up
-        else if (o.feas_jam > 0 && K.fjam >= o.feas_jam && pr > 1e-3 && o.feas_phase) { give_up = true; if (K.feas_used) K.stalled = 1; }      // jammed line search: the feasibility phase starts now (landing_nlp.h); no entry left: the solve ends here, status 4
-        else {
-          // crawling: still in the first barrier problem (mu never decreased) restart_period iterations after the last (re)start
-          const bool stalled = o.restart_period > 0 && it - K.last_reset_it >= o.restart_period && mu >= o.mu_init && nreset < o.max_resets && K.ncrawl < ((o.fresh_restart & 4) ? 2 : 1);
-          const bool overreg = o.reset_delta > 0.0 && K.delta_last > o.reset_delta && nreset < o.max_resets;
-          // a LATER barrier problem not solved 2 restart_period iterations after it began has wandered off (the dual infeasibility stays
-          // far below reset_du, nothing else catches it): restarted in place like a crawling iterate
-          const bool lost = (o.fresh_restart & 8) && o.restart_period > 0 && mu < o.mu_init && pr > 1e-3 && nreset < o.max_resets &&
-                            ((it - K.last_mu_it >= 2 * o.restart_period && it - K.last_reset_it >= o.restart_period) || K.wd_count >= 3);     // ... or crawls on although the watchdog has fired three times
-          if ((du > o.reset_du && nreset < o.max_resets) || stalled || overreg || lost) {
-            act = ACT_RESET;
-            K.last_reset_it = it;
-            if (stalled) K.ncrawl++;
-            // jammed iterate (multipliers blown up): keep x, re-initialise slacks, multipliers, barrier parameter and
-            // filter -- the role IPOPT's restoration phase plays on this problem class
-            K.nreset = nreset + 1;
-            // the restart in place did not help (second restart) or the iterate is jammed: back to the caller's initial guess with
-            // another step rule (landing_nlp.h: the members that fail from it with clip_k = 4 solve with clip_k = 2)
-            K.fresh = (((o.fresh_restart & 2) && nreset + 1 == 2) || ((o.fresh_restart & 1) && nreset + 1 == 1 && !stalled && !lost)) ? 1 : 0;
-            if (K.fresh) { if (K.clip_k_cur > 1) K.clip_k_cur = 2; K.th_max = 0.0; }
-            K.mu = o.mu_init; K.nfilt = 0; K.delta_last = 0.0; K.need_reg_streak = 0; K.wd_count = 0;
-            K.it = it + 1;
-          }
-        }
-        if (give_up) {
-          // the solve would end here as NUMERICAL / MAX_ITER: enter the feasibility phase once (landing_solver_opts::feas_phase)
-          if (K.stalled) K.status = LANDING_STALLED;      // the point a stalled phase handed back did not lead anywhere either
-          if (o.feas_phase && !K.feas_used && o.max_iter > 0 && it < K.hard_lim) {      // (max_iter < 1: the caller asked for no iteration at all, the phase would get none either)
-            act = ACT_FEAS;
-            K.feas = 1; K.n_feas++; K.feas_used = K.n_feas >= o.feas_max ? 1 : 0; K.status = LANDING_MAX_ITER; K.lim = it + o.max_iter; if (K.lim > K.hard_lim) K.lim = K.hard_lim; K.fstat = -1; K.fjam = 0; K.want_entry = 1; K.fdc = o.feas_delta_dec > 0.0 ? o.feas_delta_dec : o.delta_dec;
-            K.mu = o.mu_init; K.nfilt = 0; K.th_max = 0.0; K.delta_last = 0.0; K.need_reg_streak = 0; K.cutstreak = 0; K.force_step = 0; K.wd_count = 0;
-            K.it = it + 1;
-          } else act = ACT_STOP;
-        }
-        K.action = act;
+        S.action = ipm_decide(K, o, S.fact_failed != 0);      // (a failed factorisation hands over through fact_failed: the solve ends NUMERICAL or enters the phase)
+        S.fact_failed = 0;
       KS_END();
     }
-    if (K.action == ACT_STOP) break;
-    if (K.action == ACT_FEAS) {
+    if (S.action == ACT_STOP) break;
+    if (S.action == ACT_FEAS) {
       // ---- enter the feasibility phase from the current point (from the caller's initial guess when the iterate is not finite)
       double big = 0.0;
       for (int i = lane; i < nx; i += NT) { const double v = fabs(M.x[i]); big = fmax(big, v < 1e6 ? v : 1e300); }
@@ -1487,32 +1252,21 @@ __global__ void __launch_bounds__(SOLVER_THREADS, LANDING_MIN_WAVES) landing_ipm
       member_eval_g_rare(L, M.x, p, M.g);
       if (L.run_cost) for (int e = lane; e < N * RUNC; e += NT) M.Hc[e] = 0.0;      // no objective: its constant Hessian entries leave the condensation
       __syncthreads();
-      {
-        const double frho = o.feas_rho, mu0 = o.mu_init;
-        for (int r = lane + 12; r < ng; r += NT) {
-          const double lb = S.bnd_lb[bidx(r)], ub = S.bnd_ub[bidx(r)], g = M.g[r];
-          if (lb == ub) { M.y[r] = 0.0; continue; }
-          // slack on the row value; violation variables sized so that both distances start at a comfortable value
-          double zl = 0.0, zu = 0.0, n0 = 0.0, q0 = 0.0, wl = 0.0, wu = 0.0;
-          if (lb > -INF) { const double v = lb - g; n0 = fmax(v, 0.0) + fmax(1e-2, 0.1 * fabs(v)); zl = fmin(mu0 / (g - lb + n0), 0.5 * frho); wl = frho - zl; }
-          if (ub < INF) { const double v = g - ub; q0 = fmax(v, 0.0) + fmax(1e-2, 0.1 * fabs(v)); zu = fmin(mu0 / (ub + q0 - g), 0.5 * frho); wu = frho - zu; }
-          M.s[r] = g; M.en[r] = n0; M.ep[r] = q0; M.zL[r] = zl; M.zU[r] = zu; M.wn[r] = wl; M.wp[r] = wu; M.y[r] = zu - zl;
-        }
-      }
+      for (int r = lane + 12; r < ng; r += NT) el_init_row(M, r, S.bnd_lb[bidx(r)], S.bnd_ub[bidx(r)], o.mu_init, o.feas_rho);
       __syncthreads();
       point_pass(K.mu);
       continue;
     }
-    if (K.action == ACT_BACK) {
+    if (S.action == ACT_BACK) {
       // ---- a feasible point (or negligible violation): the interior-point solve restarts from it
       if (L.run_cost) rc_init_hc();
       for (int r = lane + 12; r < ng; r += NT) if (S.bnd_lb[bidx(r)] == S.bnd_ub[bidx(r)]) M.y[r] = 0.0;
       __syncthreads();
-      if (o.feas_ret_push > 0.0) init_slacks_return(K.mu); else init_slacks();
+      init_slacks(o.feas_ret_push > 0.0, K.mu);
       point_pass(K.mu);
       continue;
     }
-    if (K.action == ACT_RESET) {
+    if (S.action == ACT_RESET) {
       if (K.fresh) {
         for (int i = lane; i < nx; i += NT) {
           double v = A.x0[(size_t)m * nx + i];
@@ -1523,28 +1277,13 @@ __global__ void __launch_bounds__(SOLVER_THREADS, LANDING_MIN_WAVES) landing_ipm
         member_eval_g_rare(L, M.x, p, M.g);
         __syncthreads();
       }
-      init_slacks();
+      init_slacks(false, 0.0);
       point_pass(K.mu);
       continue;
     }
     // ---------------------------------------------------------------- barrier parameter (monotone)
     for (;;) {
-      KS_BEGIN()
-        double sd = 1.0, sc = 1.0;      // IPOPT's scaling of the optimality error in the barrier-subproblem test (landing_nlp.h)
-        if (o.barrier_smax > 0.0) {
-          sd = fmax(o.barrier_smax, (K.c_ys + K.c_zs) / ((double)(ng - 12) + K.c_nz)) / o.barrier_smax;
-          sc = fmax(o.barrier_smax, K.c_zs / K.c_nz) / o.barrier_smax;
-        }
-        const double mu = K.mu;
-        if (fmax(K.e_du / sd, fmax(K.c_pr, K.c_cm / sc)) <= o.kappa_eps * mu && mu > o.tol / 10.0) {
-          K.mu = fmax(o.tol / 10.0, fmin(o.kappa_mu * mu, pow(mu, o.theta_mu)));
-          K.nfilt = 0; K.last_mu_it = K.it; K.wd_count = 0;
-          K.flag = 1;
-        } else {
-          K.flag = 0;
-          K.tau = fmax(o.tau_min, 1.0 - mu);
-        }
-      KS_END();
+      KS_BEGIN() K.flag = ipm_barrier_update(K, o, ng - 12) ? 1 : 0; KS_END();
       if (!K.flag) break;
       point_pass(K.mu);                     // complementarity error, Sigma, rho for the new mu
     }
@@ -1554,54 +1293,25 @@ __global__ void __launch_bounds__(SOLVER_THREADS, LANDING_MIN_WAVES) landing_ipm
     { const int rc = (L.run_cost && !K.feas) ? 1 : 0; if (lane == 0) S.rc_on = rc; if (rc) rc_add_gamma(); __syncthreads(); }   // gradient of the running cost for the stage right-hand sides
     PROF_ADD(PH_SIGRHO, K.tp);
     // ================================================================ Riccati factorisation with inertia correction
-    // IPOPT's inertia-correction schedule (delta_w = 0 first, then max(1e-20, delta_last/3), then x8 / x100),
-    // except that an iteration following a regularised one starts from delta_last/3 directly when the
-    // unregularised attempt failed twice in a row (saves one full factorisation in nonconvex phases)
-    // (o.sticky_delta = 1: when the first trial of the previous iteration failed, start from delta_last itself)
+    // IPOPT's inertia-correction schedule (ipm_core.hpp); o.sticky_delta = 1: when the first trial of the previous iteration failed, start from delta_last itself
     KS_BEGIN()
-      const double dl = K.delta_last;
-      const double ddec = (K.feas && o.feas_delta_dec > 0.0) ? K.fdc : o.delta_dec;      // (the elastic problem has flat directions: its regularisation has to fall faster, landing_nlp.h)
-      K.delta = (K.need_reg_streak >= 2 && dl > 0.0) ? fmax(1e-20, dl * ((o.sticky_delta && K.first_failed) ? 1.0 : ddec)) : 0.0;
-      if (!L.run_cost && !K.feas) {      // proximal term of the terminal-cost form (landing_nlp.h)
-        double fl = o.delta_floor;
-        if (o.stag_relief > 0 && K.stag >= o.stag_relief) {      // ... a tenth of it per stagnating iteration
-          for (int e = K.stag - o.stag_relief; e >= 0 && fl >= 1e-12; --e) fl *= 0.1;
-          if (fl < 1e-12) fl = 0.0;
-        }
-        K.delta = fmax(K.delta, fl);
-      }
-      K.skipped_zero = K.delta > 0.0;
-      K.fact_ok = 0; K.attempt = 0; K.flag = 1;
+      ipm_first_delta(K, o, (o.sticky_delta && K.first_failed) ? 1.0 : ipm_delta_dec(K, o), (!L.run_cost && !K.feas) ? o.delta_floor : 0.0);      // (proximal term of the terminal-cost form, landing_nlp.h)
       S.prof[PH_NFACT] += 1.0;
     KS_END();
     for (;;) {
       const bool ok = riccati_backward(K.delta);
       KS_BEGIN()
-        K.fact_ok = ok ? 1 : 0;
-        if (K.attempt == 0) K.first_failed = (K.skipped_zero && !ok) ? 1 : 0;
-        K.attempt++;
-        K.flag = 0;
-        if (!ok && K.attempt < 60) {      // next attempt with a larger regularisation
-          double d = K.delta; const double dl = K.delta_last;
-          if (d == 0.0) d = (dl == 0.0) ? o.delta_init : fmax(1e-20, dl * ((K.feas && o.feas_delta_dec > 0.0) ? K.fdc : o.delta_dec));
-          else if (K.feas && o.feas_delta_dec > 0.0 && K.attempt == 1 && d < dl) d = dl;      // the regularisation of the last iteration is the best guess of what this one needs
-          else d *= (dl == 0.0 ? o.delta_inc_first : o.delta_inc);
-          if (!(d > 1e40)) { K.delta = d; K.flag = 1; S.prof[PH_NFACT] += 1.0; }
-        }
+        K.flag = ipm_next_delta(K, o, ok, 0.0) ? 1 : 0;
+        if (K.flag) S.prof[PH_NFACT] += 1.0;
       KS_END();
       if (!K.flag) break;
     }
     if (!K.fact_ok) {      // the step cannot be computed: give up (status NUMERICAL), or -- once -- continue in the feasibility phase
-      KS_BEGIN() K.status = K.stalled ? LANDING_STALLED : LANDING_NUMERICAL; K.fact_failed = (o.feas_phase && !K.feas_used && !K.feas) ? 1 : 0; KS_END();
-      if (K.fact_failed) continue;
+      KS_BEGIN() K.status = K.stalled ? LANDING_STALLED : LANDING_NUMERICAL; S.fact_failed = (o.feas_phase && !K.feas_used && !K.feas) ? 1 : 0; KS_END();
+      if (S.fact_failed) continue;
       break;
     }
-    KS_BEGIN()
-      const bool adapt = K.feas && o.feas_delta_dec > 0.0;
-      if (adapt) K.fdc = K.attempt <= 1 ? fmax(o.feas_delta_dec, K.fdc * K.fdc) : fmin(0.7, sqrt(K.fdc));      // (attempt counts the factorisations of this iteration)
-      if (K.delta > 0.0) { K.delta_last = K.delta; K.need_reg_streak++; } else K.need_reg_streak = 0;
-      if (K.need_reg_streak > 8) K.need_reg_streak = adapt ? 2 : 0;      // probe delta = 0 again from time to time (not inside the phase: the elastic problem has no objective)
-    KS_END();
+    KS_BEGIN() ipm_commit_delta(K, o, 0.0); KS_END();
     PROF_ADD(PH_BACK, K.tp);
 
     forward_pass();
@@ -1618,7 +1328,7 @@ __global__ void __launch_bounds__(SOLVER_THREADS, LANDING_MIN_WAVES) landing_ipm
     {
       const double mu = K.mu;
       const bool feas = K.feas != 0;
-      const bool clip_now = !feas && K.clip_k_cur > 1 && (K.c_pr > o.clip_until || (o.jam_clip > 0 && K.jamrun >= o.jam_clip));      // far from feasible, or jammed (landing_nlp.h)
+      const bool clip_now = !feas && K.clip_k_cur > 1 && (K.c_pr > o.clip_until || (o.jam_clip > 0 && S.jamrun >= o.jam_clip));      // far from feasible, or jammed (landing_nlp.h)
       double top[4] = {0.0, 0.0, 0.0, 0.0};
       double m_pr = 0.0, m_du = 0.0, th0 = 0.0, bar = 0.0, dphi = 0.0;
       double f0 = 0.0;
@@ -1693,7 +1403,7 @@ __global__ void __launch_bounds__(SOLVER_THREADS, LANDING_MIN_WAVES) landing_ipm
           a_pr = (rk > tau) ? tau / rk : 1.0;
         }
         K.a_pr = a_pr;
-        K.clip_now = clip_now ? 1 : 0; K.omt = clip_now ? 1.0 - tau : -1.0;
+        S.clip_now = clip_now ? 1 : 0; K.omt = clip_now ? 1.0 - tau : -1.0;
         K.th0 = v[2]; K.dphi = v[4]; K.ph0 = v[5] + mu * v[3];
         if (K.th_max == 0.0) K.th_max = 1e4 * fmax(1.0, v[2]);
         // line search state
@@ -1740,33 +1450,7 @@ __global__ void __launch_bounds__(SOLVER_THREADS, LANDING_MIN_WAVES) landing_ipm
       if (lane < 12 && !feas) { const double d = M.xt[12 * N + lane] - p[12 * N + lane]; ft = p[L.o_QN + lane] * d * d; }
       if (L.run_cost && !feas) ft += rc_f(M.xt);
       { double v[3] = {tht, bt, ft}; const int op[3] = {RSUM, RSUM, RSUM}; block_reduce<3>(v, op, S.red); tht = v[0]; bt = v[1]; ft = v[2]; }
-      KS_BEGIN_SYNCED()
-        const double th_min = 1e-4, th_floor = o.theta_floor * o.tol;     // violations below the tolerance count as equal (landing_nlp.h)
-        const double th0 = K.th0, ph0 = K.ph0, dphi = K.dphi;
-        const int nfilt = K.nfilt;
-        const double pht = ft + mu * bt;
-        bool ok_f = (tht <= K.th_max) && (pht < 1e300) && (pht > -1e300) && (tht < 1e300);
-        for (int e = 0; e < nfilt && ok_f; ++e) if (tht >= fmax(S.filt_th[e], th_floor) && pht >= S.filt_ph[e]) ok_f = false;
-        const bool switching = (dphi < 0.0) && (th0 <= th_min) && (alpha * pow(-dphi, 2.3) > 1.0 * pow(th0, 1.1));
-        bool accepted = false, done = false;
-        if (ok_f) {
-          if (switching) {
-            if (pht <= ph0 + 1e-8 * alpha * dphi) { accepted = true; K.armijo_step = 1; }
-          } else if (tht <= fmax((1.0 - 1e-5) * th0, th_floor) || pht <= ph0 - 1e-8 * th0) {
-            accepted = true;
-          }
-        }
-        if (K.force_step && ok_f) { accepted = true; K.nfilt = 0; done = true; }      // watchdog (landing_nlp.h): the step to the boundary is taken without the sufficient-decrease / switching tests;
-                                                                                      // it must still pass theta <= theta_max and must not be dominated by a filter entry (ok_f), then the filter restarts
-        if (accepted) done = true;
-        K.need_corr = 0;
-        if (!done) {
-          if (o.slack_corr > 0.0 && !K.feas && alpha == K.a_pr && tht >= th0) { K.need_corr = 1; K.ft = ft; }
-          else { K.alpha = alpha * 0.5; if (!(K.alpha > 1e-10)) done = true; }
-        }
-        K.accepted = accepted ? 1 : 0;
-        K.ls_done = done ? 1 : 0;
-      KS_END();
+      KS_BEGIN_SYNCED() ipm_ls_test(K, o, tht, ft, bt, S.filt_th, S.filt_ph); KS_END();
       if (K.need_corr) {
         // slack correction (landing_nlp.h): the rejected first trial point once more with the inequality slacks moved to g(x_trial)
         double tht2 = 0.0, bt2 = 0.0;
@@ -1788,43 +1472,12 @@ __global__ void __launch_bounds__(SOLVER_THREADS, LANDING_MIN_WAVES) landing_ipm
           }
         }
         { double v[2] = {tht2, bt2}; const int op[2] = {RSUM, RSUM}; block_reduce<2>(v, op, S.red); tht2 = v[0]; bt2 = v[1]; }
-        KS_BEGIN_SYNCED()
-          const double th_floor = o.theta_floor * o.tol, th0 = K.th0, ph0 = K.ph0;
-          const int nfilt = K.nfilt;
-          const double pht2 = K.ft + mu * bt2;
-          bool ok2 = (tht2 <= K.th_max) && (pht2 < 1e300) && (pht2 > -1e300);
-          for (int e = 0; e < nfilt && ok2; ++e) if (tht2 >= fmax(S.filt_th[e], th_floor) && pht2 >= S.filt_ph[e]) ok2 = false;
-          if (ok2 && (tht2 <= fmax((1.0 - 1e-5) * th0, th_floor) || pht2 <= ph0 - 1e-8 * th0)) { K.accepted = 1; K.s_corr = o.slack_corr; K.ls_done = 1; }
-          else { K.alpha = alpha * 0.5; if (!(K.alpha > 1e-10)) K.ls_done = 1; }
-        KS_END();
+        KS_BEGIN_SYNCED() ipm_ls_corr_test(K, o, tht2, bt2, S.filt_th, S.filt_ph); KS_END();
       }
     }
     KS_BEGIN()
-      const double a_pr = K.a_pr;
-      K.force_step = 0;
-      if (o.watchdog > 0 && !K.feas) {      // successive iterations with step lengths <= 1/16 of the step to the boundary arm the watchdog
-        if (K.accepted && K.alpha <= 0.0625 * a_pr) { if (++K.cutstreak >= o.watchdog) { K.force_step = 1; K.cutstreak = 0; K.wd_count++; } }
-        else K.cutstreak = 0;
-      }
-      K.fallback = 0;
-      if (!K.accepted) {
-        // no acceptable step: take a short step along the Newton direction and restart the filter
-        K.nfilt = 0;
-        K.alpha = fmin(a_pr, o.alpha_fallback);
-        K.fallback = 1;
-      } else if (!K.armijo_step) {
-        int nfilt = K.nfilt;
-        if (nfilt == FILT_CAP) {     // drop the oldest entry (serial, rare)
-          for (int e = 0; e + 1 < FILT_CAP; ++e) { S.filt_th[e] = S.filt_th[e + 1]; S.filt_ph[e] = S.filt_ph[e + 1]; }
-          nfilt = FILT_CAP - 1;
-        }
-        S.filt_th[nfilt] = (1.0 - 1e-5) * K.th0; S.filt_ph[nfilt] = K.ph0 - 1e-8 * K.th0;
-        K.nfilt = nfilt + 1;
-      }
-      if (o.dual_step_cap > 0.0) K.a_du = fmin(K.a_du, o.dual_step_cap * K.alpha);      // the multipliers do not run ahead of a blocked primal step (landing_nlp.h)
-      if (o.jam_clip > 0) K.jamrun = (!K.clip_now && K.a_pr < 0.02) ? K.jamrun + 1 : 0;
-      if (o.feas_jam > 0) K.fjam = (!K.feas && K.alpha < 1e-2) ? K.fjam + 1 : (K.fjam > 2 ? K.fjam - 2 : 0);
-      K.full_prev = (K.accepted && K.alpha == 1.0 && K.a_du == 1.0 && K.attempt <= 1) ? 1 : 0;
+      ipm_ls_end(K, o, S.filt_th, S.filt_ph, FILT_CAP);
+      if (o.jam_clip > 0) S.jamrun = (!S.clip_now && K.a_pr < 0.02) ? S.jamrun + 1 : 0;
     KS_END();
     if (K.fallback) {
       const double alpha = K.alpha;

@@ -1,7 +1,9 @@
 """dev probe (CPU, no GPU): two builds of the HOST EMULATION of the kernels (tests/emu) on the same members -- are the results
 identical bit for bit?  Used for refactorings of landing_ipm_kernel that must not change the arithmetic (round 3: LDS-resident
 iteration state; round 5: condensation fused into the backward sweep, fused row passes).
-    python tools/dev/emu_ab.py BASE.so NEW.so [--cases n20,n40,rc,ccc,feas,short] [--iters K]
+    python tools/dev/emu_ab.py BASE.so NEW.so [--cases n20,n40,rc,ccc,feas,short,kd] [--iters K]
+Case kd: the kinodynamic refinement solver (landing_kd_*_kernel) on the 6-interval member of tests/test_kd_solver_cpu.py, once to convergence and
+once with an iteration limit that sends it through the feasibility phase.
 BASE is typically built from a git worktree of the previous commit (make -C landing-controller_amd/csrc emu there).
 Each library is driven in its own child process (two copies of the emulation in one process would share the fiber runtime's symbols)."""
 import argparse
@@ -17,11 +19,35 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 
 
+def run_kd(lib_path):
+    """the kinodynamic solver on the short-horizon member of tests/test_kd_solver_cpu.py::test_emulated_kernels_solve_a_short_horizon_member"""
+    capi, rbd = importlib.import_module("landing-controller_amd.capi"), importlib.import_module("landing-controller_amd.rbd")
+    kd, P = importlib.import_module("landing-controller_amd.kinodyn"), importlib.import_module("landing-controller_amd.problem")
+    mass, Ib, Ibi = importlib.import_module("landing-controller_amd.constants").robot_constants()
+    Ns, dtv = 6, np.full(6, 0.05)
+    L = capi.LandingLib(Ns, lib_path=lib_path); R = rbd.Rbd(L)
+    q = np.array([0, 0, 0.0, 0.05, 0.15, -0.05]); qd = np.array([0.1, -0.1, 0.05, 0.2, -0.1, -1.0])
+    q[2] = 0.35 + abs(min((kd.rot_xyz(q[3:6]) @ np.array([sx * 0.19, sy * 0.1, 0.0]))[2] for sx in (1, -1) for sy in (1, -1))) + abs(dtv[0] * qd[5])
+    _, x0s, _, _ = P.make_member(Ns, 0.3, q, qd, P.production_constants("main"), dtv)
+    lb, ub, cost, x0 = kd.member_problem(Ns, q, qd, x0s)
+    out = {}
+    for tag, lim in (("conv", 80), ("feas", 6)):      # converges; stops at the limit of 6 and runs the feasibility phase
+        o = R.kinodyn_default_opts(); o.max_iter = lim; o.feas_phase = 1
+        r = R.kinodyn_solve_host(Ns, lb, ub, cost, x0, dtv, mass, np.asarray(Ib), np.asarray(Ibi), 0.75, o)
+        out.update({tag + "_" + k: np.asarray(v).copy() for k, v in r.items()})
+    out["status"] = np.concatenate([out["conv_status"], out["feas_status"]]); out["iters"] = np.concatenate([out["conv_iters"], out["feas_iters"]])
+    L.close()
+    return out
+
+
 def run_cases(lib_path, cases, iters):
     capi = importlib.import_module("landing-controller_amd.capi")
     problem = importlib.import_module("landing-controller_amd.problem")
     out = {}
     for c in cases:
+        if c == "kd":
+            out[c] = run_kd(lib_path)
+            continue
         if c == "n20":
             L = capi.LandingLib(20, lib_path=lib_path); P, X0, _, _ = problem.make_batch(2, 20, 0.6, seed=1); o = L.default_opts()
         elif c == "n40":
