@@ -153,7 +153,7 @@ typedef struct {
   double delta_inc_first;/* growth factor while no regularised iteration happened yet (IPOPT 100; default 10)            */
   double delta_inc;      /* growth factor afterwards (IPOPT 8; default 4: finer steps over-regularise less, tools/strag.py) */
   double delta_dec;      /* first trial = delta_last * delta_dec (IPOPT 1/3; default 1/2: 5 % fewer stage eliminations at unchanged
-                            iteration counts on three seeded batches, tests/dev/ipm_lab.py round 2)                        */
+                            iteration counts on three seeded batches, round-2 measurement)                                 */
   double tau_min;        /* fraction-to-the-boundary floor (IPOPT 0.99; default 0.9)                                     */
   double alpha_fallback; /* step taken (and filter restarted) when the line search finds no acceptable point (1e-2)      */
   double reset_delta;    /* regularisation above which the iterate counts as jammed too (steps degenerate to damped
@@ -166,7 +166,7 @@ typedef struct {
                             time cuts every step to 1..10 % for 3-4 iterations until its multiplier has grown (round-2 traces,
                             DESIGN.md 4.2); letting the few worst jam together instead of one after the other: mean 63 -> 53
                             iterations, slowest member of eight seeded batches 160..246 -> 100..133, inertia-failure retries
-                            1.28 -> 1.15 sweeps per iteration (tests/dev/ipm_lab.py).  0 / 1 = the classic rule (IPOPT).
+                            1.28 -> 1.15 sweeps per iteration (round-2 measurement).  0 / 1 = the classic rule (IPOPT).
                             landing_kinodyn_solve_batch also takes values above 4 (default there 16, round 5): the step length that
                             leaves at most clip_k - 1 slacks blocked, from a histogram of the ratios over half-octaves (never below
                             the 4-slack rule's); landing_solve_batch treats values above 4 as 4                                    */
@@ -521,7 +521,7 @@ int landing_riccati_gains_batch(landing_ctx* ctx, int B, int n, const double* d_
  * [q; qd] in X(:,0); q_init / qd_init of d_p [B][np] are overwritten in place.  d_x0 must not alias d_x_prev.
  * Warm-start options: landing_solver_opts_warm() -- the reference's `_ws` variant sets bound_push = bound_frac = 5e-3
  * (generate_landingCtrller_IPOPT_warmstart.m:246-247); with a shifted solution 1e-4 for both and mu_init = 1e-4 converge in
- * 8 iterations instead of 27 (tests/dev, round 2), which is what fits a 10 ms tick; max_iter = 14 bounds the tick time
+ * 8 iterations instead of 27 (round-2 measurement), which is what fits a 10 ms tick; max_iter = 14 bounds the tick time
  * (real-time iteration: an unconverged member keeps its iterate and continues at the next tick). */
 int landing_mpc_shift(landing_ctx* ctx, int B, const double* d_x_prev, const double* d_state, double* d_p, double* d_x0, void* stream);
 void landing_solver_opts_warm(landing_solver_opts* o);

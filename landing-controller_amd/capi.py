@@ -101,8 +101,7 @@ def load(path=None):
     lib.landing_solve_batch_host.argtypes = [vp, C.c_int, _dp, _dp, C.POINTER(SolverOpts), _dp, _dp, _dp, _ip, _ip, _dp]
     lib.landing_pack_args21.argtypes = [C.c_int, C.c_int, C.POINTER(Args21), _dp]
     lib.landing_solve_args21.argtypes = [vp, C.c_int, C.POINTER(Args21), C.POINTER(SolverOpts), _dp, _dp, _ip, _ip, _dp]
-    if hasattr(lib, "landing_riccati_gains_batch"):      # (older development builds used by tools/dev/variants.py lack it)
-        lib.landing_riccati_gains_batch.argtypes = [vp, C.c_int, C.c_int, vp, vp, _dp, C.c_double, _dp, _dp, _dp, C.c_double, C.c_int, vp, vp, vp, vp, vp]
+    lib.landing_riccati_gains_batch.argtypes = [vp, C.c_int, C.c_int, vp, vp, _dp, C.c_double, _dp, _dp, _dp, C.c_double, C.c_int, vp, vp, vp, vp, vp]
     if hasattr(lib, "landing_mpc_shift"):
         lib.landing_mpc_shift.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     if hasattr(lib, "landing_solve_args25"):

@@ -54,10 +54,8 @@ struct landing_ctx {
   // function layer: the Jacobian, Hessian and residual kernels of one landing_eval_batch call are independent; for large
   // batches they run on two auxiliary streams forked from / joined to the caller's stream so that their ramps and tails overlap
   hipStream_t host_stream = nullptr;  // stream of the *_host entry points (copies + launch), created on first use
-  hipStream_t aux[3] = {nullptr, nullptr, nullptr};
-  hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
-  int sweep_split = 0;               // dev (LANDING_SWEEP_SPLIT=<n>): bit 0: the Jacobian stream as two launches (X_k columns, U_k columns), bit 1: the Hessian stream too -- measured, no gain
-  bool sweep_concurrent = true;      // Q (576) | F (576) | 1/diag(R) (12) of the last landing_riccati_gains_batch call
+  hipStream_t aux[2] = {nullptr, nullptr};
+  hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
   // every scratch block above is re-used by the next call of its entry point, possibly on another stream: the launches that use it are
   // fenced by this event (recorded behind them, waited for before the next writer / reader touches the block) -- ADVICE r2
   hipEvent_t scratch_done = nullptr;
@@ -249,10 +247,6 @@ landing_ctx* landing_create(int N, int device, const landing_form* form) {
   landing_ctx* c = new landing_ctx();
   c->L = landing::make_layout(N);
   c->device = device;
-#ifdef LANDING_DEV_SWITCHES      // development builds only (tools/dev): environment switches of the measurements recorded in profiles/r0*_ab_experiments.txt
-  { const char* e = getenv("LANDING_SWEEP_SERIAL"); c->sweep_concurrent = !(e && e[0] == '1'); }
-  { const char* e = getenv("LANDING_SWEEP_SPLIT"); if (e && e[0] >= '0' && e[0] <= '3') c->sweep_split = e[0] - '0'; }
-#endif
   {  // positions of the U_k Jacobian entries of stages 0 / N-1 inside the uniform (middle-stage) emission sequence
     struct RecCodes { std::vector<int>* v; void col() {} void end() {} void put(int r, double) { v->push_back(r); } };
     std::vector<int> cx, cu;
@@ -298,7 +292,7 @@ void landing_destroy(landing_ctx* ctx) {
   if (ctx->d_rc_map) (void)hipFree(ctx->d_rc_map);
   if (ctx->d_h4) (void)hipFree(ctx->d_h4);
   if (ctx->d_fb_scratch) (void)hipFree(ctx->d_fb_scratch);
-  for (int i = 0; i < 3; ++i) { if (ctx->aux[i]) (void)hipStreamDestroy(ctx->aux[i]); if (ctx->ev_join[i]) (void)hipEventDestroy(ctx->ev_join[i]); }
+  for (int i = 0; i < 2; ++i) { if (ctx->aux[i]) (void)hipStreamDestroy(ctx->aux[i]); if (ctx->ev_join[i]) (void)hipEventDestroy(ctx->ev_join[i]); }
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->d_kd_pairs) (void)hipFree(ctx->d_kd_pairs);
   if (ctx->d_kd_jpat) (void)hipFree(ctx->d_kd_jpat);
@@ -321,36 +315,30 @@ int landing_eval_batch(landing_ctx* ctx, int B, const double* d_x, const double*
   HIP_TRY(hipSetDevice(ctx->device));
   landing::EvalArgs A{d_x, d_p, d_lam_f, d_lam_g, d_f, d_g, d_grad_f, d_jac, d_hess, d_ggx, d_ggp, ctx->d_edge_map, d_g ? 1 : 0};
   if (ctx->L.N < 3) return fail(LANDING_E_ARG, "landing_eval_batch: N >= 3 required");
-  hipStream_t s0 = (hipStream_t)stream, sj = s0, sh = s0, sh2 = s0;
-  const bool fork = ctx->sweep_concurrent && B >= 512 && d_jac && d_hess;
+  hipStream_t s0 = (hipStream_t)stream, sj = s0, sh = s0;
+  const bool fork = B >= 512 && d_jac && d_hess;
   if (fork) {
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (!ctx->aux[0]) {
-      for (int i = 0; i < 3; ++i) { HIP_TRY(hipStreamCreateWithFlags(&ctx->aux[i], hipStreamNonBlocking)); HIP_TRY(hipEventCreateWithFlags(&ctx->ev_join[i], hipEventDisableTiming)); }
+      for (int i = 0; i < 2; ++i) { HIP_TRY(hipStreamCreateWithFlags(&ctx->aux[i], hipStreamNonBlocking)); HIP_TRY(hipEventCreateWithFlags(&ctx->ev_join[i], hipEventDisableTiming)); }
       HIP_TRY(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
     }
-    sj = ctx->aux[0]; sh = ctx->aux[1]; sh2 = ctx->aux[2];
+    sj = ctx->aux[0]; sh = ctx->aux[1];
     HIP_TRY(hipEventRecord(ctx->ev_fork, s0));
-    HIP_TRY(hipStreamWaitEvent(sj, ctx->ev_fork, 0)); HIP_TRY(hipStreamWaitEvent(sh, ctx->ev_fork, 0)); HIP_TRY(hipStreamWaitEvent(sh2, ctx->ev_fork, 0));
+    HIP_TRY(hipStreamWaitEvent(sj, ctx->ev_fork, 0)); HIP_TRY(hipStreamWaitEvent(sh, ctx->ev_fork, 0));
   }
   const size_t lds = (size_t)landing::landing_sweep_tile_rows(ctx->L.N) * landing::TILE_LD * sizeof(double);
-  if (d_hess && ctx->sweep_split & 2) {
-    hipLaunchKernelGGL((landing::landing_sweep_kernel<1, 2>), dim3(B), dim3(64), lds, sh, ctx->L, B, A);
-    hipLaunchKernelGGL((landing::landing_sweep_kernel<1, 1>), dim3(B), dim3(64), lds, sh, ctx->L, B, A);
-  } else if (d_hess) hipLaunchKernelGGL((landing::landing_sweep_kernel<1, 0>), dim3(B), dim3(64), lds, sh, ctx->L, B, A);
-  if (d_jac && ctx->sweep_split & 1) {      // the Jacobian stream as two launches: U_k columns, X_k columns
-    hipLaunchKernelGGL((landing::landing_sweep_kernel<0, 2>), dim3(B), dim3(64), lds + 456 * sizeof(int), sj, ctx->L, B, A);
-    hipLaunchKernelGGL((landing::landing_sweep_kernel<0, 1>), dim3(B), dim3(64), lds, sh2, ctx->L, B, A);
-  } else if (d_jac) hipLaunchKernelGGL((landing::landing_sweep_kernel<0, 0>), dim3(B), dim3(64), lds + 456 * sizeof(int), sj, ctx->L, B, A);
-  if (d_g) hipLaunchKernelGGL((landing::landing_sweep_kernel<2, 0>), dim3(B), dim3(64), lds, s0, ctx->L, B, A);
+  if (d_hess) hipLaunchKernelGGL(landing::landing_sweep_kernel<1>, dim3(B), dim3(64), lds, sh, ctx->L, B, A);
+  if (d_jac) hipLaunchKernelGGL(landing::landing_sweep_kernel<0>, dim3(B), dim3(64), lds + 456 * sizeof(int), sj, ctx->L, B, A);
+  if (d_g) hipLaunchKernelGGL(landing::landing_sweep_kernel<2>, dim3(B), dim3(64), lds, s0, ctx->L, B, A);
   // the part of the sweep that needs no stage evaluation has its own light instantiation (eval_kernels.hip)
   const bool heavy = (ctx->L.run_cost && (d_f || d_grad_f)) || (d_g && !A.g_staged) || d_ggx || d_ggp;
   if (heavy) hipLaunchKernelGGL(landing::landing_sweep_misc_kernel<false>, dim3(B), dim3(64), 0, s0, ctx->L, B, A);
   else hipLaunchKernelGGL(landing::landing_sweep_misc_kernel<true>, dim3(B), dim3(64), 0, s0, ctx->L, B, A);
   HIP_TRY(hipGetLastError());
   if (fork) {
-    HIP_TRY(hipEventRecord(ctx->ev_join[0], sj)); HIP_TRY(hipEventRecord(ctx->ev_join[1], sh)); HIP_TRY(hipEventRecord(ctx->ev_join[2], sh2));
-    for (int i = 0; i < 3; ++i) HIP_TRY(hipStreamWaitEvent(s0, ctx->ev_join[i], 0));
+    HIP_TRY(hipEventRecord(ctx->ev_join[0], sj)); HIP_TRY(hipEventRecord(ctx->ev_join[1], sh));
+    for (int i = 0; i < 2; ++i) HIP_TRY(hipStreamWaitEvent(s0, ctx->ev_join[i], 0));
   }
   return 0;
 }
@@ -400,7 +388,7 @@ int landing_eval_hess_rc_batch(landing_ctx* ctx, int B, const double* d_x, const
   hipStream_t s0 = (hipStream_t)stream;
   HIP_TRY(scratch_acquire(ctx, s0));
   landing::EvalArgs A{d_x, d_p, d_lam_f, d_lam_g, nullptr, nullptr, nullptr, nullptr, ctx->d_h4, nullptr, nullptr, ctx->d_edge_map, 0};
-  hipLaunchKernelGGL((landing::landing_sweep_kernel<1, 0>), dim3(B), dim3(64), (size_t)landing::landing_sweep_tile_rows(L.N) * landing::TILE_LD * sizeof(double), s0, L, B, A);
+  hipLaunchKernelGGL(landing::landing_sweep_kernel<1>, dim3(B), dim3(64), (size_t)landing::landing_sweep_tile_rows(L.N) * landing::TILE_LD * sizeof(double), s0, L, B, A);
   hipLaunchKernelGGL(landing::landing_sweep_misc_kernel<true>, dim3(B), dim3(64), 0, s0, L, B, A);     // terminal-cost block of the Hessian
   hipLaunchKernelGGL(landing::landing_hess_rc_kernel, dim3((nrc + 255) / 256, B), dim3(256), 0, s0, L, B, nrc, ctx->d_rc_map, ctx->d_h4, d_p, d_lam_f, d_hess_rc);
   HIP_TRY(hipGetLastError());

@@ -73,13 +73,8 @@ __device__ __forceinline__ void load_stage(const Layout& L, const double* x, con
 }
 
 struct RowStore { double* g; __device__ __forceinline__ void put(int r, double v) { g[r] = v; } };
-#ifdef LANDING_DEV_NOSTORE      // development probe (timing only, garbage results): the values are summed and ONE value per segment is stored -- what do the lane-strided stores of the solver's derivative tasks cost?
-struct SeqStoreJ { double* q; double acc = 0.0; __device__ __forceinline__ void col() {} __device__ __forceinline__ void end() { *q = acc; } __device__ __forceinline__ void put(int, double v) { acc += v; } };
-struct SeqStoreH { double* q; double acc = 0.0; __device__ __forceinline__ void end() { *q = acc; } __device__ __forceinline__ void put(double v) { acc += v; } };
-#else
 struct SeqStoreJ { double* q; __device__ __forceinline__ void col() {} __device__ __forceinline__ void end() {} __device__ __forceinline__ void put(int, double v) { *q++ = v; } };
 struct SeqStoreH { double* q; __device__ __forceinline__ void end() {} __device__ __forceinline__ void put(double v) { *q++ = v; } };
-#endif
 struct LamStage { const double* l; __device__ __forceinline__ double operator()(int r) const { return l[r]; } };
 // the multipliers of a stage addressed by the row numbers of a MIDDLE stage (104 rows); `last`: the lane holds the last stage (80 rows: the six
 // no-slip rows of every foot are absent -> 0, the rows behind them move up).  r is a compile-time constant at every call site.
@@ -137,15 +132,7 @@ constexpr int TILE_HEAD = 33;
 #define LANDING_OPAQUE_LANE(x) ((void)0)
 #endif
 // tile rows (per lane) whose LDS reads are issued together in the block write-out: a lane visits rows lane>>3, +8, ... -- 5 visits at N = 40
-#ifndef LANDING_FLUSH_GROUP_J
-#define LANDING_FLUSH_GROUP_J 3
-#endif
-#ifndef LANDING_FLUSH_GROUP_H
-#define LANDING_FLUSH_GROUP_H 5
-#endif
-#ifndef LANDING_FLUSH_GROUP_G
-#define LANDING_FLUSH_GROUP_G 5
-#endif
+constexpr int FLUSH_GROUP_J = 3, FLUSH_GROUP_H = 5, FLUSH_GROUP_G = 5;
 // KIND 0: Jacobian X_k columns, 1: Jacobian U_k columns, 2: Hessian X_k columns, 3: Hessian U_k columns, 4: g rows.
 // start of stage k's segment in the member's array, and the position of emitted value `pos` inside it (-1: a placeholder of an edge stage)
 template <int KIND>
@@ -188,7 +175,7 @@ __device__ __forceinline__ void tile_round(const double* tile, double* gbase, in
   int lane = threadIdx.x & 63;
   LANDING_OPAQUE_LANE(lane);
   const int N = L->N;
-  constexpr int FG = KIND <= 1 ? LANDING_FLUSH_GROUP_J : (KIND <= 3 ? LANDING_FLUSH_GROUP_H : LANDING_FLUSH_GROUP_G);
+  constexpr int FG = KIND <= 1 ? FLUSH_GROUP_J : (KIND <= 3 ? FLUSH_GROUP_H : FLUSH_GROUP_G);
   if (cnt >= 32) {
     const int lag = cnt - 32 + 2 * (lane & 7);
 #pragma unroll 1
@@ -315,21 +302,16 @@ struct TilePair {
 // N = 40, 9 wavefronts per CU -- and the registers allow 2 wavefronts per SIMD for the Jacobian and residual streams (256 VGPRs), 1 for the
 // Hessian stream (AGPR overflow of the default bound; capping it costs 750 B of scratch per lane and doubles its time).  Measured in round 4:
 // compiling the streams for 3 wavefronts per SIMD (smaller tile, <= 168 registers, ~100 B of spills) is slower, and so is launching the X_k and
-// U_k columns of a stream as two kernels (PART 1, 2: half the instruction stream each) -- the streams are bound by the write path, not by issue.
-#ifndef LANDING_SWEEP_WAVES
-#define LANDING_SWEEP_WAVES(FAM, PART) ((FAM) == 1 && (PART) == 0 ? 1 : 2)
-#endif
+// U_k columns of a stream as two kernels (half the instruction stream each) -- the streams are bound by the write path, not by issue.
 __host__ __device__ inline int landing_sweep_tile_rows(int N) { return (N < 64 ? N : 64) + 1; }
-struct NullEmit {      // the part of a stage another launch writes: its arithmetic is dead code here
+struct NullEmit {      // the part of a stage another wave writes (eval_task_hess): its arithmetic is dead code there
   __device__ __forceinline__ void col() {}
   __device__ __forceinline__ void end() {}
   __device__ __forceinline__ void put(int, double) {}
   __device__ __forceinline__ void put(double) {}
 };
-// PART 0: both parts of a stage by one wavefront; 1: the X_k columns only; 2: the U_k columns only (the Jacobian stream is launched as 1 + 2:
-// half the instruction stream and fewer live values per wavefront, twice the wavefronts)
-template <int FAM, int PART = 0>
-__global__ void __launch_bounds__(64, LANDING_SWEEP_WAVES(FAM, PART)) landing_sweep_kernel(Layout L, int B, EvalArgs A) {
+template <int FAM>
+__global__ void __launch_bounds__(64, FAM == 1 ? 1 : 2) landing_sweep_kernel(Layout L, int B, EvalArgs A) {
   const int m = blockIdx.x;
   if (m >= B) return;
   const int N = L.N, ln = threadIdx.x;
@@ -342,7 +324,7 @@ __global__ void __launch_bounds__(64, LANDING_SWEEP_WAVES(FAM, PART)) landing_sw
   static double tile[65 * TILE_LD + 228];      // host emulation (tests/emu): no dynamic LDS
 #endif
   int* emap = reinterpret_cast<int*>(tile + landing_sweep_tile_rows(N) * TILE_LD);      // of the edge stages: read at every U-column write-out -- from LDS, not through a dependent global load
-  if (FAM == 0 && PART != 1) {
+  if (FAM == 0) {
     int e[8];      // all eight loads in flight before the first is waited for
 #pragma unroll
     for (int j = 0; j < 8; ++j) e[j] = ln + 64 * j < 456 ? A.edge_map[ln + 64 * j] : 0;
@@ -358,24 +340,12 @@ __global__ void __launch_bounds__(64, LANDING_SWEEP_WAVES(FAM, PART)) landing_sw
     load_stage(L, x, p, k, z, P);
     if (FAM == 0) {
       double fz_prev[4] = {0, 0, 0, 0};
-      if (PART != 1 && k > 0) { const double* Up = x + L.x_U(k - 1); for (int l = 0; l < 4; ++l) fz_prev[l] = Up[12 + 3 * l + 2]; }
+      if (k > 0) { const double* Up = x + L.x_U(k - 1); for (int l = 0; l < 4; ++l) fz_prev[l] = Up[12 + 3 * l + 2]; }
       double* J = A.jac + (size_t)m * L.nnz_jac;
-      if (PART == 0) {
-        TilePair<0, 1> t{tile, J, tile_ga(J), &L, emap, k0, rows_here};
-        TilePair<0, 1>::X ex{t}; TilePair<0, 1>::U eu{t};
-        srbm::stage_jac(z, P, false, false, fz_prev, ex, eu);
-        t.finish();
-      } else if (PART == 1) {
-        TilePair<0, 0> t{tile, J, tile_ga(J), &L, nullptr, k0, rows_here};
-        TilePair<0, 0>::X ex{t}; NullEmit eu;
-        srbm::stage_jac(z, P, false, false, fz_prev, ex, eu);
-        t.finish();
-      } else {
-        TilePair<1, 1> t{tile, J, tile_ga(J), &L, emap, k0, rows_here};
-        NullEmit ex; TilePair<1, 1>::X eu{t};
-        srbm::stage_jac(z, P, false, false, fz_prev, ex, eu);
-        t.finish();
-      }
+      TilePair<0, 1> t{tile, J, tile_ga(J), &L, emap, k0, rows_here};
+      TilePair<0, 1>::X ex{t}; TilePair<0, 1>::U eu{t};
+      srbm::stage_jac(z, P, false, false, fz_prev, ex, eu);
+      t.finish();
     } else if (FAM == 2) {
       double* G = A.g + (size_t)m * L.ng;
       TilePair<4, 4> t{tile, G, tile_ga(G), &L, nullptr, k0, rows_here};
@@ -399,22 +369,10 @@ __global__ void __launch_bounds__(64, LANDING_SWEEP_WAVES(FAM, PART)) landing_sw
 #pragma unroll
           for (int i = 0; i < 3; ++i) lps[3 * l + i] = on * (lp[16 + 12 * l + 2 + i] + lp[16 + 12 * l + 5 + i]);
       }
-      if (PART == 0) {
-        TilePair<2, 3> t{tile, H, tile_ga(H), &L, nullptr, k0, rows_here};
-        TilePair<2, 3>::X hx{t}; TilePair<2, 3>::U hu{t};
-        srbm::stage_hess(z, P, false, false, lam, lps, hx, hu);
-        t.finish();
-      } else if (PART == 1) {
-        TilePair<2, 2> t{tile, H, tile_ga(H), &L, nullptr, k0, rows_here};
-        TilePair<2, 2>::X hx{t}; NullEmit hu;
-        srbm::stage_hess(z, P, false, false, lam, lps, hx, hu);
-        t.finish();
-      } else {
-        TilePair<3, 3> t{tile, H, tile_ga(H), &L, nullptr, k0, rows_here};
-        NullEmit hx; TilePair<3, 3>::X hu{t};
-        srbm::stage_hess(z, P, false, false, lam, lps, hx, hu);
-        t.finish();
-      }
+      TilePair<2, 3> t{tile, H, tile_ga(H), &L, nullptr, k0, rows_here};
+      TilePair<2, 3>::X hx{t}; TilePair<2, 3>::U hu{t};
+      srbm::stage_hess(z, P, false, false, lam, lps, hx, hu);
+      t.finish();
     }
   }
 }
@@ -594,21 +552,12 @@ __global__ void __launch_bounds__(256) landing_hess_rc_kernel(Layout L, int B, i
 }
 
 // ---- member-level device functions shared with the solver kernel (lane = stage) -------------------
-// inlining policy of the solver's phase functions (development switches; the defaults are what the product build uses)
+// the solver's phase functions are out of line
 // (measured round 3, A/B on one box: with every phase inlined into landing_ipm_kernel the callee-saved-register traffic disappears
 // -- 209 -> 192 GB of HBM traffic per launch -- but the monolithic kernel is allocated and scheduled far worse: condensation 0.104 ->
 // 0.231 ms, forward sweep 0.082 -> 0.146 ms per iteration under load, 96 -> 141 ms per batch.  Out of line it is.)
-#ifndef LANDING_INL_EVAL_G
-#define LANDING_INL_EVAL_G __noinline__
-#endif
-#ifndef LANDING_INL_TASK
-#define LANDING_INL_TASK __noinline__
-#endif
-#ifndef LANDING_INL_EVAL_JH
-#define LANDING_INL_EVAL_JH __noinline__
-#endif
 // residual g(x) of one member (boundary rows + all stages); the caller synchronises afterwards.
-__device__ LANDING_INL_EVAL_G void member_eval_g(const Layout& L, const double* x, const double* p, double* g) {
+__device__ __noinline__ void member_eval_g(const Layout& L, const double* x, const double* p, double* g) {
   const int N = L.N;
   for (int r = threadIdx.x; r < 36; r += blockDim.x) {
     double v;
@@ -634,12 +583,12 @@ __device__ __forceinline__ void load_stage_in(const Layout& L, const double* x, 
   for (int l = 0; l < 4; ++l) I.fz_prev[l] = 0.0;
   if (k > 0) { const double* Up = x + L.x_U(k - 1); for (int l = 0; l < 4; ++l) I.fz_prev[l] = Up[12 + 3 * l + 2]; }
 }
-__device__ LANDING_INL_TASK void eval_task_jac(const Layout& L, const double* x, const double* p, int k, double* J) {
+__device__ __noinline__ void eval_task_jac(const Layout& L, const double* x, const double* p, int k, double* J) {
   StageIn I; load_stage_in(L, x, p, k, I);
   SeqStoreJ ex{J + L.jx(k)}, eu{J + L.ju(k)};
   srbm::stage_jac(I.z, I.P, k == 0, k == L.N - 1, I.fz_prev, ex, eu);
 }
-__device__ LANDING_INL_TASK void eval_task_jty(const Layout& L, const double* x, const double* p, int k, const double* y, double* gx) {
+__device__ __noinline__ void eval_task_jty(const Layout& L, const double* x, const double* p, int k, const double* y, double* gx) {
   StageIn I; load_stage_in(L, x, p, k, I);
   const bool first = (k == 0);
   const double* lprev = first ? y : y + L.g_stage(k - 1);
@@ -651,7 +600,7 @@ __device__ LANDING_INL_TASK void eval_task_jty(const Layout& L, const double* x,
 // Hessian values of stage k: PART 0 = both column groups, 1 = the X_k columns (29 values), 2 = the U_k columns (148 / 160).  The solver
 // runs 1 and 2 on two waves (round 5; the fourth wave used to idle through the derivative phase)
 template <int PART>
-__device__ LANDING_INL_TASK void eval_task_hess(const Layout& L, const double* x, const double* p, int k, const double* y, double* H) {
+__device__ __noinline__ void eval_task_hess(const Layout& L, const double* x, const double* p, int k, const double* y, double* H) {
   StageIn I; load_stage_in(L, x, p, k, I);
   const bool first = (k == 0);
   double lps[12];
@@ -667,7 +616,7 @@ __device__ LANDING_INL_TASK void eval_task_hess(const Layout& L, const double* x
 }
 
 // Jacobian / Hessian nonzeros (CCS order) and gx = grad f + J^T y of one member.
-__device__ LANDING_INL_EVAL_JH void member_eval_jh(const Layout& L, const double* x, const double* p, const double* y,
+__device__ __noinline__ void member_eval_jh(const Layout& L, const double* x, const double* p, const double* y,
                                             double* J, double* H, double* gx, double* tiles = nullptr, const int* edge_map = nullptr, double obj = 1.0) {
   const int N = L.N;      // obj: 1, or 0 in the solver's feasibility phase (no objective)
   for (int i = threadIdx.x; i < 36; i += blockDim.x) J[L.jx(N) + i] = 1.0;
@@ -684,9 +633,6 @@ __device__ LANDING_INL_EVAL_JH void member_eval_jh(const Layout& L, const double
   (void)tiles; (void)edge_map;      // (round 2's tiled write-out of the Jacobian task inside the solver: measured slower, removed)
   for (int task = wave; task < 4; task += nwave)
   for (int k = threadIdx.x & 63; k < N; k += 64) {
-#ifdef LANDING_DEV_SKIP_TASK          // development probe (tools/dev): which task bounds the derivative phase
-    if (task == LANDING_DEV_SKIP_TASK) continue;
-#endif
     if (task == 0) eval_task_jac(L, x, p, k, J);
     else if (task == 1) eval_task_jty(L, x, p, k, y, gx);
     else if (task == 2) eval_task_hess<1>(L, x, p, k, y, H);

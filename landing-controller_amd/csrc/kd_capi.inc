@@ -37,7 +37,7 @@ void landing_kinodyn_solver_opts_default(landing_solver_opts* o) {
   // Round 6: the SRBM solver's restoration-style rules (several entries with an early return, landing_nlp.h feas_max / feas_back) need the jam rule to pay; with entries at the
   // iteration limit only they triple the work of the members that end without a decision (MI355X, law datagen, seeds 102 / 104: 1500 instead of 700 iterations, 2.5 instead of
   // 1.4 s per batch), and with the jam rule on (8 / 12) the six hold-out batches of the hard law take 0.69-1.34 / 0.63-1.45 s against 0.70-1.82 s -- inside the spread, while
-  // a batch of law main loses a member (tools/dev/gpu_r06f.sh).  One entry, no early return, as in round 5; the polishing step, LANDING_STALLED and the adapted regularisation
+  // a batch of law main loses a member (round-6 measurement).  One entry, no early return, as in round 5; the polishing step, LANDING_STALLED and the adapted regularisation
   // decay of the phase apply.
   o->feas_max = 1; o->feas_back = 0.0;
   // Round 5, late (profiles/r05_ab_experiments.txt "kinodynamic portfolio"; 5 bench batches of 1024, law main): the batch time is set by single members
@@ -149,10 +149,6 @@ int landing_kinodyn_solve_batch(landing_ctx* ctx, int B, int N, const landing_ki
   // launch over finished members costs microseconds (every workgroup leaves at once), a host round trip per round cost more
   constexpr int KD_SYNC_EVERY = 4;
   const long long max_rounds = 8LL * (o.max_iter > 0 ? (long long)o.max_iter : 0LL);
-#ifdef LANDING_KD_DEV      // development build only (tools/dev): LANDING_KD_TRACE=<member> prints that member's iteration state after every round
-  const char* tr_ = getenv("LANDING_KD_TRACE");
-  const int trace_m = tr_ ? atoi(tr_) : -1;
-#endif
   for (long long it = 0; it <= max_rounds && active > 0; ++it) {
     for (int w = 0; w < landing::KD_NWAVE && S > 0; ++w)
       if (it == (long long)o.kd_clone_after * (w + 1)) {      // portfolio: the members still iterating are posed again under the variants' option sets
@@ -171,7 +167,7 @@ int landing_kinodyn_solve_batch(landing_ctx* ctx, int B, int N, const landing_ki
     // Riccati sweeps, line search, acceptance.  The head kernel runs over the round's derivative list (members with a new point + pending ones), the other two over the list the head passes on (ADVICE r5: no launch over empty clone slots)
     const int nb = bound < BT ? bound : BT;      // (the lists of the round hold at most as many members as the host saw at its last look + the clones posed since)
     hipLaunchKernelGGL(landing::landing_kd_head_kernel, dim3(nb), dim3(landing::KD_THREADS), 0, st, A);
-    hipLaunchKernelGGL(landing::landing_kd_condense_kernel, dim3(nb * N < KD_COND_GRID ? nb * N : KD_COND_GRID), dim3(landing::KD_THREADS), 0, st, A);
+    hipLaunchKernelGGL(landing::landing_kd_condense_kernel, dim3(nb * N < landing::KD_COND_GRID ? nb * N : landing::KD_COND_GRID), dim3(landing::KD_THREADS), 0, st, A);
     hipLaunchKernelGGL(landing::landing_kd_iter_kernel, dim3(nb), dim3(landing::KD_THREADS), 0, st, A);
     if (look) {
       HIP_TRY(hipMemcpyAsync(&active, A.n_active, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -179,33 +175,8 @@ int landing_kinodyn_solve_batch(landing_ctx* ctx, int B, int N, const landing_ki
       bound = active;
     }
     cur ^= 1;
-#ifdef LANDING_KD_DEV
-    if (trace_m >= 0 && trace_m < BT) {
-      landing::KdState K;
-      const size_t off = stride - ((sizeof(landing::KdState) + 7) / 8 + 8);
-      HIP_TRY(hipStreamSynchronize(st));
-      HIP_TRY(hipMemcpy(&K, ctx->d_kd_ws + (size_t)trace_m * stride + off, sizeof(K), hipMemcpyDeviceToHost));
-      fprintf(stderr, "kd it %3d  pr %9.2e du %9.2e co %9.2e  mu %8.1e  alpha %8.2e a_pr %8.2e a_du %8.2e  delta %8.1e  th0 %9.2e f %10.3e nfilt %d acc %d arm %d sc %g done %d status %d (active %d)\n",
-              K.it, K.e_pr, K.e_du, K.e_co, K.mu, K.alpha, K.a_pr, K.a_du, K.delta, K.th0, K.fval, K.nfilt, K.accepted, K.armijo_step, K.s_corr, K.done, K.status, active);
-    }
-#endif
   }
   if (active > 0) derivs(false);      // members stopped by the iteration limit: their J blocks belong to the previous iterate
-#ifdef LANDING_KD_DEV
-  if (getenv("LANDING_KD_PROF")) {      // phase ticks of the iteration kernel summed over all members
-    HIP_TRY(hipStreamSynchronize(st));
-    double tot[8] = {0, 0, 0, 0, 0, 0, 0, 0}; long long nit = 0, ntr = 0, nf = 0;
-    const size_t off = stride - ((sizeof(landing::KdState) + 7) / 8 + 8);
-    std::vector<landing::KdState> Ks(1);
-    for (int m = 0; m < B; ++m) {
-      HIP_TRY(hipMemcpy(Ks.data(), ctx->d_kd_ws + (size_t)m * stride + off, sizeof(landing::KdState), hipMemcpyDeviceToHost));
-      for (int i = 0; i < 8; ++i) tot[i] += Ks[0].prof[i];
-      nit += Ks[0].it; ntr += Ks[0].ntrial; nf += Ks[0].nfact;
-    }
-    fprintf(stderr, "kd prof: %lld member-iterations, %lld factorisations, %lld trial points; us per member-iteration: grad %.1f mu %.1f backward %.1f (of which P-products %.1f) forward %.1f dual %.1f linesearch %.1f accept %.1f\n",
-            nit, nf, ntr, tot[0] / nit / 100.0, tot[1] / nit / 100.0, tot[2] / nit / 100.0, tot[7] / nit / 100.0, tot[3] / nit / 100.0, tot[4] / nit / 100.0, tot[5] / nit / 100.0, tot[6] / nit / 100.0);
-  }
-#endif
   hipLaunchKernelGGL(landing::landing_kd_finish_kernel, dim3(B), dim3(landing::KD_THREADS), 0, st, A);
   HIP_TRY(hipGetLastError());
   return 0;      // (scratch_guard records the fence)

@@ -35,10 +35,7 @@ constexpr int KD_NSIG = 24, KD_NV = 60;          // state; stage variables v = (
 constexpr int KD_MS = 62;                        // LDS row stride of the stage array [M | m] (column 60 = right-hand side)
 constexpr int KD_PS = 25;                        // LDS row stride of the cost-to-go P (24 x 24)
 constexpr int KD_AS = 37;                        // LDS row stride of [A^ | b] (12 x 37)
-#ifndef KD_JC_ROWS_DEF
-#define KD_JC_ROWS_DEF 44
-#endif
-constexpr int KD_JC_ROWS = KD_JC_ROWS_DEF, KD_JC_S = 65;     // rows per chunk of the staged Jacobian (the 129 inequality rows of an interval = 3 chunks of 44; round 5: 4 of 36), LDS row stride (64 columns + pad)
+constexpr int KD_JC_ROWS = 44, KD_JC_S = 65;     // rows per chunk of the staged Jacobian (the 129 inequality rows of an interval = 3 chunks of 44; round 5: 4 of 36), LDS row stride (64 columns + pad)
 // per-interval record of the backward sweep (doubles): gains K (36 x 24) | kappa (36) | [A^ | b] (12 x 37) | state rows of the cost-to-go
 // P_k (12 x 24) | p_k (12)
 constexpr int KD_REC_K = 0, KD_REC_KAP = 864, KD_REC_AH = 900, KD_REC_PX = 1344, KD_REC_PV = 1632, KD_REC = 1648;
@@ -49,11 +46,7 @@ constexpr int KD_THREADS = 256;
 __device__ __constant__ int KD_ROW2X[12] = {9, 10, 11, 6, 7, 8, 0, 1, 2, 3, 4, 5};
 
 // out-of-line phases of the iteration kernel
-#if defined(__HIP_DEVICE_COMPILE__)
 #define KD_PHASE __device__ __noinline__
-#else
-#define KD_PHASE __device__ __noinline__
-#endif
 struct KdState : IpmCtl {      // (the control fields both solvers keep: ipm_core.hpp)
   double fval;
   double filt_th[KD_FILT], filt_ph[KD_FILT];
@@ -141,13 +134,7 @@ struct KdSolveArgs {
   int* cloned;             // [B0] 1 = the original has clones
   landing_solver_opts ov[3];
 };
-#ifndef KD_NVAR_DEF
-#define KD_NVAR_DEF 3
-#endif
-#ifndef KD_NWAVE_DEF
-#define KD_NWAVE_DEF 4
-#endif
-constexpr int KD_NVAR = KD_NVAR_DEF, KD_NWAVE = KD_NWAVE_DEF;
+constexpr int KD_NVAR = 3, KD_NWAVE = 4;
 constexpr int KD_NOWIN = 0x7f7f7f7f;      // (a byte pattern: the host sets it with one memset)
 __device__ __forceinline__ int kd_problem_of(const KdSolveArgs& A, int m) { return m < A.B0 ? m : A.src[m - A.B0]; }
 __device__ __forceinline__ const landing_solver_opts& kd_opts_of(const KdSolveArgs& A, int m) { return m < A.B0 ? A.o : A.ov[((m - A.B0) / A.F) % KD_NVAR]; }
@@ -236,14 +223,10 @@ KD_PHASE void kd_member_eval_g(const KdNlpParams& P, const RbdModel& M, int N, c
 // Round 6: split in two.  (a) kd_condense_rows_sparse -- the inequality rows' part J_I' Sigma J_I and J_I' rho of EVERY interval of every member that iterates this
 // round, one workgroup per (member, interval) in landing_kd_condense_kernel between the head and the iteration kernel: it does not depend on the Riccati recursion, and
 // inside the backward sweep its three chunks per stage were 15 % of a batch of law main and 18 % of a round of the lock-step tail, where one member's chain is all there
-// is (tools/dev/gpu_r06p.sh: builds that run the loop 1 / 2 / 3 times).  (b) kd_assemble_stage -- inside the sweep: M = (H + delta_w I) + [that part], m, [A^ | b],
+// is (round-6 measurement: builds that run the loop 1 / 2 / 3 times).  (b) kd_assemble_stage -- inside the sweep: M = (H + delta_w I) + [that part], m, [A^ | b],
 // every load of a thread in flight together.
-#ifndef KD_COND_WGS
-#define KD_COND_WGS 3      // (168 registers: at 4 the chunk loop spills -- 35 against 19 ms of kernel time per batch, tools/dev/gpu_r06t.sh)
-#endif
-#ifndef KD_COND_GRID
-#define KD_COND_GRID 2048
-#endif
+constexpr int KD_COND_WGS = 3;      // (168 registers: at 4 the chunk loop spills -- 35 against 19 ms of kernel time per batch, round-6 measurement)
+constexpr int KD_COND_GRID = 2048;
 
 // (a) J_I' Sigma J_I and m = J_I' rho over the structural non-zeros of the block (KdJPat / KdCPat): the entries of the block into LDS (529 gathers), then one lane per
 // destination of the 60 x 60 array (upper triangle, mirrored on the way out) and per right-hand side.  Entries of the array that no row couples are never written: the
@@ -403,9 +386,6 @@ KD_PHASE bool kd_riccati_stage(const KdMem& M, int N, int k) {
   const int tid = threadIdx.x, NT = blockDim.x;
   const bool last = k == N - 1;
   const int nv = last ? 48 : KD_NV, nu = nv - KD_NSIG;
-#ifdef LANDING_KD_DEV
-  const long long t_in_ = (long long)wall_clock64();
-#endif
   // Gauss-Jordan on the control rows / columns 24 .. nv-1 of [M | m] on the fp64 matrix cores (round 5): the 64 x 64 array lives in
   // v_mfma_f64_16x16x4 accumulator tiles (wave w owns column tile w, four row tiles), pivot blocks of 4 x 4 -- kd_pivot_block_step, the
   // scheme of the SRBM solver's block_eliminate (solver_kernels.hip): 9 exchange + barrier rounds per stage instead of 36.  (Round 4: scalar
@@ -457,9 +437,6 @@ KD_PHASE bool kd_riccati_stage(const KdMem& M, int N, int k) {
         for (int kt = 0; kt < 3; ++kt) T[rt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[rt][kt], Y1[kt], T[rt], 0, 0, 0);
       T[3][0] += Y2[0]; T[3][1] += Y2[1]; T[3][2] += Y2[2];      // rows of c+ (48..59): + rows 12..23 of P E
     }
-#ifdef LANDING_KD_DEV      // development timer: the products with the cost-to-go of the next stage (prof[7], part of the backward sweep's slot)
-    if (tid == 0) S.ks.prof[7] += (double)((long long)wall_clock64() - t_in_);
-#endif
     ok &= kd_pivot_block_step<24, 0>(T, ct, lj, lk, c);
     ok &= kd_pivot_block_step<28, 1>(T, ct, lj, lk, c);
     ok &= kd_pivot_block_step<32, 2>(T, ct, lj, lk, c);
@@ -527,9 +504,6 @@ KD_PHASE bool kd_backward(const KdMem& M, int N, const double* cost, double delt
 }
 
 // forward sweep: dx of every variable, multipliers of the defect rows (yn), ds of every inequality row
-#ifndef KD_DS_U
-#define KD_DS_U 16
-#endif
 KD_PHASE void kd_forward(const KdMem& M, int N, const double* lbm, const KdJPat* jpat) {
   KdLds& S = KSH;
   const int tid = threadIdx.x, NT = blockDim.x;
@@ -597,16 +571,13 @@ KD_PHASE void kd_forward(const KdMem& M, int N, const double* lbm, const KdJPat*
   // ds = J_I dx + (g - s).  The steps of all intervals' block variables are gathered first (into the stage array, free here), so that no barrier separates the intervals.
   // Round 6: over the STRUCTURAL non-zeros of the rows (KdJPat: 4.1 entries per row on average, at most 9, of 72): one lane per row, its entries gathered from the dense
   // block with all loads of the row in flight, summed in column order -- no cross-lane reduction.  Rounds 4-5 streamed the dense rows (one wave per row, lanes over the 72
-  // columns, a 6-level shuffle reduction per row): 9.5 % of a batch of law main, 0.18 ms per round of the lock-step tail (tools/dev/gpu_r06w.sh).
+  // columns, a 6-level shuffle reduction per row): 9.5 % of a batch of law main, 0.18 ms per round of the lock-step tail (round-6 measurement).
   static_assert(64 * KD_NW <= KD_NV * KD_MS + KD_NSIG * KD_PS + KD_NSIG + 12 * KD_AS + KD_NSIG * KD_AS, "the gathered steps of N <= 64 intervals fit the arrays in front of Jc");
   double* dxa = S.Ms;      // [N][72]  (runs on into Pm, pv, Ah, Y for long horizons: all free during the forward sweep)
   for (int e = tid; e < N * KD_NW; e += NT) { const int k = e / KD_NW, i = kd_w_index(N, k, e % KD_NW); dxa[e] = i >= 0 ? M.dx[i] : 0.0; }
   { const unsigned long long* src = reinterpret_cast<const unsigned long long*>(jpat); unsigned long long* dst = reinterpret_cast<unsigned long long*>(&S.jp);
     for (int e = tid; e < (int)(sizeof(KdJPat) / 8); e += NT) dst[e] = src[e]; }
   __syncthreads();
-#ifdef KD_DEV_DS_REPS      // timing probe (tools/dev): the pass KD_DEV_DS_REPS times, same results
-  for (int rep_ = 0; rep_ < KD_DEV_DS_REPS; ++rep_)
-#endif
   {
     constexpr int RM = KD_ROWS - 12, RL = KD_ROWS_LAST - 12;      // inequality rows of a middle / of the last interval
     const int nmid = (N - 1) * RM, ntot = nmid + RL;
@@ -757,10 +728,8 @@ __global__ void __launch_bounds__(KD_THREADS) landing_kd_init_kernel(KdSolveArgs
 
 // ---- one interior-point iteration of one member (J and H blocks of the current (x, y) are in the workspace) ---------------------------
 constexpr int KD_DELTA_JUMP = 12;      // (round 5, profiles/r05_ab_experiments.txt: the delta_w continuation of landing_kd_iter_kernel)
-#ifndef KD_TRIES_PER_ROUND
-#define KD_TRIES_PER_ROUND 2      // (round 5: 3 with the matrix-core elimination, 0.7 instead of 1.8 ms per attempt -- 1.23 -> 1.07 s per batch of 1024; round 4: 1.  With the
-                                  // portfolio and the delta_w continuation 2: the tail rounds wait for their slowest member's attempts -- 0.408 -> 0.394 s, 1 attempt 0.411)
-#endif
+constexpr int KD_TRIES_PER_ROUND = 2;      // (round 5: 3 with the matrix-core elimination, 0.7 instead of 1.8 ms per attempt -- 1.23 -> 1.07 s per batch of 1024; round 4: 1.
+                                           // With the portfolio and the delta_w continuation 2: the tail rounds wait for their slowest member's attempts -- 0.408 -> 0.394 s, 1 attempt 0.411)
 // Round 6: three launches per round.  landing_kd_head_kernel -- error test, stop / restart / phase decisions, barrier parameter, delta_w of the first attempt (one
 // workgroup per member); landing_kd_condense_kernel -- J_I' Sigma J_I and J_I' rho of every interval (one workgroup per member and interval: sigma and rho are final
 // once the head has set the barrier parameter); landing_kd_iter_kernel -- Riccati sweeps with inertia correction, forward sweep, line search, acceptance.  The state
@@ -1013,17 +982,6 @@ __global__ void __launch_bounds__(KD_THREADS, 2) landing_kd_iter_kernel(KdSolveA
       if (K.th_max == 0.0) K.th_max = 1e4 * fmax(1.0, v[2]);
       K.alpha = K.a_pr; K.s_corr = 0.0; K.accepted = 0; K.armijo_step = 0; K.ls_done = K.a_pr > 1e-10 ? 0 : 1;
     KD_END();
-#ifdef LANDING_KD_BLOCKERS      // development aid: the rows whose slack sets the primal step length of this iteration
-    if (!feas) {
-      const double apr = K.a_pr;
-      for (int r = tid + 24; r < ng; r += NT) {
-        const double lb = lbm[r], ub = ubm[r]; if (lb == ub) continue;
-        const double s = M.s[r], ds = M.ds[r];
-        const double rl = lb > -INF ? -ds / (s - lb) : 0.0, ru = ub < INF ? ds / (ub - s) : 0.0;
-        if (fmax(rl, ru) * apr >= 0.25) printf("  blk it %d a_pr %.2e row %d k %d j %d %s ratio %.2e dist %.2e ds %.2e g %.3e s %.3e z %.2e\n", K.it, apr, r, r < 48 ? -1 : (r - 48) / 141, r < 48 ? r : (r - 48) % 141, rl > ru ? "L" : "U", fmax(rl, ru), rl > ru ? s - lb : ub - s, ds, M.g[r], s, rl > ru ? M.zL[r] : M.zU[r]);
-      }
-    }
-#endif
   }
   KD_PROF(4);
   // ================================================================ filter line search

@@ -516,10 +516,7 @@ __global__ void __launch_bounds__(64) landing_fb_lin_exact_prep_kernel(FbArgs a,
   }
 }
 template <bool QUAD>      // QUAD: the model has the topology of rnea_tangent_quad (FbArgs::arrow); its own instantiation, so that it does not inherit the generic recursion's scratch
-#ifndef LANDING_FBLIN_WAVES
-#define LANDING_FBLIN_WAVES 1
-#endif
-__global__ void __launch_bounds__(64, QUAD ? LANDING_FBLIN_WAVES : 1) landing_fb_lin_exact_kernel(FbArgs a, const double* qdd_in, const double* hinv_in) {
+__global__ void __launch_bounds__(64, 1) landing_fb_lin_exact_kernel(FbArgs a, const double* qdd_in, const double* hinv_in) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   const int pt = idx / 36, col = idx % 36;
   if (pt >= a.npts) return;
@@ -948,13 +945,10 @@ __global__ void __launch_bounds__(64) landing_kinodyn_nlp_g_kernel(KdNlpArgs a) 
 // Jacobian blocks: jac[b][k][row][col], col over w (72), one thread per (member, interval, column)
 // One block = KD_JAC_STAGES intervals of ONE member x 72 columns (4 intervals = 4.5 wavefronts: 0.435 s per batch; 8 = 9 full wavefronts but 168 VGPRs: 0.443; 2: 0.453); the stage variables of those intervals live in LDS and the seeded
 // dual numbers are formed on access (as in the Hessian kernel below) instead of 72 dual numbers = 144 VGPRs per lane.  Grid = B * ceil(N / KD_JAC_STAGES).
-#ifndef KD_JAC_STAGES_DEF
-#define KD_JAC_STAGES_DEF 4
-#endif
 // Round 6: wavefront-pure columns, as in the Hessian kernel.  A column of leg l (c_l, f_l, jpos_l, c_l of the next interval) only moves that leg's kinematic rows -- the expensive part of
 // kd_stage_rows -- so wave l (0..3) takes the 12 columns of leg l of the block's four intervals (48 lanes, legmask 1 << l), wave 4 the 12 columns of X (every leg: pos and rpy move them all),
 // wave 5 the 12 columns of X_k+1 (no leg: the defect rows only).  4.5 waves x 4 legs of kinematics became 4 x 1 + 1 x 4: 0.95 -> see DESIGN.md 4.8b ms per round of the full batch.
-constexpr int KD_JAC_STAGES = KD_JAC_STAGES_DEF, KD_JAC_THREADS = 6 * 64;
+constexpr int KD_JAC_STAGES = 4, KD_JAC_THREADS = 6 * 64;
 static_assert(KD_JAC_STAGES == 4, "the lane map of landing_kinodyn_nlp_jac_kernel: 4 intervals x 12 columns = 48 lanes of a wavefront");
 __host__ __device__ inline long long kd_jac_blocks(long long B, int N) { return B * ((N + KD_JAC_STAGES - 1) / KD_JAC_STAGES); }
 template <int STDB>
@@ -1037,16 +1031,10 @@ constexpr int KD_NPAIR = 561;
 // ds_read each) instead of 144 VGPRs per lane -- the kernel ran at 256 VGPRs + 256 AGPRs + 1.6 KB of scratch per lane with them.  Grid = B * N * ceil(npair / 64).
 // (The pairs of KD_HESS_G = 2 consecutive intervals are numbered through: 2 x 286 = 572 pairs fill 9 wavefronts but for 4 lanes; interval by interval the fifth
 // wavefront of each had 30 of 64 lanes at work.)
-#ifndef KD_HESS_G_DEF
-#define KD_HESS_G_DEF 2
-#endif
-constexpr int KD_HESS_G = KD_HESS_G_DEF;
+constexpr int KD_HESS_G = 2;
 __host__ __device__ inline long long kd_hess_blocks(long long B, int N, int npair) { return B * ((N + KD_HESS_G - 1) / KD_HESS_G) * ((KD_HESS_G * npair + 63) / 64); }
-#ifndef KD_HESS_WAVES
-#define KD_HESS_WAVES 1
-#endif
 template <int STDB>
-__global__ void __launch_bounds__(64, KD_HESS_WAVES) landing_kinodyn_nlp_hess_kernel(KdNlpArgs a, const unsigned char* __restrict__ pair_i, const unsigned char* __restrict__ pair_j, int npair) {
+__global__ void __launch_bounds__(64, 1) landing_kinodyn_nlp_hess_kernel(KdNlpArgs a, const unsigned char* __restrict__ pair_i, const unsigned char* __restrict__ pair_j, int npair) {
   const int nch = (KD_HESS_G * npair + 63) / 64, N = a.N, ngr = (N + KD_HESS_G - 1) / KD_HESS_G;
   const long long blk = blockIdx.x;
   const int ch = (int)(blk % nch); const int gr = (int)((blk / nch) % ngr); int b = (int)(blk / ((long long)nch * ngr));

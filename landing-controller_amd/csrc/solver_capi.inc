@@ -284,9 +284,6 @@ int build_tables(const Layout& L, std::vector<int>& data, std::vector<int>& stag
         load[l] += (int)q.ops.size();
       }
       c_ml = std::max(c_ml, *std::max_element(load.begin(), load.end()));
-#ifdef LANDING_DEV_SWITCHES
-      if (getenv("LANDING_DEBUG_TABLES")) fprintf(stderr, "assembly table %zu: %d terms, %zu pieces, %d summed from %d slots, longest list %d\n", u, n, pieces.size(), ncomb, nslot, *std::max_element(load.begin(), load.end()));
-#endif
     }
     c_ml = (c_ml + landing::ATAB_TB - 1) / landing::ATAB_TB * landing::ATAB_TB;
     if (c_ml > landing::ATAB_LTMAX) return -10;
@@ -1031,23 +1028,12 @@ int landing_wb_rollout(landing_ctx* ctx, int B, int N, int nalpha, const double*
   landing::WbRollArgs a;
   a.model = ctx->d_rbd; a.B = B; a.N = N; a.nalpha = nalpha; a.dt = dt; a.semi = ctx->wb_semi; a.alphas = d_alphas; a.x = d_x; a.u = d_u; a.xref = d_xref; a.f_foot = d_f_foot;
   a.K = d_K; a.kff = d_kff; a.skip = ctx->wb_skip; ctx->wb_skip = nullptr;
-#ifdef LANDING_DEV_SWITCHES
-  static const bool dense_solve = getenv("LANDING_WB_DENSE_SOLVE") != nullptr;      // dev switch: the dense 18 x 18 Cholesky factorisation
-#else
-  static const bool dense_solve = false;
-#endif
-  a.arrow = (ctx->rbd_arrow && !dense_solve) ? 1 : 0;
+  a.arrow = ctx->rbd_arrow ? 1 : 0;
   for (int i = 0; i < 36; ++i) { a.Q[i] = Q36[i]; a.QN[i] = QN36[i]; }
   for (int i = 0; i < 12; ++i) a.R[i] = R12[i];
   a.xnew = d_xnew; a.unew = d_unew; a.cost = d_cost;
   const long long n = (long long)nalpha * B;
-#ifdef LANDING_DEV_SWITCHES
-  static const bool scratch_version = getenv("LANDING_WB_ROLLOUT_SCRATCH") != nullptr;      // dev switch: the round-2 kernel (per-thread arrays in scratch)
-#else
-  static const bool scratch_version = false;
-#endif
-  if (scratch_version) hipLaunchKernelGGL(landing::landing_wb_rollout_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(landing::landing_wb_rollout_lds_kernel, dim3((unsigned)((n + landing::WB_TPB - 1) / landing::WB_TPB)), dim3(64), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(landing::landing_wb_rollout_lds_kernel, dim3((unsigned)((n + landing::WB_TPB - 1) / landing::WB_TPB)), dim3(64), 0, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -19,22 +19,10 @@
 #include "../../include/landing_nlp.h"
 #include "ipm_core.hpp"
 
-// inlining policy of the solver's phase functions (development switches; the defaults are what the product build uses).
-// Measured round 3, A/B on one box: with every phase inlined into landing_ipm_kernel the callee-saved-register traffic disappears
-// (209 -> 192 GB of HBM traffic per launch) but the monolithic kernel is allocated and scheduled far worse -- condensation 0.104 ->
-// 0.231 ms, forward sweep 0.082 -> 0.146 ms per iteration under load, 96 -> 141 ms per batch.  Out of line it is.
-#ifndef LANDING_INL_COND
-#define LANDING_INL_COND __noinline__
-#endif
-#ifndef LANDING_INL_BACK
-#define LANDING_INL_BACK __noinline__
-#endif
-#ifndef LANDING_INL_FWD
-#define LANDING_INL_FWD __noinline__
-#endif
-#ifndef LANDING_INL_ROWP
-#define LANDING_INL_ROWP __noinline__
-#endif
+// The phase functions of the solver (riccati_backward, forward_pass, row_products, ...) are __noinline__.  Measured round 3, A/B on
+// one box: with every phase inlined into landing_ipm_kernel the callee-saved-register traffic disappears (209 -> 192 GB of HBM traffic
+// per launch) but the monolithic kernel is allocated and scheduled far worse -- condensation 0.104 -> 0.231 ms, forward sweep
+// 0.082 -> 0.146 ms per iteration under load, 96 -> 141 ms per batch.  Out of line it is.
 
 namespace landing {
 
@@ -93,11 +81,7 @@ struct SolverWorkspace {
 
 // optional per-member phase timers (wall_clock64 ticks, 100 MHz) -- enabled when SolveArgs.prof != nullptr
 enum { PH_EVAL = 0, PH_ERR, PH_SIGRHO, PH_BACK, PH_FWD, PH_DUAL, PH_LS, PH_ACCEPT, PH_NFACT, PH_NTRIAL, PH_NITER, PH_NSTAGE_OK, PH_B_ASM, PH_NSTAGE, PH_B_ELIM, PH_B_POST,
-#ifdef LANDING_STAGE_PROF      // development build (tools/dev/stage_prof.py): time of wave 0 between marks inside block_eliminate, slots 16..
-       PH_COUNT = 32 };
-#else
-       PH_COUNT = 16 };
-#endif   // 11 / 13: stage eliminations that succeeded / were attempted (stage-0 foot block included)
+       PH_COUNT = 16 };   // 11 / 13: stage eliminations that succeeded / were attempted (stage-0 foot block included)
 #define PROF_ADD(slot, tstart) do { if (SH.prof_on) { const long long n_ = (long long)wall_clock64(); if (threadIdx.x == 0) { SH.prof[slot] += (double)(n_ - (tstart)); (tstart) = n_; } } } while (0)
 
 struct SolveArgs {
@@ -140,16 +124,7 @@ __device__ __forceinline__ MemberMem carve(const Layout& L, double* w) {
 
 // LDS of one member
 constexpr int FWD_DXL_NMAX = 64;   // horizons up to this keep a copy of dx in LDS for row_products: 36 N + 12 doubles in [P | A1 | A^]
-#ifndef LANDING_FWD_WAVE
-#define LANDING_FWD_WAVE 0         // 1: the state recursion of the forward sweep by one wave (forward_pass; round-6 experiment)
-#endif
-#ifndef LANDING_PIVOT_2X2
-#define LANDING_PIVOT_2X2 1        // the 4 x 4 pivot block through its 2 x 2 partition (pivot_block_step; 0: LDL^T + two triangular solves, rounds 2-4)
-#endif
-#ifndef LANDING_PIVOT_BLOCK
-#define LANDING_PIVOT_BLOCK 4      // pivot-block size of the fp64 stage elimination (8: built, measured, slower -- pivot_block_step)
-#endif
-constexpr int XCH = 112 * LANDING_PIVOT_BLOCK;   // one exchange buffer of the blocked elimination: pivot rows [64][PB] + pivot columns [48][PB]
+constexpr int XCH = 112 * 4;    // one exchange buffer of the blocked elimination (4 x 4 pivot blocks): pivot rows [64][4] + pivot columns [48][4]
 static_assert(2 * XCH >= 24 * YS, "A1 also holds Y (24 x YS)");
 struct Lds {
   double G[48 * GS];
@@ -397,60 +372,52 @@ typedef double* landing_gptr_w;
 // first).  After NU/4 block steps the control rows hold [I | K | kappa] and the state rows hold the Schur complement
 // [0 | P_k | p_k] -- gains and cost-to-go in one pass.  The array lives in v_mfma_f64_16x16x4 accumulator tiles: wave w
 // owns column tile w (16 columns x 48 rows = 3 tiles; with NU = 24 the right-hand side is column 48, the only live column of
-// wave 3's tile).  One block step = one LDS exchange (the owner of the pivot
-// columns publishes them, every wave publishes its slice of the 4 pivot rows), one barrier, the 4 x 4 LDL^T
-// (recomputed by every lane from the broadcast block: no further communication), the normalised pivot rows of the
-// own columns, and ONE rank-4 MFMA per tile:  T -= C R  (C = pivot columns with the pivot rows blanked; the pivot
-// rows are then overwritten by R itself -- forming them as W - (D - I) R would cancel at the scale of W).  The pivots of the 4 x 4 LDL^T are the scalar pivots of the unblocked
-// elimination, so the inertia test (all pivots positive) is unchanged.  Returns false on a non-positive pivot (at the end of the stage).
+// wave 3's tile).  Returns false on a non-positive pivot (at the end of the stage).
 //
-// One step of the blocked Gauss-Jordan elimination with a PS x PS pivot block (PS = 4 or 8) at rows / columns [OFF, OFF + PS) of the
-// tile array T (wave ct owns column tile ct, accumulator layout: T[rt][r] = element (row 16 rt + lk + 4 r, column 16 ct + lj)).
-// Exchange through LDS (buffer STEP & 1 of S.A1): every lane publishes the PS pivot-row entries of its column, W[c][PS]; the PS
-// lane-columns that hold the pivot columns publish them, C[row][PS]; one barrier; then every lane factors the pivot block
-// D = L diag(d) L^T redundantly from the broadcast copy (no further communication), solves D r = w for its own column and the
-// wave applies the rank-PS update T -= C R with PS / 4 matrix-core instructions per tile; the pivot rows become R itself
-// (forming them as W - (D - I) R would cancel at the scale of W).  The scalar pivots d are those of the unblocked elimination
-// (inertia test unchanged).  PS = 4 is the product setting.  8 x 8 blocks (3 exchange + barrier rounds per stage
-// instead of 6) were built and measured in round 3 and are SLOWER: the redundant per-lane factorisation grows with PS^3 -- about 210
-// fp64 operations per lane and block at 4 issue cycles each against 2 x 40 -- which costs more than the three barrier rounds it
-// saves: backward sweep 0.353 instead of 0.293 ms per iteration with the CU to itself (tools/dev/ab.sh, -DLANDING_PIVOT_BLOCK=8).
-template <int NU, int PS, int OFF, int STEP>
+// One block step (pivot_block_step): the 4 x 4 pivot block at rows / columns [OFF, OFF + 4), OFF = 4 STEP, of the tile array T (wave
+// ct owns column tile ct, accumulator layout: T[rt][r] = element (row 16 rt + lk + 4 r, column 16 ct + lj)).  Exchange through LDS
+// (buffer STEP & 1 of S.A1): every lane publishes the 4 pivot-row entries of its column, W[c][4]; the 4 lane-columns that hold the
+// pivot columns publish them, C[row][4]; one barrier; then every lane solves D r = w for its own column with the pivot block D
+// recomputed redundantly from the broadcast copy (no further communication), and the wave applies the rank-4 update T -= C R with ONE
+// matrix-core instruction per tile; the pivot rows become R itself (forming them as W - (D - I) R would cancel at the scale of W).
+// Rounds 2-4 factored D as L diag(d) L^T with two triangular solves; the 2 x 2 partition below has the shorter serial chain.
+// 8 x 8 blocks (3 exchange + barrier rounds per stage instead of 6) were built and measured in round 3 and are
+// SLOWER: the redundant per-lane factorisation grows with the cube of the block size -- about 210 fp64 operations per lane and block at
+// 4 issue cycles each against 2 x 40 -- which costs more than the three barrier rounds it saves: backward sweep 0.353 instead of
+// 0.293 ms per iteration with the CU to itself.
+template <int STEP>
 __device__ __forceinline__ bool pivot_block_step(f64x4 (&T)[3], int ct, int lj, int lk, int c) {
-  static_assert(PS == 4 || PS == 8, "pivot blocks of 4 or 8");
-  static_assert((OFF & 3) == 0 && (OFF >> 4) == ((OFF + PS - 1) >> 4), "a pivot block lies inside one row tile");
+  constexpr int OFF = 4 * STEP;
+  static_assert((OFF >> 4) == ((OFF + 3) >> 4), "a pivot block lies inside one row tile");
   Lds& S = SH;
-  constexpr int RTB = OFF >> 4, R0 = (OFF & 15) >> 2, NQ = PS / 4;
-  constexpr int WSZ = 64 * PS;
-  static_assert(WSZ + 48 * PS <= XCH, "exchange buffer");
+  constexpr int RTB = OFF >> 4, R0 = (OFF & 15) >> 2;
+  constexpr int WSZ = 64 * 4;
+  static_assert(WSZ + 48 * 4 <= XCH, "exchange buffer");
   double* W = S.A1 + (STEP & 1) * XCH;
   double* C = W + WSZ;
+  // (a one-trip loop: written as a plain store, the same store compiles into another instruction schedule of block_eliminate)
 #pragma unroll
-  for (int q = 0; q < NQ; ++q) W[c * PS + 4 * q + lk] = T[RTB][R0 + q];
-  if (ct == RTB && lj >= (OFF & 15) && lj < (OFF & 15) + PS) {
+  for (int q = 0; q < 1; ++q) W[c * 4 + 4 * q + lk] = T[RTB][R0 + q];
+  if (ct == RTB && lj >= (OFF & 15) && lj < (OFF & 15) + 4) {
 #pragma unroll
     for (int rt = 0; rt < 3; ++rt)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) C[(16 * rt + lk + 4 * r) * PS + (lj - (OFF & 15))] = T[rt][r];
+      for (int r = 0; r < 4; ++r) C[(16 * rt + lk + 4 * r) * 4 + (lj - (OFF & 15))] = T[rt][r];
   }
   __syncthreads();
   // pivot block (uniform reads), pivot rows of the own column, pivot-column operands
-  double a[PS][PS];
+  double a[4][4];
 #pragma unroll
-  for (int i = 0; i < PS; ++i)
+  for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int j = 0; j <= i; ++j) a[i][j] = C[(OFF + i) * PS + j];
-  double w[PS];
+    for (int j = 0; j <= i; ++j) a[i][j] = C[(OFF + i) * 4 + j];
+  double w[4];
 #pragma unroll
-  for (int i = 0; i < PS; ++i) w[i] = W[c * PS + i];
-  double am[NQ][3];
+  for (int i = 0; i < 4; ++i) w[i] = W[c * 4 + i];
+  double am[3];
 #pragma unroll
-  for (int q = 0; q < NQ; ++q)
-#pragma unroll
-    for (int rt = 0; rt < 3; ++rt) { const int row = 16 * rt + lj; const double cv = C[row * PS + 4 * q + lk]; am[q][rt] = (row >= OFF && row < OFF + PS) ? 0.0 : cv; }   // pivot rows: no update
+  for (int rt = 0; rt < 3; ++rt) { const int row = 16 * rt + lj; const double cv = C[row * 4 + lk]; am[rt] = (row >= OFF && row < OFF + 4) ? 0.0 : cv; }   // pivot rows: no update
   auto recip = [](double d) { double i = __builtin_amdgcn_rcp(d); i = fma(i, fma(-d, i, 1.0), i); return fma(i, fma(-d, i, 1.0), i); };
-#if LANDING_PIVOT_2X2
-  static_assert(PS == 4, "2 x 2 partitioned pivot block");
   // The 4 x 4 pivot block through its 2 x 2 partition  D = [A B^T; B C]:  A^-1 from its determinant, E = B A^-1, Schur complement S = C - E B^T, S^-1 from its
   // determinant, then  r_2 = S^-1 (w_2 - E w_1),  r_1 = A^-1 w_1 - E^T r_2.  Two reciprocals on the serial chain instead of four and ~24 dependent operations
   // instead of ~64 of the LDL^T + two triangular solves (every lane computes this between the barrier and its matrix-core update: it is latency, not
@@ -466,72 +433,25 @@ __device__ __forceinline__ bool pivot_block_step(f64x4 (&T)[3], int ct, int lj, 
 #pragma unroll
     for (int j = 0; j < 4; ++j) { const unsigned h = (unsigned)__double2hiint(piv[j]) - 0x00100000u; hm = h > hm ? h : hm; } }
   const bool ok = hm < (0x7e37e43cu - 0x00100000u);
-  auto solve = [&](const double (&wv)[PS], double (&R)[NQ]) {
+  // normalised pivot row of the own column: D r = w, lane group lk keeps r[lk]
+  auto solve = [&](const double (&wv)[4]) {
     const double t2 = fma(-e01, wv[1], fma(-e00, wv[0], wv[2])), t3 = fma(-e11, wv[1], fma(-e10, wv[0], wv[3]));
     const double r2 = fma(s11, t2, -s10 * t3) * iS, r3 = fma(s00, t3, -s10 * t2) * iS;
     const double q0 = fma(a11, wv[0], -a10 * wv[1]) * iA, q1 = fma(a00, wv[1], -a10 * wv[0]) * iA;
     const double r0 = fma(-e10, r3, fma(-e00, r2, q0)), r1 = fma(-e11, r3, fma(-e01, r2, q1));
-    R[0] = lk == 0 ? r0 : (lk == 1 ? r1 : (lk == 2 ? r2 : r3));
+    return lk == 0 ? r0 : (lk == 1 ? r1 : (lk == 2 ? r2 : r3));
   };
-#else
-  // D = L diag(d) L^T: t[i][j] = l[i][j] d[j] = a[i][j] - sum_{k<j} l[i][k] t[j][k]
-  double l[PS][PS], t[PS][PS], inv[PS];
-  unsigned hm = 0u;
-#pragma unroll
-  for (int j = 0; j < PS; ++j) {
-#pragma unroll
-    for (int i = j; i < PS; ++i) {
-      double acc = a[i][j];
-#pragma unroll
-      for (int kk = 0; kk < j; ++kk) acc = fma(-l[i][kk], t[j][kk], acc);
-      t[i][j] = acc;
-    }
-    inv[j] = recip(t[j][j]);
-#pragma unroll
-    for (int i = j + 1; i < PS; ++i) l[i][j] = t[i][j] * inv[j];
-    // all pivots in (2^-1022, ~1e300): one unsigned range test on the high words (negative, zero, subnormal, huge, inf and NaN
-    // pivots all fall outside)
-    const unsigned h = (unsigned)__double2hiint(t[j][j]) - 0x00100000u;
-    hm = h > hm ? h : hm;
-  }
-  const bool ok = hm < (0x7e37e43cu - 0x00100000u);
-  // normalised pivot rows of a column: D r = w by the two triangular solves (no explicit inverse: a badly conditioned
-  // pivot block costs no more accuracy than the scalar elimination would); lane group lk keeps r[4 q + lk]
-  auto solve = [&](const double (&wv)[PS], double (&R)[NQ]) {
-    double y[PS], r[PS];
-#pragma unroll
-    for (int i = 0; i < PS; ++i) {
-      double acc = wv[i];
-#pragma unroll
-      for (int kk = 0; kk < i; ++kk) acc = fma(-l[i][kk], y[kk], acc);
-      y[i] = acc;
-    }
-#pragma unroll
-    for (int i = PS - 1; i >= 0; --i) {
-      double acc = y[i] * inv[i];
-#pragma unroll
-      for (int kk = i + 1; kk < PS; ++kk) acc = fma(-l[kk][i], r[kk], acc);
-      r[i] = acc;
-    }
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) R[q] = lk == 0 ? r[4 * q] : (lk == 1 ? r[4 * q + 1] : (lk == 2 ? r[4 * q + 2] : r[4 * q + 3]));
-  };
-#endif
-  double R[NQ];
-  solve(w, R);
+  const double R = solve(w);
   if (16 * ct + 16 > OFF) {                              // tiles whose columns are all eliminated already stay as they are
 #pragma unroll
-    for (int q = 0; q < NQ; ++q)
-#pragma unroll
-      for (int rt = 0; rt < 3; ++rt) T[rt] = __builtin_amdgcn_mfma_f64_16x16x4f64(am[q][rt], -R[q], T[rt], 0, 0, 0);
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) T[RTB][R0 + q] = R[q];  // the pivot rows become the normalised rows, exactly
+    for (int rt = 0; rt < 3; ++rt) T[rt] = __builtin_amdgcn_mfma_f64_16x16x4f64(am[rt], -R, T[rt], 0, 0, 0);
+    T[RTB][R0] = R;                                      // the pivot rows become the normalised rows, exactly
   }
   return ok;                                             // identical in every lane of the workgroup (tested after the update so
 }                                                        // that the operand fetches are not held behind it)
 
 // (`k` = stage, its copy of A^ / b is k & 1; the assembly of stage k - 1 rides along)
-template <int NU, int PB>
+template <int NU>
 __device__ __noinline__ bool block_eliminate(double* __restrict__ rec, double delta, int k) {
   Lds& S = SH;
   constexpr int NR = NU + 24;                         // rows; column NR is gamma
@@ -542,12 +462,6 @@ __device__ __noinline__ bool block_eliminate(double* __restrict__ rec, double de
   const int cb = k & 1;
   const double* Ah = S.Ah + cb * (12 * YS);
   const double* bv = S.bv + cb * 12;
-#ifdef LANDING_STAGE_PROF
-  long long stg_t_ = SH.prof_on ? (long long)wall_clock64() : 0;
-#define STG_T(i) do { if (SH.prof_on && threadIdx.x == 0) { const long long n_ = (long long)wall_clock64(); SH.prof[16 + (i)] += (double)(n_ - stg_t_); stg_t_ = n_; } } while (0)
-#else
-#define STG_T(i) do { } while (0)
-#endif
   f64x4 T[3];
   // Every operand of the prologue is ONE unconditional LDS load: where a lane has no operand (dead column, row outside the array, structural zero)
   // the index points at a slot that holds 0.0 (cx's constant).  Written as `cond ? S.Ah[i] : 0.0` the compiler turned each of the ~40 operand fetches
@@ -629,37 +543,25 @@ __device__ __noinline__ bool block_eliminate(double* __restrict__ rec, double de
   // the tile fetch: G and gamma are free), LDS copy before block step SC, whose barrier publishes it, products and stores behind
   // that step, sums of several threads behind the next one.
   // A non-positive pivot does not end the stage early: the sweep is abandoned by the caller, a few block steps later
-  constexpr int NSTEP = (NU + PB - 1) / PB, SC = NSTEP >= 5 ? 3 : 1;
-  static_assert(NSTEP >= 3 && NSTEP <= 6 && SC + 2 <= NSTEP, "3..6 block steps per stage");
+  static_assert(NU == 12 || NU == 24, "3 or 6 block steps per stage");
+  constexpr int SC = NU == 24 ? 3 : 1;
   AsmRegs nxt;
   const bool more = k > 0;                               // (uniform)
-#ifndef LANDING_DEV_ASM_LEVEL      // development probe (tools/dev/stage_time.py): 0 = no assembly, 1 = loads and LDS copy, 2 = + products, 3 = everything (results are garbage below 3)
-#define LANDING_DEV_ASM_LEVEL 3
-#endif
-#define ASM_HOOK(step) do { if constexpr (SC == (step) && LANDING_DEV_ASM_LEVEL >= 1) { if (more) asm_copy(nxt); } if constexpr (SC + 1 == (step) && LANDING_DEV_ASM_LEVEL >= 2) { if (more) asm_terms(k - 1, cb ^ 1, nxt); } if constexpr (SC + 2 == (step) && LANDING_DEV_ASM_LEVEL >= 3) { if (more) asm_combine(k - 1, cb ^ 1); } } while (0)
-  STG_T(0);      // prologue
-  bool ok = pivot_block_step<NU, (PB > NU ? NU : PB), 0, 0>(T, ct, lj, lk, c);
-  STG_T(1);      // block step 0
-  if (more && LANDING_DEV_ASM_LEVEL >= 1) asm_issue(k - 1, nxt);
-  STG_T(2);      // asm_issue
+#define ASM_HOOK(step) do { if constexpr (SC == (step)) { if (more) asm_copy(nxt); } if constexpr (SC + 1 == (step)) { if (more) asm_terms(k - 1, cb ^ 1, nxt); } if constexpr (SC + 2 == (step)) { if (more) asm_combine(k - 1, cb ^ 1); } } while (0)
+  bool ok = pivot_block_step<0>(T, ct, lj, lk, c);
+  if (more) asm_issue(k - 1, nxt);
   ASM_HOOK(1);
-  if constexpr (NU > PB) ok &= pivot_block_step<NU, (NU - PB >= PB ? PB : NU - PB), PB, 1>(T, ct, lj, lk, c);
+  ok &= pivot_block_step<1>(T, ct, lj, lk, c);
   ASM_HOOK(2);
-  if constexpr (NU > 2 * PB) ok &= pivot_block_step<NU, (NU - 2 * PB >= PB ? PB : NU - 2 * PB), 2 * PB, 2>(T, ct, lj, lk, c);
-  STG_T(3);      // block steps 1, 2
+  ok &= pivot_block_step<2>(T, ct, lj, lk, c);
   ASM_HOOK(3);
-  STG_T(4);      // asm_copy (NU = 24)
-  if constexpr (NU > 3 * PB) ok &= pivot_block_step<NU, (NU - 3 * PB >= PB ? PB : NU - 3 * PB), 3 * PB, 3>(T, ct, lj, lk, c);
-  STG_T(5);      // block step 3
-  ASM_HOOK(4);
-  STG_T(6);      // asm_terms
-  if constexpr (NU > 4 * PB) ok &= pivot_block_step<NU, (NU - 4 * PB >= PB ? PB : NU - 4 * PB), 4 * PB, 4>(T, ct, lj, lk, c);
-  STG_T(7);      // block step 4
-  ASM_HOOK(5);
-  STG_T(8);      // asm_combine
-  if constexpr (NU > 5 * PB) ok &= pivot_block_step<NU, (NU - 5 * PB >= PB ? PB : NU - 5 * PB), 5 * PB, 5>(T, ct, lj, lk, c);
-  STG_T(9);      // block step 5
-  ASM_HOOK(6);
+  if constexpr (NU == 24) {
+    ok &= pivot_block_step<3>(T, ct, lj, lk, c);
+    ASM_HOOK(4);
+    ok &= pivot_block_step<4>(T, ct, lj, lk, c);
+    ASM_HOOK(5);
+    ok &= pivot_block_step<5>(T, ct, lj, lk, c);
+  }
 #undef ASM_HOOK
   if (!ok) return false;                                 // (identical in every lane)
   {   // closed-loop state map for the forward sweep: X+ = A^_sigma sigma + A^_f f + b with f = -(K_f sigma + kappa_f), i.e.
@@ -698,7 +600,6 @@ __device__ __noinline__ bool block_eliminate(double* __restrict__ rec, double de
         }
       }
   }
-  STG_T(10);     // epilogue
   return true;
 }
 
@@ -706,14 +607,14 @@ __device__ __noinline__ bool block_eliminate(double* __restrict__ rec, double de
 // controls of stage k (G + T^T P T; P_k, p_k -> LDS, gains -> record k) with the assembly of stage k - 1 riding along.
 template <int NU>
 __device__ __forceinline__ bool riccati_step(double* rec, double delta, int k) {
-  const bool ok = block_eliminate<NU, LANDING_PIVOT_BLOCK>(rec, delta, k);
+  const bool ok = block_eliminate<NU>(rec, delta, k);
   __syncthreads();
   return ok;
 }
 
 // One backward Riccati sweep with regularisation delta (terminal cost-to-go, stages N-1..0, free feet of
 // stage 0).  false = a pivot was not positive (wrong inertia): the caller raises delta and retries.
-__device__ LANDING_INL_BACK bool riccati_backward(double delta) {
+__device__ __noinline__ bool riccati_backward(double delta) {
   Lds& S = SH;
   const Layout& L = S.L;
   const MemberMem& M = S.M;
@@ -793,7 +694,7 @@ __device__ LANDING_INL_BACK bool riccati_backward(double delta) {
 // and passed on through a double-buffered LDS slot).  The forces f_k = -(K_f sigma_k + kappa_f) and the multipliers
 // of the dynamics rows y_k = -(P_{k+1} sigma_{k+1} + p_{k+1})_X do not feed the recursion: they are evaluated for
 // all stages at once afterwards.
-__device__ LANDING_INL_FWD void forward_pass() {
+__device__ __noinline__ void forward_pass() {
   Lds& S = SH;
   const Layout& L = S.L;
   const MemberMem& M = S.M;
@@ -814,67 +715,6 @@ __device__ LANDING_INL_FWD void forward_pass() {
     for (int j = 0; j < 3; ++j) { const int e = tid + j * 256; if (k < N && e < RIC_FWDN) b[e] = r[j]; }
   };
   if (tid < 24) sg[tid] = S.sig[tid];
-#if LANDING_FWD_WAVE
-  // Round 6 experiment (profiles/r06_ab_experiments.txt): the recursion is a 24 x 24 product per stage -- ONE wave runs it (two lanes per row, the same association of the sums as the
-  // eight-lanes-per-row form below, so the same bits), with a wave-local ordering between the stages instead of a workgroup barrier; the other three waves stage the records of the next
-  // two stages into LDS meanwhile (loads issued two groups ahead).  One workgroup barrier per TWO stages.
-  {
-    constexpr int FW = RIC_FWDN;
-    static_assert(FW <= NZ_TOT + RUNC && FW <= 2 * 12 * YS && 2 * FW <= 24 * PS + 2 * XCH, "four stage slots: cx | A^ | [P | A1] (two)");
-    double* const slotp[4] = {S.jhl, S.Ah, S.P, S.P + FW};      // (P and A1 are adjacent members of Lds)
-    static_assert(offsetof(Lds, A1) == offsetof(Lds, P) + sizeof(double) * 24 * PS, "P and A1 adjacent");
-    const int wave = tid >> 6, l = tid & 63, lt = tid - 64;
-    auto gfetch = [&](int grp, double (&r)[7]) {      // stages 2 grp, 2 grp + 1: 2 x 612 doubles over the 192 loader threads
-#pragma unroll
-      for (int i = 0; i < 7; ++i) {
-        int e = lt + 192 * i; e = e < 2 * FW ? e : 2 * FW - 1;
-        const int st = e >= FW ? 1 : 0; int k = 2 * grp + st; k = k < N ? k : N - 1;
-        r[i] = ((landing_gptr)(M.ric + (size_t)k * RIC_STRIDE + RIC_FWD0))[e - st * FW];
-      }
-    };
-    auto gstash = [&](int grp, const double (&r)[7]) {
-      double* const b0 = slotp[2 * (grp & 1)]; double* const b1 = slotp[2 * (grp & 1) + 1];
-#pragma unroll
-      for (int i = 0; i < 7; ++i) {
-        const int e = lt + 192 * i, st = e >= FW ? 1 : 0;
-        if (e < 2 * FW && 2 * grp + st < N) (st ? b1 : b0)[e - st * FW] = r[i];
-      }
-    };
-    auto group = [&](int grp) {      // the compute wave: stages 2 grp, 2 grp + 1 from the slots of pair grp & 1
-      const int r = l & 31, h = l >> 5; const bool valid = r < 24; const int rr = valid ? r : 0;
-#pragma unroll
-      for (int st = 0; st < 2; ++st) {
-        const int k = 2 * grp + st;
-        if (k < N) {      // (uniform)
-          const double* b = slotp[2 * (grp & 1) + st];
-          const bool lastk = (k == N - 1);
-          const double* row = (rr < 12) ? b + 312 + rr * 24 : b + (rr - 12) * 24;
-          const double* sk = sg + 24 * k;
-          double a[4];
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) { const int j = 4 * h + jj; a[jj] = row[3 * j] * sk[3 * j] + row[3 * j + 1] * sk[3 * j + 1] + row[3 * j + 2] * sk[3 * j + 2]; }
-          double acc = (a[0] + a[1]) + (a[2] + a[3]);
-          acc += __shfl_xor(acc, 32);
-          if (valid && h == 0) sg[24 * (k + 1) + r] = (r < 12) ? b[600 + r] + acc : (lastk ? 0.0 : -(b[300 + (r - 12)] + acc));
-        }
-#if defined(__HIP_DEVICE_COMPILE__)
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // sigma_{k+1} is read by the other lanes of this wave in the next stage (LDS is in order within a wave)
-#endif
-        __builtin_amdgcn_wave_barrier();
-      }
-    };
-    double rA[7], rB[7];
-    if (wave > 0) { gfetch(0, rA); gfetch(1, rB); gstash(0, rA); gfetch(2, rA); }
-    __syncthreads();
-    const int NG = (N + 1) / 2;
-    for (int g0 = 0; g0 < NG; g0 += 2) {
-      if (wave == 0) group(g0); else { gstash(g0 + 1, rB); gfetch(g0 + 3, rB); }
-      __syncthreads();
-      if (wave == 0) group(g0 + 1); else { gstash(g0 + 2, rA); gfetch(g0 + 4, rA); }
-      __syncthreads();
-    }
-  }
-#else
   double r0[3], r1[3], r2[3], r3[3];
   fetch(0, r0); fetch(1, r1); fetch(2, r2); fetch(3, r3);
   stash(0, r0); fetch(4, r0);
@@ -900,7 +740,6 @@ __device__ LANDING_INL_FWD void forward_pass() {
   for (int k0 = 0; k0 < N; k0 += 4) {
     stage(k0, r1); stage(k0 + 1, r2); stage(k0 + 2, r3); stage(k0 + 3, r0);
   }
-#endif
   // ---- everything that hangs off the states, all stages at once.  Round 6: dx also goes to LDS in the x layout ([P | A1 | A^] are free from here to the next backward sweep) for
   // row_products, whose gathers of dx were one of its two remaining global gathers per term (horizons up to FWD_DXL_NMAX; longer ones gather from the workspace as before)
   double* const dxl = S.P;
@@ -944,7 +783,7 @@ __device__ LANDING_INL_FWD void forward_pass() {
 // with the records of the next batch fetched under the gathers of this one.  (Tried in round 2: the stage-local LDS
 // table scheme of condense() -- one term per thread and stage, carries through LDS, a barrier per 4 stages -- is slower
 // here, alone 0.065 vs 0.039 ms and under load 0.105 vs 0.091: the list is short, 15 k terms, and latency-bound.)
-__device__ LANDING_INL_ROWP void row_products(const unsigned long long* __restrict__ rterm, int rlen) {
+__device__ __noinline__ void row_products(const unsigned long long* __restrict__ rterm, int rlen) {
   Lds& S = SH;
   const MemberMem& M = S.M;
   const int tid = threadIdx.x, NT = blockDim.x;
@@ -1036,9 +875,7 @@ __device__ __noinline__ double rc_f(const double* x) {                 // runnin
 // (256 VGPRs) beats 3 (168) at batch 1024 -- 5220 vs 4760 NLPs/s -- and ties beyond (2048: 5410 vs 5330, 8192: 7080 vs
 // 7050); 4 per CU (128 VGPRs, and the 46 KB of LDS would only fit three) is far behind.  Every phase is latency-bound:
 // more resident workgroups mostly add contention, and the row passes / derivative phases spill less with 256 registers.
-#ifndef LANDING_MIN_WAVES
-#define LANDING_MIN_WAVES 2
-#endif
+constexpr int SOLVER_MIN_WAVES = 2;
 // Receding-horizon shift (SURVEY 8f row N3 / BASELINE configs[4]): the initial guess of the next control tick is the previous
 // solution advanced by one stage -- X(:,k) <- X(:,k+1), U(:,k) <- U(:,k+1), the last column held -- with the measured state
 // in X(:,0); the parameter vector gets the new q_init / qd_init.  (The reference's warm-start variant re-solves from the stored
@@ -1063,7 +900,7 @@ __global__ void landing_mpc_shift_kernel(Layout L, int B, const double* __restri
 // is much later when that member only starts in the second wave.  Members likely to need many iterations go first.
 // Difficulty proxy = initial body height z0 = q_init(3) (it grows with |pitch| and the drop speed through the callers'
 // touch-down rule, generate_training_data_automated.m:52-60): correlation 0.65 with the iteration count on the bench
-// batches (tests/dev/ipm_lab.py), as good as what a 30-iteration probe predicts.  rank = number of members with a larger
+// batches (round-2 measurement), as good as what a 30-iteration probe predicts.  rank = number of members with a larger
 // key (ties: lower index first) -- O(B^2) comparisons, deterministic, no atomics.  NaN keys sort last.
 __global__ void landing_order_kernel(Layout L, int B, const double* __restrict__ p, int* __restrict__ order) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1080,7 +917,7 @@ __global__ void landing_order_kernel(Layout L, int B, const double* __restrict__
   order[rank] = m;
 }
 
-__global__ void __launch_bounds__(SOLVER_THREADS, LANDING_MIN_WAVES) landing_ipm_kernel(SolveArgs A) {
+__global__ void __launch_bounds__(SOLVER_THREADS, SOLVER_MIN_WAVES) landing_ipm_kernel(SolveArgs A) {
   if ((int)blockIdx.x >= A.B) return;
   const int m = A.order ? A.order[blockIdx.x] : (int)blockIdx.x;
   const Layout& L = A.L;
@@ -1148,10 +985,7 @@ __global__ void __launch_bounds__(SOLVER_THREADS, LANDING_MIN_WAVES) landing_ipm
   // Row passes: every thread owns the rows lane + NT j.  They are processed RB at a time with ALL loads of a batch issued
   // up-front and unconditionally (every array is fully allocated; out-of-range rows re-read the last row and are masked):
   // one memory round trip per batch instead of two or three dependent ones per row behind the bound-type branches.
-#ifndef LANDING_RB
-#define LANDING_RB 4
-#endif
-  constexpr int RB = LANDING_RB;
+  constexpr int RB = 4;
   // primal / complementarity errors, Sigma and rho of the CURRENT point for barrier parameter mu_ (one pass over the
   // rows; the accept pass below produces the same quantities for the next iterate, so this runs only at the start,
   // after a multiplier reset and when mu changes).  Leaves c_pr, c_co, c_cm, |y|_1, |z|_1 and the number of bound multipliers in K.
@@ -1228,9 +1062,6 @@ __global__ void __launch_bounds__(SOLVER_THREADS, LANDING_MIN_WAVES) landing_ipm
       du = block_reduce1(du, RMAX, S.red);
       KS_BEGIN_SYNCED()      // ---- what happens with this iterate: stop, restart, into / out of the feasibility phase, or another iteration
         ipm_errors(K, o, du);
-#if !defined(__HIP_DEVICE_COMPILE__) && defined(LANDING_EMU_TRACE)
-        if (getenv("LO_TRACE")) fprintf(stderr, "it %4d pr %9.2e du %9.2e co %9.2e mu %8.1e dlast %8.1e nreset %d nfilt %d feas %d fdc %.3f\n", K.it, K.e_pr, K.e_du, K.e_co, K.mu, K.delta_last, K.nreset, K.nfilt, K.feas, K.fdc);
-#endif
         S.action = ipm_decide(K, o, S.fact_failed != 0);      // (a failed factorisation hands over through fact_failed: the solve ends NUMERICAL or enters the phase)
         S.fact_failed = 0;
       KS_END();
@@ -1315,9 +1146,7 @@ __global__ void __launch_bounds__(SOLVER_THREADS, LANDING_MIN_WAVES) landing_ipm
     PROF_ADD(PH_BACK, K.tp);
 
     forward_pass();
-#ifndef LANDING_DEV_SKIP_ROWP      // development probe (timing only: the results are garbage without it)
     row_products(A.rterm, A.rlen);
-#endif
 
     PROF_ADD(PH_FWD, K.tp);
     // ================================================================ dual steps, step bounds, merit data

@@ -8,7 +8,7 @@
 //   qd+ = qd + dt qdd(q, qd, [0; u], f);  cost  sum_k 1/2 |x_k - xref_k|^2_Q + 1/2 |u_k|^2_R  +  1/2 |x_N - xref_N|^2_QN.
 // One SQP iteration = (1) exact linearisation of the dynamics at every knot (rbd_kernels.hip, one thread per (knot, tangent)),
 // (2) landing_wb_backward_kernel: the LQ subproblem by a Riccati recursion, one wavefront per member, the 36 x 36 value function and
-// the stage matrices in LDS, (3) landing_wb_rollout_kernel: the nonlinear dynamics rolled out under the feedback policy for a set
+// the stage matrices in LDS, (3) landing_wb_rollout_lds_kernel: the nonlinear dynamics rolled out under the feedback policy for a set
 // of step lengths, one thread per (step length, member); the host backtracks over them (landing-controller_amd/wb.py).
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -172,48 +172,12 @@ struct WbRollArgs {
   const double* skip;                                            // [B] or null: members with skip[b] != 0 (a step length already taken, landing_wb_select) are not rolled out: cost = inf
 };
 
-// nonlinear rollout under u = u_k + alpha kff_k + K_k (x - x_k), one thread per (step length, member)
-__global__ void __launch_bounds__(64) landing_wb_rollout_kernel(WbRollArgs a) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= a.nalpha * a.B) return;
-  const int ia = idx / a.B, b = idx % a.B, N = a.N;
-  if (a.skip && a.skip[b] != 0.0) { a.cost[(size_t)ia * a.B + b] = INFINITY; return; }
-  const RbdModel& M = *a.model;
-  const double alpha = a.alphas[ia];
-  const double* xb = a.x + (size_t)b * (N + 1) * WB_NX; const double* ub = a.u + (size_t)b * N * WB_NU;
-  const double* rb = a.xref + (size_t)b * (N + 1) * WB_NX;
-  double* xo = a.xnew + ((size_t)ia * a.B + b) * (N + 1) * WB_NX; double* uo = a.unew + ((size_t)ia * a.B + b) * N * WB_NU;
-  double xs[WB_NX], un[WB_NU], H[RB_NB * RB_NB], C[RB_NB], rhs[RB_NB];
-  for (int i = 0; i < WB_NX; ++i) { xs[i] = xb[i]; xo[i] = xs[i]; }
-  double cost = 0.0; bool ok = true;
-  for (int k = 0; k < N; ++k) {
-    for (int c = 0; c < WB_NU; ++c) {
-      double s = ub[k * WB_NU + c];
-      if (a.K) {
-        s += alpha * a.kff[((size_t)b * N + k) * WB_NU + c];
-        const double* Kr = a.K + (((size_t)b * N + k) * WB_NU + c) * WB_NX;
-        for (int j = 0; j < WB_NX; ++j) s += Kr[j] * (xs[j] - xb[k * WB_NX + j]);
-      }
-      un[c] = s; uo[k * WB_NU + c] = s;
-      cost += 0.5 * a.R[c] * s * s;
-    }
-    for (int i = 0; i < WB_NX; ++i) { const double d = xs[i] - rb[k * WB_NX + i]; cost += 0.5 * a.Q[i] * d * d; }
-    hand_c(M, xs, xs + 18, a.f_foot ? a.f_foot + ((size_t)b * N + k) * 12 : nullptr, H, C);
-    for (int i = 0; i < RB_NB; ++i) rhs[i] = (i >= 6 ? un[i - 6] : 0.0) - C[i];
-    ok = chol_solve18(H, rhs) && ok;
-    for (int i = 0; i < 18; ++i) { const double qd = xs[18 + i], qn = qd + a.dt * rhs[i]; xs[i] += a.dt * (a.semi ? qn : qd); xs[18 + i] = qn; }
-    for (int i = 0; i < WB_NX; ++i) xo[(k + 1) * WB_NX + i] = xs[i];
-  }
-  for (int i = 0; i < WB_NX; ++i) { const double d = xs[i] - rb[N * WB_NX + i]; cost += 0.5 * a.QN[i] * d * d; }
-  a.cost[(size_t)ia * a.B + b] = (ok && cost == cost) ? cost : INFINITY;
-}
-
-// ---- the same rollout with every per-thread array in LDS -------------------------------------------------------------------------
-// The kernel above keeps E[18][9], r[18][3], v, a, f (18 spatial vectors each), the composite inertias, H (18 x 18) and the state in private
+// ---- nonlinear rollout under u = u_k + alpha kff_k + K_k (x - x_k), one thread per (step length, member), every per-thread array in LDS ----
+// Round 2's rollout kept E[18][9], r[18][3], v, a, f (18 spatial vectors each), the composite inertias, H (18 x 18) and the state in private
 // memory (8.5 KB per thread): the 18-body recursion indexes them through the model's parent array, so they live in scratch and one forward-dynamics
 // evaluation costs ~325 us of dependent scratch round trips (13 ms per rollout of 40 knots).  Here the arrays of WB_TPB
 // threads sit in LDS, element-major ([element][thread]: the WB_TPB lanes of a wave touch consecutive banks), one workgroup = one wave with WB_TPB
-// active lanes.  Same arithmetic in the same order as hand_c / chol_solve18 / landing_wb_rollout_kernel: results are identical bit for bit.
+// active lanes.  Same arithmetic in the same order as hand_c / chol_solve18 (rbd_kernels.hip): results are identical bit for bit.
 constexpr int WB_TPB = 16;
 constexpr int WS_E = 0, WS_R = 162, WS_V = 216, WS_F = 324, WS_U = 432, WS_H = 612, WS_C = 936, WS_RHS = 954, WS_X = 972, WS_UN = 1008, WS_PER = 1020;
 static_assert(WB_TPB * WS_PER * 8 + 4096 <= 160 * 1024, "LDS of one workgroup");
@@ -229,7 +193,7 @@ __device__ __forceinline__ void ws_ld_xf(const WsView& W, int i, double* E, doub
 #pragma unroll
   for (int j = 0; j < 3; ++j) r[j] = W(WS_R + 3 * i + j);
 }
-// H -> W(WS_H + 18 i + j), C -> W(WS_C + i); q = W(WS_X + i), qd = W(WS_X + 18 + i)   (hand_c above, line for line)
+// H -> W(WS_H + 18 i + j), C -> W(WS_C + i); q = W(WS_X + i), qd = W(WS_X + 18 + i)   (hand_c of rbd_kernels.hip, line for line)
 __device__ void hand_c_lds(const RbdModel& M, const double* f_foot, const WsView& W) {
   double Ei[9], ri[3];
   for (int i = 0; i < RB_NB; ++i) {

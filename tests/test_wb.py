@@ -1,5 +1,5 @@
 """SURVEY 8(f) row N2 / BASELINE configs[3]: the SQP (Gauss-Newton / iLQR) loop on the 18-DoF floating-base dynamics -- exact
-linearisation, LQ backward pass (landing_wb_backward_kernel) and nonlinear rollouts (landing_wb_rollout_kernel) -- against the numpy
+linearisation, LQ backward pass (landing_wb_backward_kernel) and nonlinear rollouts (landing_wb_rollout_lds_kernel) -- against the numpy
 oracle of oracle/wb_oracle.py (6 x 6 Pluecker dynamics, Richardson-extrapolated derivatives, dense textbook LQ pass).
 CPU: the kernels through tests/emu on a short horizon, iterate for iterate.  GPU: N = 40 steps of 1 ms, a batch of members: monotone cost,
 agreement of one member with the oracle after one iteration.  Tolerances (fp64): 1e-6 relative on trajectories and costs (the two
