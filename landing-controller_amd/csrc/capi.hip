@@ -39,18 +39,56 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
     if (e_ != hipSuccess) return fail(LANDING_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
   } while (0)
 
+// Owning device block of n elements of T: freed by its destructor, moved but never copied.  There are no fences inside: a caller that
+// replaces a block a queued launch may still read waits for that launch first, at the call site.
+namespace {
+template <typename T> class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept { *this = std::move(o); }
+  DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); std::swap(p_, o.p_); std::swap(n_, o.n_); } return *this; }
+  ~DevBuf() { reset(); }
+  hipError_t alloc(size_t n) { reset(); const hipError_t e = hipMalloc((void**)&p_, n * sizeof(T)); if (e == hipSuccess) n_ = n; else p_ = nullptr; return e; }
+  hipError_t grow(size_t n) { return n_ < n ? alloc(n) : hipSuccess; }      // the old block is freed before the new one is allocated
+  void reset() { if (p_) (void)hipFree(p_); p_ = nullptr; n_ = 0; }
+  T* get() const { return p_; }
+  size_t size() const { return n_; }
+  explicit operator bool() const { return p_ != nullptr; }
+ private:
+  T* p_ = nullptr; size_t n_ = 0;
+};
+struct KdCasadi;      // kd_casadi_capi.inc
+struct KdCasadiFree { void operator()(KdCasadi* k) const; };
+}  // namespace
+
+namespace landing {
+// Device state of landing_solve_batch (ensure / release: solver_capi.inc): the assembly tables, built once per context, and the workspace of
+// member_stride(L) doubles per member and the dispatch order, grown to the largest batch seen.
+struct SolverWorkspace {
+  DevBuf<double> buf;
+  DevBuf<int> d_order;
+  hipEvent_t done = nullptr;     // recorded behind every solve launch: the next launch (any stream) and any re-allocation wait for it
+  DevBuf<int> d_tab, d_stage_tab, d_rterm, d_ctype;      // d_tab is moved in last: d_tab set <=> all tables are resident
+  DevBuf<unsigned long long> d_ctab, d_ccomb;      // packed per-stage-type assembly tables (aterm_pack): [type][c_ml][256]; destinations summed from partial slots
+  int n_tab = 0, rlen = 0, c_ml = 0, c_mid = 0;    // ... c_mid: the most frequent stage type
+  int ensure(const Layout& L, int B, hipStream_t stream);
+  void release();
+};
+}  // namespace landing
+
+// Everything a context owns.  Device blocks free themselves with the context; landing_destroy first waits for the work that may still use them.
 struct landing_ctx {
   Layout L;
   int device;
-  int* d_edge_map = nullptr;
+  DevBuf<int> d_edge_map;
   landing::SolverWorkspace ws;
-  double* d_prof = nullptr;
-  double* d_vbl = nullptr;
+  double* d_prof = nullptr;     // the caller's (landing_set_profile_buffer)
+  DevBuf<double> d_vbl;
   double* h_vbl = nullptr; hipEvent_t vbl_copied = nullptr;      // pinned staging block of landing_riccati_gains_batch and the event behind its copy
-  landing::RbdModel* d_rbd = nullptr;     // uploaded by landing_rbd_set_model
-  int2* d_rc_map = nullptr;               // landing_eval_hess_rc_batch: source nonzero + running-cost code of every entry of the extended pattern
-  double* d_fb_scratch = nullptr; size_t fb_scratch_n = 0;   // qdd and H^-1 per knot of the exact floating-base linearisation
-  double* d_h4 = nullptr; size_t h4_cap = 0;   // ... and its scratch for the casadi_s4-pattern nonzeros
+  DevBuf<landing::RbdModel> d_rbd;     // uploaded by landing_rbd_set_model
+  DevBuf<int2> d_rc_map;               // landing_eval_hess_rc_batch: source nonzero + running-cost code of every entry of the extended pattern
+  DevBuf<double> d_fb_scratch;         // qdd and H^-1 per knot of the exact floating-base linearisation
+  DevBuf<double> d_h4;                 // ... and its scratch for the casadi_s4-pattern nonzeros
   // function layer: the Jacobian, Hessian and residual kernels of one landing_eval_batch call are independent; for large
   // batches they run on two auxiliary streams forked from / joined to the caller's stream so that their ramps and tails overlap
   hipStream_t host_stream = nullptr;  // stream of the *_host entry points (copies + launch), created on first use
@@ -59,10 +97,11 @@ struct landing_ctx {
   // every scratch block above is re-used by the next call of its entry point, possibly on another stream: the launches that use it are
   // fenced by this event (recorded behind them, waited for before the next writer / reader touches the block) -- ADVICE r2
   hipEvent_t scratch_done = nullptr;
-  double* d_kd_ws = nullptr; size_t kd_cap = 0; int* d_kd_active = nullptr; int* d_kd_done = nullptr; int kd_done_cap = 0;      // workspace of landing_kinodyn_solve_batch (kd_capi.inc), count of members still iterating
+  DevBuf<double> d_kd_ws; DevBuf<int> d_kd_active, d_kd_done;      // workspace of landing_kinodyn_solve_batch (kd_capi.inc), count of members still iterating
   int kd_jpat_nnz[2] = {0, 0}; size_t kd_cpat_off = 0;
-  void* d_kd_jpat = nullptr;      // landing::KdJPat: structural non-zeros of the kinodynamic NLP's Jacobian blocks (kd_ensure_jpat, solver_capi.inc)
-  unsigned char* d_kd_pairs = nullptr; int kd_npair = 0; int rbd_std_base = 0;      // structurally non-zero pairs of a Hessian block of the kinodynamic NLP ([2][kd_npair]: i | j; solver_capi.inc, kd_ensure_pairs)
+  DevBuf<unsigned char> d_kd_jpat;      // [landing::KdJPat | landing::KdCPat at kd_cpat_off]: structural non-zeros of the kinodynamic NLP's Jacobian blocks (kd_ensure_jpat, solver_capi.inc)
+  DevBuf<unsigned char> d_kd_pairs; int kd_npair = 0; int rbd_std_base = 0;      // structurally non-zero pairs of a Hessian block of the kinodynamic NLP ([2][kd_npair]: i | j; solver_capi.inc, kd_ensure_pairs)
+  std::mutex kdc_mu; std::map<int, std::unique_ptr<KdCasadi, KdCasadiFree>> kdc;      // CasADi face of the kinodynamic NLP per N (kd_casadi_capi.inc)
   const double* wb_skip = nullptr;      // landing_wb_skip_taken: consumed by the next landing_wb_rollout
   int wb_semi = 0;             // integrator of the whole-body loop: 0 explicit Euler, 1 semi-implicit Euler (landing_wb_set_integrator)
   bool rbd_arrow = false;      // the model set by landing_rbd_set_model is "six base joints + four 3-joint legs on the base": H is block-arrow (wb_kernels.hip)
@@ -264,8 +303,8 @@ landing_ctx* landing_create(int N, int device, const landing_form* form) {
       if (!prev_entry) map[i] = nf++;
       if (!slip_entry) map[228 + i] = nl++;
     }
-    if (cu.size() != 228 || nf != 204 || nl != 180 || hipMalloc((void**)&c->d_edge_map, 456 * sizeof(int)) != hipSuccess ||
-        hipMemcpy(c->d_edge_map, map.data(), 456 * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+    if (cu.size() != 228 || nf != 204 || nl != 180 || c->d_edge_map.alloc(456) != hipSuccess ||
+        hipMemcpy(c->d_edge_map.get(), map.data(), 456 * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
       fail(LANDING_E_HIP, "landing_create: edge map setup failed"); delete c; return nullptr;
     }
   }
@@ -285,23 +324,12 @@ void landing_destroy(landing_ctx* ctx) {
   hipSetDevice(ctx->device);
   if (ctx->hs_obj) { landing_stream_destroy(ctx->hs_obj); ctx->hs_obj = nullptr; }
   ctx->ws.release();
-  if (ctx->d_edge_map) (void)hipFree(ctx->d_edge_map);
-  if (ctx->d_vbl) (void)hipFree(ctx->d_vbl);
   if (ctx->h_vbl) { (void)hipEventSynchronize(ctx->vbl_copied); (void)hipHostFree(ctx->h_vbl); (void)hipEventDestroy(ctx->vbl_copied); }
-  if (ctx->d_rbd) (void)hipFree(ctx->d_rbd);
-  if (ctx->d_rc_map) (void)hipFree(ctx->d_rc_map);
-  if (ctx->d_h4) (void)hipFree(ctx->d_h4);
-  if (ctx->d_fb_scratch) (void)hipFree(ctx->d_fb_scratch);
   for (int i = 0; i < 2; ++i) { if (ctx->aux[i]) (void)hipStreamDestroy(ctx->aux[i]); if (ctx->ev_join[i]) (void)hipEventDestroy(ctx->ev_join[i]); }
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
-  if (ctx->d_kd_pairs) (void)hipFree(ctx->d_kd_pairs);
-  if (ctx->d_kd_jpat) (void)hipFree(ctx->d_kd_jpat);
-  if (ctx->d_kd_ws) (void)hipFree(ctx->d_kd_ws);
-  if (ctx->d_kd_active) (void)hipFree(ctx->d_kd_active);
-  if (ctx->d_kd_done) (void)hipFree(ctx->d_kd_done);
   if (ctx->scratch_done) { (void)hipEventSynchronize(ctx->scratch_done); (void)hipEventDestroy(ctx->scratch_done); }
   if (ctx->host_stream) (void)hipStreamDestroy(ctx->host_stream);
-  delete ctx;
+  delete ctx;      // (the device blocks and the CasADi-face cache free themselves)
 }
 
 // ---- function layer -----------------------------------------------------------------------------
@@ -313,7 +341,7 @@ int landing_eval_batch(landing_ctx* ctx, int B, const double* d_x, const double*
   if ((d_hess || d_ggx || d_ggp) && !d_lam_g) return fail(LANDING_E_ARG, "landing_eval_batch: lam_g required for hess/grad_gamma");
   if (ctx->L.run_cost && d_hess) return fail(LANDING_E_ARG, "landing_eval_batch: with a running cost the Hessian does not fit the CCS pattern of the terminal-cost NLP; use landing_eval_hess_rc_batch");
   HIP_TRY(hipSetDevice(ctx->device));
-  landing::EvalArgs A{d_x, d_p, d_lam_f, d_lam_g, d_f, d_g, d_grad_f, d_jac, d_hess, d_ggx, d_ggp, ctx->d_edge_map, d_g ? 1 : 0};
+  landing::EvalArgs A{d_x, d_p, d_lam_f, d_lam_g, d_f, d_g, d_grad_f, d_jac, d_hess, d_ggx, d_ggp, ctx->d_edge_map.get(), d_g ? 1 : 0};
   if (ctx->L.N < 3) return fail(LANDING_E_ARG, "landing_eval_batch: N >= 3 required");
   hipStream_t s0 = (hipStream_t)stream, sj = s0, sh = s0;
   const bool fork = B >= 512 && d_jac && d_hess;
@@ -375,34 +403,22 @@ int landing_eval_hess_rc_batch(landing_ctx* ctx, int B, const double* d_x, const
       }
       if (i4 != c4[c + 1]) return fail(LANDING_E_ARG, "internal: hess_rc pattern does not contain casadi_s4");
     }
-    HIP_TRY(hipMalloc((void**)&ctx->d_rc_map, sizeof(int2) * (size_t)nrc));
-    HIP_TRY(hipMemcpy(ctx->d_rc_map, map.data(), sizeof(int2) * (size_t)nrc, hipMemcpyHostToDevice));
+    DevBuf<int2> d_map;
+    HIP_TRY(d_map.alloc((size_t)nrc));
+    HIP_TRY(hipMemcpy(d_map.get(), map.data(), sizeof(int2) * (size_t)nrc, hipMemcpyHostToDevice));
+    ctx->d_rc_map = std::move(d_map);      // set once filled
   }
-  const size_t need = (size_t)B * L.nnz_hess;
-  if (ctx->h4_cap < need) {
-    if (ctx->d_h4) HIP_TRY(hipFree(ctx->d_h4));      // hipFree waits for the device: no launch still reads the old block
-    ctx->d_h4 = nullptr; ctx->h4_cap = 0;
-    HIP_TRY(hipMalloc((void**)&ctx->d_h4, need * sizeof(double)));
-    ctx->h4_cap = need;
-  }
+  HIP_TRY(ctx->d_h4.grow((size_t)B * L.nnz_hess));      // hipFree waits for the device: no launch still reads the old block
   hipStream_t s0 = (hipStream_t)stream;
   HIP_TRY(scratch_acquire(ctx, s0));
-  landing::EvalArgs A{d_x, d_p, d_lam_f, d_lam_g, nullptr, nullptr, nullptr, nullptr, ctx->d_h4, nullptr, nullptr, ctx->d_edge_map, 0};
+  landing::EvalArgs A{d_x, d_p, d_lam_f, d_lam_g, nullptr, nullptr, nullptr, nullptr, ctx->d_h4.get(), nullptr, nullptr, ctx->d_edge_map.get(), 0};
   hipLaunchKernelGGL(landing::landing_sweep_kernel<1>, dim3(B), dim3(64), (size_t)landing::landing_sweep_tile_rows(L.N) * landing::TILE_LD * sizeof(double), s0, L, B, A);
   hipLaunchKernelGGL(landing::landing_sweep_misc_kernel<true>, dim3(B), dim3(64), 0, s0, L, B, A);     // terminal-cost block of the Hessian
-  hipLaunchKernelGGL(landing::landing_hess_rc_kernel, dim3((nrc + 255) / 256, B), dim3(256), 0, s0, L, B, nrc, ctx->d_rc_map, ctx->d_h4, d_p, d_lam_f, d_hess_rc);
+  hipLaunchKernelGGL(landing::landing_hess_rc_kernel, dim3((nrc + 255) / 256, B), dim3(256), 0, s0, L, B, nrc, ctx->d_rc_map.get(), ctx->d_h4.get(), d_p, d_lam_f, d_hess_rc);
   HIP_TRY(hipGetLastError());
   HIP_TRY(scratch_release(ctx, s0));
   return 0;
 }
-
-namespace {
-struct DevBuf {
-  double* p = nullptr;
-  ~DevBuf() { if (p) hipFree(p); }
-  hipError_t alloc(size_t n) { return hipMalloc((void**)&p, n * sizeof(double)); }
-};
-}  // namespace
 
 int landing_eval_batch_host(landing_ctx* ctx, int B, const double* x, const double* p, const double* lam_f,
                             const double* lam_g, double* f, double* g, double* grad_f, double* jac, double* hess,
@@ -410,13 +426,13 @@ int landing_eval_batch_host(landing_ctx* ctx, int B, const double* x, const doub
   if (!ctx || B <= 0 || !x || !p) return fail(LANDING_E_ARG, "landing_eval_batch_host: bad argument");
   const Layout& L = ctx->L;
   HIP_TRY(hipSetDevice(ctx->device));
-  DevBuf dx, dp, dlf, dlg, df, dg, dgf, dj, dh, dgx, dgp;
+  DevBuf<double> dx, dp, dlf, dlg, df, dg, dgf, dj, dh, dgx, dgp;
   const size_t b = (size_t)B;
   HIP_TRY(dx.alloc(b * L.nx)); HIP_TRY(dp.alloc(b * L.np));
-  HIP_TRY(hipMemcpy(dx.p, x, b * L.nx * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dp.p, p, b * L.np * 8, hipMemcpyHostToDevice));
-  if (lam_f) { HIP_TRY(dlf.alloc(b)); HIP_TRY(hipMemcpy(dlf.p, lam_f, b * 8, hipMemcpyHostToDevice)); }
-  if (lam_g) { HIP_TRY(dlg.alloc(b * L.ng)); HIP_TRY(hipMemcpy(dlg.p, lam_g, b * L.ng * 8, hipMemcpyHostToDevice)); }
+  HIP_TRY(hipMemcpy(dx.get(), x, b * L.nx * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dp.get(), p, b * L.np * 8, hipMemcpyHostToDevice));
+  if (lam_f) { HIP_TRY(dlf.alloc(b)); HIP_TRY(hipMemcpy(dlf.get(), lam_f, b * 8, hipMemcpyHostToDevice)); }
+  if (lam_g) { HIP_TRY(dlg.alloc(b * L.ng)); HIP_TRY(hipMemcpy(dlg.get(), lam_g, b * L.ng * 8, hipMemcpyHostToDevice)); }
   if (f) HIP_TRY(df.alloc(b));
   if (g) HIP_TRY(dg.alloc(b * L.ng));
   if (grad_f) HIP_TRY(dgf.alloc(b * L.nx));
@@ -424,16 +440,16 @@ int landing_eval_batch_host(landing_ctx* ctx, int B, const double* x, const doub
   if (hess) HIP_TRY(dh.alloc(b * L.nnz_hess));
   if (ggx) HIP_TRY(dgx.alloc(b * L.nx));
   if (ggp) HIP_TRY(dgp.alloc(b * L.np));
-  int rc = landing_eval_batch(ctx, B, dx.p, dp.p, dlf.p, dlg.p, df.p, dg.p, dgf.p, dj.p, dh.p, dgx.p, dgp.p, nullptr);
+  int rc = landing_eval_batch(ctx, B, dx.get(), dp.get(), dlf.get(), dlg.get(), df.get(), dg.get(), dgf.get(), dj.get(), dh.get(), dgx.get(), dgp.get(), nullptr);
   if (rc) return rc;
   HIP_TRY(hipDeviceSynchronize());
-  if (f) HIP_TRY(hipMemcpy(f, df.p, b * 8, hipMemcpyDeviceToHost));
-  if (g) HIP_TRY(hipMemcpy(g, dg.p, b * L.ng * 8, hipMemcpyDeviceToHost));
-  if (grad_f) HIP_TRY(hipMemcpy(grad_f, dgf.p, b * L.nx * 8, hipMemcpyDeviceToHost));
-  if (jac) HIP_TRY(hipMemcpy(jac, dj.p, b * L.nnz_jac * 8, hipMemcpyDeviceToHost));
-  if (hess) HIP_TRY(hipMemcpy(hess, dh.p, b * L.nnz_hess * 8, hipMemcpyDeviceToHost));
-  if (ggx) HIP_TRY(hipMemcpy(ggx, dgx.p, b * L.nx * 8, hipMemcpyDeviceToHost));
-  if (ggp) HIP_TRY(hipMemcpy(ggp, dgp.p, b * L.np * 8, hipMemcpyDeviceToHost));
+  if (f) HIP_TRY(hipMemcpy(f, df.get(), b * 8, hipMemcpyDeviceToHost));
+  if (g) HIP_TRY(hipMemcpy(g, dg.get(), b * L.ng * 8, hipMemcpyDeviceToHost));
+  if (grad_f) HIP_TRY(hipMemcpy(grad_f, dgf.get(), b * L.nx * 8, hipMemcpyDeviceToHost));
+  if (jac) HIP_TRY(hipMemcpy(jac, dj.get(), b * L.nnz_jac * 8, hipMemcpyDeviceToHost));
+  if (hess) HIP_TRY(hipMemcpy(hess, dh.get(), b * L.nnz_hess * 8, hipMemcpyDeviceToHost));
+  if (ggx) HIP_TRY(hipMemcpy(ggx, dgx.get(), b * L.nx * 8, hipMemcpyDeviceToHost));
+  if (ggp) HIP_TRY(hipMemcpy(ggp, dgp.get(), b * L.np * 8, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -442,16 +458,16 @@ int landing_eval_hess_rc_batch_host(landing_ctx* ctx, int B, const double* x, co
   if (!ctx || B <= 0 || !x || !p || !lam_g || !hess_rc) return fail(LANDING_E_ARG, "landing_eval_hess_rc_batch_host: bad argument");
   const Layout& L = ctx->L;
   HIP_TRY(hipSetDevice(ctx->device));
-  DevBuf dx, dp, dlf, dlg, dh;
+  DevBuf<double> dx, dp, dlf, dlg, dh;
   const size_t b = (size_t)B, nrc = (size_t)landing_nnz_hess_rc(L.N);
   HIP_TRY(dx.alloc(b * L.nx)); HIP_TRY(dp.alloc(b * L.np)); HIP_TRY(dlg.alloc(b * L.ng)); HIP_TRY(dh.alloc(b * nrc));
-  HIP_TRY(hipMemcpy(dx.p, x, b * L.nx * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dp.p, p, b * L.np * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dlg.p, lam_g, b * L.ng * 8, hipMemcpyHostToDevice));
-  if (lam_f) { HIP_TRY(dlf.alloc(b)); HIP_TRY(hipMemcpy(dlf.p, lam_f, b * 8, hipMemcpyHostToDevice)); }
-  if (int rc = landing_eval_hess_rc_batch(ctx, B, dx.p, dp.p, dlf.p, dlg.p, dh.p, nullptr)) return rc;
+  HIP_TRY(hipMemcpy(dx.get(), x, b * L.nx * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dp.get(), p, b * L.np * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dlg.get(), lam_g, b * L.ng * 8, hipMemcpyHostToDevice));
+  if (lam_f) { HIP_TRY(dlf.alloc(b)); HIP_TRY(hipMemcpy(dlf.get(), lam_f, b * 8, hipMemcpyHostToDevice)); }
+  if (int rc = landing_eval_hess_rc_batch(ctx, B, dx.get(), dp.get(), dlf.get(), dlg.get(), dh.get(), nullptr)) return rc;
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(hess_rc, dh.p, b * nrc * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hess_rc, dh.get(), b * nrc * 8, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -1,9 +1,6 @@
 // kd_capi.inc -- host side of the kinodynamic refinement solve (included by capi.hip; kernels in kd_solver_kernels.hip, function layer in
 // rbd_kernels.hip).  The interior-point loop runs here, one round of launches per iteration for the whole batch (members that have finished
 // are skipped by every kernel); the only host <-> device traffic inside the loop is the 4-byte count of members still iterating.
-namespace {
-struct KdWorkspace { double* buf = nullptr; size_t cap = 0; int* d_flags = nullptr; int flags_cap = 0; };
-}
 
 extern "C" {
 
@@ -69,23 +66,21 @@ int landing_kinodyn_solve_batch(landing_ctx* ctx, int B, int N, const landing_ki
   const int cloneF = (o.kd_clone_after > 0 && o.kd_clone_max > 0 && o.max_iter > 0) ? (o.kd_clone_max < B ? o.kd_clone_max : B) : 0;
   const int S = cloneF * landing::KD_NVAR * landing::KD_NWAVE, BT = B + S;
   const size_t stride = landing::kd_ws_stride(N), need = stride * (size_t)BT;
-  if (ctx->kd_cap < need) {
-    if (ctx->d_kd_ws) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(ctx->d_kd_ws); ctx->d_kd_ws = nullptr; ctx->kd_cap = 0; }
-    HIP_TRY(hipMalloc((void**)&ctx->d_kd_ws, need * sizeof(double)));
-    ctx->kd_cap = need;
+  if (ctx->d_kd_ws.size() < need) {
+    if (ctx->d_kd_ws) HIP_TRY(hipDeviceSynchronize());      // (a launch of an earlier call may still use the old block)
+    HIP_TRY(ctx->d_kd_ws.grow(need));
   }
   // counters: derivative list A | members still iterating | members the head kernel has prepared this round | derivative list B  (the two in the middle and the list of the NEXT round are cleared by one memset per round)
-  if (!ctx->d_kd_active) HIP_TRY(hipMalloc((void**)&ctx->d_kd_active, 4 * sizeof(int)));
-  const int nflag = BT + S + 3 * B + 3 * BT;      // done [BT] | src [S] | win [B] | cloned [B] | win_prev [B] | work list of the condensation [BT] | derivative lists A, B [BT] each
-  if (ctx->kd_done_cap < nflag) {
-    if (ctx->d_kd_done) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(ctx->d_kd_done); ctx->d_kd_done = nullptr; ctx->kd_done_cap = 0; }
-    HIP_TRY(hipMalloc((void**)&ctx->d_kd_done, (size_t)nflag * sizeof(int)));
-    ctx->kd_done_cap = nflag;
+  if (!ctx->d_kd_active) HIP_TRY(ctx->d_kd_active.alloc(4));
+  const size_t nflag = (size_t)BT + S + 3 * B + 3 * BT;      // done [BT] | src [S] | win [B] | cloned [B] | win_prev [B] | work list of the condensation [BT] | derivative lists A, B [BT] each
+  if (ctx->d_kd_done.size() < nflag) {
+    if (ctx->d_kd_done) HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(ctx->d_kd_done.grow(nflag));
   }
   landing::KdSolveArgs A;
-  A.model = ctx->d_rbd; A.B = BT; A.N = N; A.o = o;
+  A.model = ctx->d_rbd.get(); A.B = BT; A.N = N; A.o = o;
   A.B0 = B; A.F = cloneF > 0 ? cloneF : 1; A.m_lo = 0;
-  A.src = ctx->d_kd_done + BT; A.win = S > 0 ? A.src + S : nullptr; A.cloned = A.src + S + B; A.win_prev = A.cloned + B; A.cond_list = A.src + S + 3 * B;
+  A.src = ctx->d_kd_done.get() + BT; A.win = S > 0 ? A.src + S : nullptr; A.cloned = A.src + S + B; A.win_prev = A.cloned + B; A.cond_list = A.src + S + 3 * B;
   // the clones' option sets: what decided the outliers of five bench batches in 28 .. 73 iterations (profiles/r05_ab_experiments.txt, tools/dev/kd_variants.py) --
   // the step rule with 16 clipped slacks, the same with the slacks pushed 0.1 into their rows, a first barrier parameter of 1
   for (int v = 0; v < landing::KD_NVAR; ++v) { A.ov[v] = o; A.ov[v].max_iter = o.kd_clone_iter > 0 ? o.kd_clone_iter : 200; }
@@ -97,23 +92,24 @@ int landing_kinodyn_solve_batch(landing_ctx* ctx, int B, int N, const landing_ki
   for (int i = 0; i < 3; ++i) { A.P.Ib[i] = prm->Ib[i]; A.P.Ibi[i] = prm->Ib_inv[i]; }
   { const int rc = kd_ensure_pairs(ctx, A.P); if (rc) return rc; }      // structurally non-zero pairs of a Hessian block (solver_capi.inc)
   { const int rc = kd_ensure_jpat(ctx); if (rc) return rc; }            // structurally non-zero entries of a Jacobian block (solver_capi.inc)
-  A.jpat = (const landing::KdJPat*)ctx->d_kd_jpat; A.cpat = (const landing::KdCPat*)((const char*)ctx->d_kd_jpat + ctx->kd_cpat_off);
-  A.x0 = d_x0; A.lb = d_lbg; A.ub = d_ubg; A.cost = d_cost; A.ws = ctx->d_kd_ws; A.ws_stride = stride;
-  A.x_out = d_x; A.f_out = d_f; A.lam_out = d_lam_g; A.status = d_status; A.iters = d_iters; A.kkt = d_kkt; A.n_active = ctx->d_kd_active + 1; A.n_cond = ctx->d_kd_active + 2; A.done = ctx->d_kd_done;
-  int* const dlist[2] = {A.cond_list + BT, A.cond_list + 2 * BT}; int* const dcnt[2] = {ctx->d_kd_active, ctx->d_kd_active + 3};
+  A.jpat = (const landing::KdJPat*)ctx->d_kd_jpat.get(); A.cpat = (const landing::KdCPat*)(ctx->d_kd_jpat.get() + ctx->kd_cpat_off);
+  A.x0 = d_x0; A.lb = d_lbg; A.ub = d_ubg; A.cost = d_cost; A.ws = ctx->d_kd_ws.get(); A.ws_stride = stride;
+  int* const cnt = ctx->d_kd_active.get();
+  A.x_out = d_x; A.f_out = d_f; A.lam_out = d_lam_g; A.status = d_status; A.iters = d_iters; A.kkt = d_kkt; A.n_active = cnt + 1; A.n_cond = cnt + 2; A.done = ctx->d_kd_done.get();
+  int* const dlist[2] = {A.cond_list + BT, A.cond_list + 2 * BT}; int* const dcnt[2] = {cnt, cnt + 3};
   A.dlist_next = dlist[0]; A.n_dnext = dcnt[0];      // (the init kernel fills the list of round 0)
   // function-layer launches straight into the workspace of every member
   const size_t nx = (size_t)landing::kd_nx(N), ng = (size_t)landing::kd_ng(N);
   landing::KdNlpArgs F;
-  F.model = ctx->d_rbd; F.P = A.P; F.B = BT; F.N = N;
-  F.x = ctx->d_kd_ws;                           // M.x is the first array of a member's block
-  F.lam = ctx->d_kd_ws + 4 * nx + 6 * ng;       // M.y
+  F.model = ctx->d_rbd.get(); F.P = A.P; F.B = BT; F.N = N;
+  F.x = A.ws;                           // M.x is the first array of a member's block
+  F.lam = A.ws + 4 * nx + 6 * ng;       // M.y
   F.g = nullptr;
-  F.jac = ctx->d_kd_ws + 4 * nx + 10 * ng;      // M.J
+  F.jac = A.ws + 4 * nx + 10 * ng;      // M.J
   F.jcol = &A.cpat->jcol[0][0][0];               // the Jacobian kernel writes compact blocks (rbd_kernels.hip KD_JCS)
   F.hess = F.jac + (size_t)N * landing::KD_JCS;      // (compact Jacobian blocks)
   F.jty = F.hess + (size_t)N * landing::KD_NW * landing::KD_NW + (size_t)(N + 1) * landing::KD_REC + (size_t)N * landing::KD_NW;      // M.jty (behind H, the records and wbuf)
-  F.sx = F.sg = F.sj = F.sh = (long long)stride; F.skip = ctx->d_kd_done;
+  F.sx = F.sg = F.sj = F.sh = (long long)stride; F.skip = A.done;
   // structural zeros of the Hessian blocks are written once; the kernel rewrites the 561 pairs of every block each iteration.  (The whole
   // workspace is cleared: the blocks are its largest part.)
   const long long nj = (long long)BT * N * landing::KD_NW, nh = (long long)BT * N * ctx->kd_npair;
@@ -123,15 +119,15 @@ int landing_kinodyn_solve_batch(landing_ctx* ctx, int B, int N, const landing_ki
   // whatever path leaves this function from here on, the work queued so far is fenced for the next user of the context's scratch blocks (ADVICE r5: the error returns
   // below used to skip scratch_release, and the next call on another stream was then not ordered behind the memsets and launches already queued)
   struct ScratchGuard { landing_ctx* c; hipStream_t s; ~ScratchGuard() { (void)scratch_release(c, s); } } scratch_guard{ctx, st};
-  HIP_TRY(hipMemsetAsync(ctx->d_kd_ws, 0, need * sizeof(double), st));
+  HIP_TRY(hipMemsetAsync(A.ws, 0, need * sizeof(double), st));
   if (S > 0) {      // clone slots start unused (src = -1) and "finished" for the derivative kernels; no family has a winner
-    HIP_TRY(hipMemsetAsync(ctx->d_kd_done + B, 0x01, (size_t)S * sizeof(int), st));      // (any non-zero word: only the originals' flags are compared with 1)
+    HIP_TRY(hipMemsetAsync(A.done + B, 0x01, (size_t)S * sizeof(int), st));      // (any non-zero word: only the originals' flags are compared with 1)
     HIP_TRY(hipMemsetAsync(A.src, 0xff, (size_t)S * sizeof(int), st));
     HIP_TRY(hipMemsetAsync(A.win, 0x7f, (size_t)B * sizeof(int), st));      // KD_NOWIN
     HIP_TRY(hipMemsetAsync(A.cloned + B, 0x7f, (size_t)B * sizeof(int), st));      // win_prev
     HIP_TRY(hipMemsetAsync(A.cloned, 0, (size_t)B * sizeof(int), st));
   }
-  HIP_TRY(hipMemsetAsync(ctx->d_kd_active, 0, 4 * sizeof(int), st));
+  HIP_TRY(hipMemsetAsync(cnt, 0, 4 * sizeof(int), st));
   hipLaunchKernelGGL(landing::landing_kd_init_kernel, dim3(B), dim3(landing::KD_THREADS), 0, st, A);
   // The derivative launches cover the members of the round's list (kd_solver_kernels.hip dlist_next), gridded for `bound` members: the count the host saw at its last look
   // (+ the clones posed since) -- a launch over the whole batch cost 0.1-0.2 ms of workgroups that leave at once per round of the lock-step tail
@@ -141,7 +137,7 @@ int landing_kinodyn_solve_batch(landing_ctx* ctx, int B, int N, const landing_ki
     const int nbd = bound < BT ? bound : BT;
     kd_launch_jac(ctx, F, nbd, N, st);
     if (with_hess)
-      kd_launch_hess(ctx, F, nbd, N, (const unsigned char*)ctx->d_kd_pairs, (const unsigned char*)ctx->d_kd_pairs + ctx->kd_npair, ctx->kd_npair, st);
+      kd_launch_hess(ctx, F, nbd, N, ctx->d_kd_pairs.get(), ctx->d_kd_pairs.get() + ctx->kd_npair, ctx->kd_npair, st);
   };
   int active = B;
   // (rounds, not iterations: a member whose inertia correction is spread over several launches needs more rounds than iterations; its own
@@ -160,7 +156,7 @@ int landing_kinodyn_solve_batch(landing_ctx* ctx, int B, int N, const landing_ki
       }
     derivs(true);
     const bool look = (it % KD_SYNC_EVERY) == KD_SYNC_EVERY - 1 || it == max_rounds;
-    HIP_TRY(hipMemsetAsync(ctx->d_kd_active + (cur == 0 ? 1 : 0), 0, 3 * sizeof(int), st));      // members still iterating, members prepared, the list of the next round
+    HIP_TRY(hipMemsetAsync(cnt + (cur == 0 ? 1 : 0), 0, 3 * sizeof(int), st));      // members still iterating, members prepared, the list of the next round
     A.dlist_next = dlist[cur ^ 1]; A.n_dnext = dcnt[cur ^ 1]; A.dlist_cur = dlist[cur]; A.n_dcur = dcnt[cur];
     if (S > 0 && it >= (long long)o.kd_clone_after) HIP_TRY(hipMemcpyAsync(A.cloned + B, A.win, (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, st));      // winners of the earlier rounds end their relatives in this one
     // three launches per iteration (kd_solver_kernels.hip): head (stop test, barrier parameter) | condensation of the inequality rows, one workgroup per member and interval |
@@ -253,28 +249,25 @@ int landing_kinodyn_solve_batch_host(landing_ctx* ctx, int B, int N, const landi
   if (!opts && !status) { status_own.resize((size_t)B); status = status_own.data(); }
   HIP_TRY(hipSetDevice(ctx->device));
   const size_t nx = (size_t)landing::kd_nx(N), ng = (size_t)landing::kd_ng(N);
-  double *d_lb = nullptr, *d_ub = nullptr, *d_cost = nullptr, *d_x0 = nullptr, *d_x = nullptr, *d_f = nullptr, *d_lam = nullptr, *d_kkt = nullptr;
-  int *d_st = nullptr, *d_it = nullptr;
-  auto cleanup = [&]() { for (void* q : {(void*)d_lb, (void*)d_ub, (void*)d_cost, (void*)d_x0, (void*)d_x, (void*)d_f, (void*)d_lam, (void*)d_kkt, (void*)d_st, (void*)d_it}) if (q) (void)hipFree(q); };
-#define KD_TRY(e) do { hipError_t e_ = (e); if (e_ != hipSuccess) { cleanup(); return fail(LANDING_E_HIP, std::string(#e) + ": " + hipGetErrorString(e_)); } } while (0)
-  KD_TRY(hipMalloc((void**)&d_lb, B * ng * sizeof(double))); KD_TRY(hipMalloc((void**)&d_ub, B * ng * sizeof(double)));
-  KD_TRY(hipMalloc((void**)&d_cost, (size_t)B * 24 * sizeof(double))); KD_TRY(hipMalloc((void**)&d_x0, B * nx * sizeof(double)));
-  KD_TRY(hipMalloc((void**)&d_x, B * nx * sizeof(double))); KD_TRY(hipMalloc((void**)&d_f, (size_t)B * sizeof(double)));
-  KD_TRY(hipMalloc((void**)&d_lam, B * ng * sizeof(double))); KD_TRY(hipMalloc((void**)&d_kkt, (size_t)B * 3 * sizeof(double)));
-  KD_TRY(hipMalloc((void**)&d_st, (size_t)B * sizeof(int))); KD_TRY(hipMalloc((void**)&d_it, (size_t)B * sizeof(int)));
-  KD_TRY(hipMemcpy(d_lb, lbg, B * ng * sizeof(double), hipMemcpyHostToDevice)); KD_TRY(hipMemcpy(d_ub, ubg, B * ng * sizeof(double), hipMemcpyHostToDevice));
-  KD_TRY(hipMemcpy(d_cost, cost, (size_t)B * 24 * sizeof(double), hipMemcpyHostToDevice)); KD_TRY(hipMemcpy(d_x0, x0, B * nx * sizeof(double), hipMemcpyHostToDevice));
-  const int rc = landing_kinodyn_solve_batch(ctx, B, N, prm, d_lb, d_ub, d_cost, d_x0, opts, d_x, d_f, d_lam, d_st, d_it, d_kkt, nullptr);
-  if (rc) { cleanup(); return rc; }
-  KD_TRY(hipDeviceSynchronize());
-  KD_TRY(hipMemcpy(x, d_x, B * nx * sizeof(double), hipMemcpyDeviceToHost));
-  if (f) KD_TRY(hipMemcpy(f, d_f, (size_t)B * sizeof(double), hipMemcpyDeviceToHost));
-  if (lam_g) KD_TRY(hipMemcpy(lam_g, d_lam, B * ng * sizeof(double), hipMemcpyDeviceToHost));
-  if (status) KD_TRY(hipMemcpy(status, d_st, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
-  if (iters) KD_TRY(hipMemcpy(iters, d_it, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
-  if (kkt) KD_TRY(hipMemcpy(kkt, d_kkt, (size_t)B * 3 * sizeof(double), hipMemcpyDeviceToHost));
-#undef KD_TRY
-  cleanup();
+  const size_t b = (size_t)B;
+  {
+    DevBuf<double> d_lb, d_ub, d_cost, d_x0, d_x, d_f, d_lam, d_kkt;
+    DevBuf<int> d_st, d_it;
+    HIP_TRY(d_lb.alloc(b * ng)); HIP_TRY(d_ub.alloc(b * ng)); HIP_TRY(d_cost.alloc(b * 24)); HIP_TRY(d_x0.alloc(b * nx));
+    HIP_TRY(d_x.alloc(b * nx)); HIP_TRY(d_f.alloc(b)); HIP_TRY(d_lam.alloc(b * ng)); HIP_TRY(d_kkt.alloc(b * 3));
+    HIP_TRY(d_st.alloc(b)); HIP_TRY(d_it.alloc(b));
+    HIP_TRY(hipMemcpy(d_lb.get(), lbg, b * ng * sizeof(double), hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(d_ub.get(), ubg, b * ng * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_cost.get(), cost, b * 24 * sizeof(double), hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(d_x0.get(), x0, b * nx * sizeof(double), hipMemcpyHostToDevice));
+    const int rc = landing_kinodyn_solve_batch(ctx, B, N, prm, d_lb.get(), d_ub.get(), d_cost.get(), d_x0.get(), opts, d_x.get(), d_f.get(), d_lam.get(), d_st.get(), d_it.get(), d_kkt.get(), nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(x, d_x.get(), b * nx * sizeof(double), hipMemcpyDeviceToHost));
+    if (f) HIP_TRY(hipMemcpy(f, d_f.get(), b * sizeof(double), hipMemcpyDeviceToHost));
+    if (lam_g) HIP_TRY(hipMemcpy(lam_g, d_lam.get(), b * ng * sizeof(double), hipMemcpyDeviceToHost));
+    if (status) HIP_TRY(hipMemcpy(status, d_st.get(), b * sizeof(int), hipMemcpyDeviceToHost));
+    if (iters) HIP_TRY(hipMemcpy(iters, d_it.get(), b * sizeof(int), hipMemcpyDeviceToHost));
+    if (kkt) HIP_TRY(hipMemcpy(kkt, d_kkt.get(), b * 3 * sizeof(double), hipMemcpyDeviceToHost));
+  }      // (the staging blocks go before the retry ladder allocates its own)
   // ---- retry ladder (default options only): the members the first pass left undecided (iteration limit / numerical failure) are solved again
   // from the same initial guess with another slack initialisation, then with a smaller first barrier parameter.  Which members end undecided
   // depends on the path, not on the problem: on the hard sampling law 19 of 1024 with the defaults, 17 with each of the two alternatives, and
@@ -373,17 +366,18 @@ int landing_kinodyn_pattern(landing_ctx* ctx, int N, int which /* 0 = jac_g_x, 1
   auto rnd = [&]() { sd ^= sd << 13; sd ^= sd >> 7; sd ^= sd << 17; return (double)(sd >> 11) / 9007199254740992.0 - 0.5; };
   for (auto& v : x) v = 0.8 * rnd() + 0.05;
   for (auto& v : lam) v = rnd() + 0.01;
-  double *d_x = nullptr, *d_l = nullptr, *d_o = nullptr;
   const size_t no = (size_t)T * N * (which ? NW * NW : NR * NW);
-  auto cleanup = [&]() { if (d_x) (void)hipFree(d_x); if (d_l) (void)hipFree(d_l); if (d_o) (void)hipFree(d_o); };
-  if (hipMalloc((void**)&d_x, x.size() * 8) != hipSuccess || hipMalloc((void**)&d_l, lam.size() * 8) != hipSuccess || hipMalloc((void**)&d_o, no * 8) != hipSuccess) { cleanup(); return fail(LANDING_E_HIP, "landing_kinodyn_pattern: hipMalloc"); }
-  (void)hipMemcpy(d_x, x.data(), x.size() * 8, hipMemcpyHostToDevice); (void)hipMemcpy(d_l, lam.data(), lam.size() * 8, hipMemcpyHostToDevice);
-  (void)hipMemset(d_o, 0, no * 8);
-  int rc = which ? landing_kinodyn_nlp_hess(ctx, T, N, d_x, &prm, d_l, d_o, nullptr) : landing_kinodyn_nlp_eval(ctx, T, N, d_x, &prm, nullptr, d_o, nullptr);
   std::vector<double> out(no);
-  if (!rc && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out.data(), d_o, no * 8, hipMemcpyDeviceToHost) != hipSuccess)) rc = fail(LANDING_E_HIP, "landing_kinodyn_pattern: copy");
-  cleanup();
-  if (rc) return rc;
+  {
+    DevBuf<double> d_x, d_l, d_o;
+    HIP_TRY(d_x.alloc(x.size())); HIP_TRY(d_l.alloc(lam.size())); HIP_TRY(d_o.alloc(no));
+    HIP_TRY(hipMemcpy(d_x.get(), x.data(), x.size() * 8, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(d_l.get(), lam.data(), lam.size() * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(d_o.get(), 0, no * 8));
+    const int rc = which ? landing_kinodyn_nlp_hess(ctx, T, N, d_x.get(), &prm, d_l.get(), d_o.get(), nullptr) : landing_kinodyn_nlp_eval(ctx, T, N, d_x.get(), &prm, nullptr, d_o.get(), nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out.data(), d_o.get(), no * 8, hipMemcpyDeviceToHost));
+  }
   // x index of block column j of interval k (kd_w_index, host copy)
   auto widx = [&](int k, int j) {
     const int oJ = 12 * (N + 1), oU = oJ + 12 * N;
@@ -433,7 +427,7 @@ int landing_kinodyn_block_nonzeros(landing_ctx* ctx, int* nnz_mid, int* nnz_last
   *nnz_mid = ctx->kd_jpat_nnz[0]; *nnz_last = ctx->kd_jpat_nnz[1];
   if (entries) {
     std::vector<landing::KdJPat> T(1);
-    HIP_TRY(hipMemcpy(T.data(), ctx->d_kd_jpat, sizeof(landing::KdJPat), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(T.data(), ctx->d_kd_jpat.get(), sizeof(landing::KdJPat), hipMemcpyDeviceToHost));
     size_t n = 0;
     for (int lp = 0; lp < 2; ++lp) {
       const int nrow = (lp ? landing::KD_ROWS_LAST : landing::KD_ROWS) - 12;

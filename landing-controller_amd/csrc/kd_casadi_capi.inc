@@ -21,11 +21,9 @@ struct KdCasadi {
   std::vector<int> jsrc;                            // Jacobian nonzero -> index into the block array [N][141][72], or -1: the constant 1 of a boundary row
   std::vector<std::array<int, 2>> hsrc;             // Hessian nonzero -> up to two entries of the block array [N][72][72] (shared X_k+1 / c_k+1 pairs), -1: none
   std::vector<int> hterm;                           // ... and the index i of the terminal-cost diagonal 2 QN_i, or -1
-  double *d_x = nullptr, *d_l = nullptr, *d_g = nullptr, *d_j = nullptr, *d_h = nullptr;
-  ~KdCasadi() { for (double* q : {d_x, d_l, d_g, d_j, d_h}) if (q) (void)hipFree(q); }
+  DevBuf<double> d_x, d_l, d_g, d_j, d_h;
 };
-std::mutex g_kdc_mu;
-std::map<std::pair<landing_ctx*, int>, std::unique_ptr<KdCasadi>> g_kdc;
+void KdCasadiFree::operator()(KdCasadi* k) const { delete k; }
 
 int kdc_widx(int N, int k, int j) {
   const int oJ = 12 * (N + 1), oU = oJ + 12 * N;
@@ -60,12 +58,12 @@ int landing_kinodyn_casadi_bounds(int N, const landing_kinodyn_form* form, const
 
 int landing_kinodyn_casadi_pattern(landing_ctx* ctx, int N, int which, const long long** colind, const long long** row, long long* nnz);
 
+// the context's cache for horizon N, built at the first call
 static KdCasadi* kdc_get(landing_ctx* ctx, int N) {
-  std::lock_guard<std::mutex> lk(g_kdc_mu);
-  auto key = std::make_pair(ctx, N);
-  auto it = g_kdc.find(key);
-  if (it != g_kdc.end()) return it->second.get();
-  std::unique_ptr<KdCasadi> K(new KdCasadi());
+  std::lock_guard<std::mutex> lk(ctx->kdc_mu);
+  auto it = ctx->kdc.find(N);
+  if (it != ctx->kdc.end()) return it->second.get();
+  std::unique_ptr<KdCasadi, KdCasadiFree> K(new KdCasadi());
   K->N = N;
   const int nx = landing::kd_nx(N), ng = landing::kd_ng(N), NW = landing::KD_NW, NR = landing::KD_ROWS;
   for (int which = 0; which < 2; ++which) {
@@ -93,18 +91,19 @@ static KdCasadi* kdc_get(landing_ctx* ctx, int N) {
     for (int k = 0; k < N; ++k) { const int a = inv[k][lo], b = inv[k][hi]; if (a >= 0 && b >= 0 && n < 2) K->hsrc[q][n++] = (k * NW + a) * NW + b; }
     if (lo == hi && lo >= 12 * N && lo < 12 * (N + 1)) K->hterm[q] = lo - 12 * N;
   }
-  if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc((void**)&K->d_x, (size_t)nx * 8) != hipSuccess || hipMalloc((void**)&K->d_l, (size_t)ng * 8) != hipSuccess ||
-      hipMalloc((void**)&K->d_g, (size_t)ng * 8) != hipSuccess || hipMalloc((void**)&K->d_j, (size_t)N * NR * NW * 8) != hipSuccess || hipMalloc((void**)&K->d_h, (size_t)N * NW * NW * 8) != hipSuccess) {
+  if (hipSetDevice(ctx->device) != hipSuccess || K->d_x.alloc((size_t)nx) != hipSuccess || K->d_l.alloc((size_t)ng) != hipSuccess ||
+      K->d_g.alloc((size_t)ng) != hipSuccess || K->d_j.alloc((size_t)N * NR * NW) != hipSuccess || K->d_h.alloc((size_t)N * NW * NW) != hipSuccess) {
     fail(LANDING_E_HIP, "landing_kinodyn_casadi: hipMalloc"); return nullptr;
   }
   KdCasadi* raw = K.get();
-  g_kdc[key] = std::move(K);
+  ctx->kdc[N] = std::move(K);
   return raw;
 }
 
-void landing_kinodyn_casadi_release(landing_ctx* ctx) {      // call before landing_destroy of a context that evaluated through this face
-  std::lock_guard<std::mutex> lk(g_kdc_mu);
-  for (auto it = g_kdc.begin(); it != g_kdc.end();) { if (it->first.first == ctx) it = g_kdc.erase(it); else ++it; }
+void landing_kinodyn_casadi_release(landing_ctx* ctx) {      // drops the context's cache now (landing_destroy drops it too)
+  if (!ctx) return;
+  std::lock_guard<std::mutex> lk(ctx->kdc_mu);
+  ctx->kdc.clear();
 }
 
 int landing_kinodyn_casadi_pattern(landing_ctx* ctx, int N, int which, const long long** colind, const long long** row, long long* nnz) {
@@ -145,13 +144,13 @@ int landing_kinodyn_casadi_eval_host(landing_ctx* ctx, int N, const double* x, c
   if (grad_f) { for (int i = 0; i < nx; ++i) grad_f[i] = 0.0; for (int i = 0; i < 12; ++i) grad_f[12 * N + i] = 2.0 * QN[i] * (x[12 * N + i] - Xref_end[i]); }
   if (!g && !jac && !hess && !ggx && !ggp) return 0;
   HIP_TRY(hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> lk(g_kdc_mu);      // the device buffers of K are used by one call at a time (CasADi calls sequentially from IPOPT's / KNITRO's thread)
-  HIP_TRY(hipMemcpy(K->d_x, x, (size_t)nx * 8, hipMemcpyHostToDevice));
+  std::lock_guard<std::mutex> lk(ctx->kdc_mu);      // the device buffers of K are used by one call at a time (CasADi calls sequentially from IPOPT's / KNITRO's thread)
+  HIP_TRY(hipMemcpy(K->d_x.get(), x, (size_t)nx * 8, hipMemcpyHostToDevice));
   const bool need_j = jac || ggx;
-  { const int rc = landing_kinodyn_nlp_eval(ctx, 1, N, K->d_x, &prm, g ? K->d_g : nullptr, need_j ? K->d_j : nullptr, nullptr); if ((g || need_j) && rc) return rc; }
+  { const int rc = landing_kinodyn_nlp_eval(ctx, 1, N, K->d_x.get(), &prm, g ? K->d_g.get() : nullptr, need_j ? K->d_j.get() : nullptr, nullptr); if ((g || need_j) && rc) return rc; }
   std::vector<double> blk;
-  if (need_j) { blk.resize((size_t)N * NR * NW); HIP_TRY(hipMemcpy(blk.data(), K->d_j, blk.size() * 8, hipMemcpyDeviceToHost)); }
-  if (g) HIP_TRY(hipMemcpy(g, K->d_g, (size_t)ng * 8, hipMemcpyDeviceToHost));
+  if (need_j) { blk.resize((size_t)N * NR * NW); HIP_TRY(hipMemcpy(blk.data(), K->d_j.get(), blk.size() * 8, hipMemcpyDeviceToHost)); }
+  if (g) HIP_TRY(hipMemcpy(g, K->d_g.get(), (size_t)ng * 8, hipMemcpyDeviceToHost));
   if (jac) for (size_t q = 0; q < K->jr.size(); ++q) jac[q] = K->jsrc[q] < 0 ? 1.0 : blk[K->jsrc[q]];
   if (ggx) {      // lam_f grad f + J' lam
     for (int i = 0; i < nx; ++i) ggx[i] = 0.0;
@@ -159,10 +158,10 @@ int landing_kinodyn_casadi_eval_host(landing_ctx* ctx, int N, const double* x, c
     for (int c = 0; c < nx; ++c) { double a = 0.0; for (long long q = K->jc[c]; q < K->jc[c + 1]; ++q) a += (K->jsrc[q] < 0 ? 1.0 : blk[K->jsrc[q]]) * lam_g[K->jr[q]]; ggx[c] += a; }
   }
   if (hess) {
-    HIP_TRY(hipMemcpy(K->d_l, lam_g, (size_t)ng * 8, hipMemcpyHostToDevice));
-    { const int rc = landing_kinodyn_nlp_hess(ctx, 1, N, K->d_x, &prm, K->d_l, K->d_h, nullptr); if (rc) return rc; }
+    HIP_TRY(hipMemcpy(K->d_l.get(), lam_g, (size_t)ng * 8, hipMemcpyHostToDevice));
+    { const int rc = landing_kinodyn_nlp_hess(ctx, 1, N, K->d_x.get(), &prm, K->d_l.get(), K->d_h.get(), nullptr); if (rc) return rc; }
     std::vector<double> hb((size_t)N * NW * NW);
-    HIP_TRY(hipMemcpy(hb.data(), K->d_h, hb.size() * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(hb.data(), K->d_h.get(), hb.size() * 8, hipMemcpyDeviceToHost));
     for (size_t q = 0; q < K->hr.size(); ++q) {
       double v = 0.0;
       for (int n = 0; n < 2; ++n) if (K->hsrc[q][n] >= 0) v += hb[K->hsrc[q][n]];
@@ -184,8 +183,8 @@ int landing_kinodyn_casadi_eval_host(landing_ctx* ctx, int N, const double* x, c
       for (int s = 0; s < 2; ++s) {
         pp[ip] = p[ip] + (s ? -h : h);
         set_prm(pp.data());
-        { const int rc = landing_kinodyn_nlp_eval(ctx, 1, N, K->d_x, &prm, K->d_g, nullptr, nullptr); if (rc) return rc; }
-        HIP_TRY(hipMemcpy((s ? gm : gp).data(), K->d_g, (size_t)ng * 8, hipMemcpyDeviceToHost));
+        { const int rc = landing_kinodyn_nlp_eval(ctx, 1, N, K->d_x.get(), &prm, K->d_g.get(), nullptr, nullptr); if (rc) return rc; }
+        HIP_TRY(hipMemcpy((s ? gm : gp).data(), K->d_g.get(), (size_t)ng * 8, hipMemcpyDeviceToHost));
       }
       pp[ip] = p[ip];
       double a = 0.0;

@@ -352,67 +352,44 @@ int SolverWorkspace::ensure(const Layout& L, int B, hipStream_t stream) {
   if (!done && hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess) return -100;
   if (!d_tab) {
     std::vector<int> data, st, rt, rs, cty;
-    std::vector<unsigned long long> ctb;
-    std::vector<unsigned long long> ccb;
+    std::vector<unsigned long long> ctb, ccb;
     const int rc = build_tables(L, data, st, rt, rs, ctb, ccb, cty, c_ml, c_mid);
     if (rc) return rc;
     n_tab = (int)data.size();
     rlen = rs[0];
-    auto up = [](int** dst, const std::vector<int>& v) {
-      if (hipMalloc((void**)dst, v.size() * sizeof(int)) != hipSuccess) { *dst = nullptr; return -100; }
-      if (hipMemcpy(*dst, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return -101;
+    auto up = [](auto& dst, const auto& v) {
+      if (dst.alloc(v.size()) != hipSuccess) return -100;
+      if (hipMemcpy(dst.get(), v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice) != hipSuccess) return -101;
       return 0;
     };
-    int e = 0;
-    int* tab = nullptr;
-    if (!e) e = up(&d_rterm, rt);
-    if (!e) e = up(&d_stage_tab, st);
-    if (!e) e = up(&d_ctype, cty);
-    if (!e) { std::vector<int> raw(ctb.size() * 2); memcpy(raw.data(), ctb.data(), ctb.size() * 8); e = up(&d_ctab, raw); }
-    if (!e) { std::vector<int> raw(ccb.size() * 2); memcpy(raw.data(), ccb.data(), ccb.size() * 8); e = up(&d_ccomb, raw); }
-    if (!e) e = up(&tab, data);
-    if (e) {   // partial failure: give everything back, the next call starts from scratch
-      if (tab) (void)hipFree(tab);
-      hipEvent_t keep = done; done = nullptr;
-      release();
-      done = keep;
-      return e;
-    }
-    d_tab = tab;   // set last: d_tab != nullptr <=> all tables are resident
+    DevBuf<int> rterm, stage_tab, ctype, tab;      // all filled before any is moved in: a failure leaves the workspace as it was
+    DevBuf<unsigned long long> ctab, ccomb;
+    int e = up(rterm, rt);
+    if (!e) e = up(stage_tab, st);
+    if (!e) e = up(ctype, cty);
+    if (!e) e = up(ctab, ctb);
+    if (!e) e = up(ccomb, ccb);
+    if (!e) e = up(tab, data);
+    if (e) return e;
+    d_rterm = std::move(rterm); d_stage_tab = std::move(stage_tab); d_ctype = std::move(ctype); d_ctab = std::move(ctab); d_ccomb = std::move(ccomb);
+    d_tab = std::move(tab);   // set last: d_tab set <=> all tables are resident
   }
-  const size_t stride = member_stride(L);
-  if ((size_t)B * stride > cap) {
+  const size_t need = (size_t)B * member_stride(L);
+  if (buf.size() < need) {
     // an earlier launch (possibly on another stream) may still be using the old buffer
     if (hipEventSynchronize(done) != hipSuccess) return -102;
-    if (buf) (void)hipFree(buf);
-    buf = nullptr; cap = 0;
-    if (hipMalloc((void**)&buf, (size_t)B * stride * sizeof(double)) != hipSuccess) return -100;
-    cap = (size_t)B * stride;
+    if (buf.grow(need) != hipSuccess) return -100;
   }
-  if (B > order_cap) {
+  if (d_order.size() < (size_t)B) {
     if (hipEventSynchronize(done) != hipSuccess) return -102;
-    if (d_order) (void)hipFree(d_order);
-    d_order = nullptr; order_cap = 0;
-    if (hipMalloc((void**)&d_order, (size_t)B * sizeof(int)) != hipSuccess) return -100;
-    order_cap = B;
+    if (d_order.grow((size_t)B) != hipSuccess) return -100;
   }
   // the previous solve of this context must have finished before this one touches the workspace
   if (hipStreamWaitEvent(stream, done, 0) != hipSuccess) return -102;
   return 0;
 }
-void SolverWorkspace::release() {
-  if (done) { (void)hipEventSynchronize(done); (void)hipEventDestroy(done); }
-  if (buf) (void)hipFree(buf);
-  if (d_order) (void)hipFree(d_order);
-  if (d_tab) (void)hipFree(d_tab);
-  if (d_stage_tab) (void)hipFree(d_stage_tab);
-  if (d_rterm) (void)hipFree(d_rterm);
-  if (d_ctab) (void)hipFree(d_ctab);
-  if (d_ctype) (void)hipFree(d_ctype);
-  if (d_ccomb) (void)hipFree(d_ccomb);
-  d_ctab = d_ctype = d_ccomb = nullptr;
-  buf = nullptr; d_tab = nullptr; d_stage_tab = nullptr; d_rterm = nullptr; cap = 0; done = nullptr;
-  d_order = nullptr; order_cap = 0;
+void SolverWorkspace::release() {      // (the blocks free themselves with the context)
+  if (done) { (void)hipEventSynchronize(done); (void)hipEventDestroy(done); done = nullptr; }
 }
 }  // namespace landing
 
@@ -421,7 +398,7 @@ extern "C" {
 // diagnostic: device pointer and member stride (in doubles) of the solver workspace of the last landing_solve_batch call
 int landing_debug_workspace(landing_ctx* ctx, double** d_ws, unsigned long long* stride) {
   if (!ctx || !d_ws || !stride) return LANDING_E_ARG;
-  *d_ws = ctx->ws.buf; *stride = (unsigned long long)landing::SolverWorkspace::member_stride(ctx->L);
+  *d_ws = ctx->ws.buf.get(); *stride = (unsigned long long)landing::member_stride(ctx->L);
   return 0;
 }
 
@@ -446,17 +423,17 @@ int landing_solve_batch(landing_ctx* ctx, int B, const double* d_p, const double
   if (rc) return fail(rc <= -100 ? LANDING_E_HIP : LANDING_E_ARG, "landing_solve_batch: workspace/table setup failed (" + std::to_string(rc) + ")");
   landing::SolveArgs A;
   A.L = ctx->L; A.B = B; A.o = o; A.p = d_p; A.x0 = d_x0; A.x_out = d_x; A.f_out = d_f; A.lam_out = d_lam_g;
-  A.status = d_status; A.iters = d_iters; A.kkt = d_kkt; A.ws = ctx->ws.buf; A.ws_stride = landing::SolverWorkspace::member_stride(ctx->L);
-  A.ctab = (const unsigned long long*)ctx->ws.d_ctab; A.ctype = ctx->ws.d_ctype; A.c_ml = ctx->ws.c_ml; A.c_mid = ctx->ws.c_mid; A.ccomb = (const unsigned long long*)ctx->ws.d_ccomb;
-  A.rterm = (const unsigned long long*)ctx->ws.d_rterm; A.rlen = ctx->ws.rlen;
+  A.status = d_status; A.iters = d_iters; A.kkt = d_kkt; A.ws = ctx->ws.buf.get(); A.ws_stride = landing::member_stride(ctx->L);
+  A.ctab = ctx->ws.d_ctab.get(); A.ctype = ctx->ws.d_ctype.get(); A.c_ml = ctx->ws.c_ml; A.c_mid = ctx->ws.c_mid; A.ccomb = ctx->ws.d_ccomb.get();
+  A.rterm = (const unsigned long long*)ctx->ws.d_rterm.get(); A.rlen = ctx->ws.rlen;
   A.prof = ctx->d_prof;
-  A.edge_map = ctx->d_edge_map;
+  A.edge_map = ctx->d_edge_map.get();
   A.order = nullptr;
   // hard-first order: pointless while every member is resident from the start (2 workgroups on each of the 256 CUs), and the
   // all-pairs ranking kernel is O(B^2) -- skipped for the huge batches of a data-generation job (ADVICE r2)
   if (o.dispatch_order && B > 512 && B <= 16384) {
-    hipLaunchKernelGGL(landing::landing_order_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, ctx->L, B, d_p, ctx->ws.d_order);
-    A.order = ctx->ws.d_order;
+    hipLaunchKernelGGL(landing::landing_order_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, ctx->L, B, d_p, ctx->ws.d_order.get());
+    A.order = ctx->ws.d_order.get();
   }
   hipLaunchKernelGGL(landing::landing_ipm_kernel, dim3(B), dim3(landing::SOLVER_THREADS), 0, (hipStream_t)stream, A);
   HIP_TRY(hipGetLastError());
@@ -485,21 +462,22 @@ int landing_solve_batch_host(landing_ctx* ctx, int B, const double* p, const dou
     if (!ctx->host_stream) HIP_TRY(hipStreamCreateWithFlags(&ctx->host_stream, hipStreamNonBlocking)); }
   hipStream_t hs = ctx->host_stream;
   const size_t b = (size_t)B;
-  DevBuf dp, dx0, dx, df, dl, dk, dsi;          // dsi: status | iters as two int arrays inside one buffer
+  DevBuf<double> dp, dx0, dx, df, dl, dk;
+  DevBuf<int> dsi;          // status | iters
   HIP_TRY(dp.alloc(b * L.np)); HIP_TRY(dx0.alloc(b * L.nx)); HIP_TRY(dx.alloc(b * L.nx)); HIP_TRY(df.alloc(b));
-  HIP_TRY(dl.alloc(b * L.ng)); HIP_TRY(dk.alloc(b * 3)); HIP_TRY(dsi.alloc(b));
-  int* ds = reinterpret_cast<int*>(dsi.p); int* di = ds + b;
-  HIP_TRY(hipMemcpyAsync(dp.p, p, b * L.np * 8, hipMemcpyHostToDevice, hs));
-  HIP_TRY(hipMemcpyAsync(dx0.p, x0, b * L.nx * 8, hipMemcpyHostToDevice, hs));
-  int rc = landing_solve_batch(ctx, B, dp.p, dx0.p, opts, dx.p, df.p, dl.p, ds, di, dk.p, hs);
+  HIP_TRY(dl.alloc(b * L.ng)); HIP_TRY(dk.alloc(b * 3)); HIP_TRY(dsi.alloc(2 * b));
+  int* ds = dsi.get(); int* di = ds + b;
+  HIP_TRY(hipMemcpyAsync(dp.get(), p, b * L.np * 8, hipMemcpyHostToDevice, hs));
+  HIP_TRY(hipMemcpyAsync(dx0.get(), x0, b * L.nx * 8, hipMemcpyHostToDevice, hs));
+  int rc = landing_solve_batch(ctx, B, dp.get(), dx0.get(), opts, dx.get(), df.get(), dl.get(), ds, di, dk.get(), hs);
   if (rc == 0 && hipStreamSynchronize(hs) != hipSuccess) rc = fail(LANDING_E_HIP, "landing_solve_batch_host: kernel failed");
   if (rc) { (void)hipStreamSynchronize(hs); return rc; }
-  HIP_TRY(hipMemcpyAsync(x, dx.p, b * L.nx * 8, hipMemcpyDeviceToHost, hs));
-  if (f) HIP_TRY(hipMemcpyAsync(f, df.p, b * 8, hipMemcpyDeviceToHost, hs));
-  if (lam_g) HIP_TRY(hipMemcpyAsync(lam_g, dl.p, b * L.ng * 8, hipMemcpyDeviceToHost, hs));
+  HIP_TRY(hipMemcpyAsync(x, dx.get(), b * L.nx * 8, hipMemcpyDeviceToHost, hs));
+  if (f) HIP_TRY(hipMemcpyAsync(f, df.get(), b * 8, hipMemcpyDeviceToHost, hs));
+  if (lam_g) HIP_TRY(hipMemcpyAsync(lam_g, dl.get(), b * L.ng * 8, hipMemcpyDeviceToHost, hs));
   if (status) HIP_TRY(hipMemcpyAsync(status, ds, b * sizeof(int), hipMemcpyDeviceToHost, hs));
   if (iters) HIP_TRY(hipMemcpyAsync(iters, di, b * sizeof(int), hipMemcpyDeviceToHost, hs));
-  if (kkt) HIP_TRY(hipMemcpyAsync(kkt, dk.p, b * 3 * 8, hipMemcpyDeviceToHost, hs));
+  if (kkt) HIP_TRY(hipMemcpyAsync(kkt, dk.get(), b * 3 * 8, hipMemcpyDeviceToHost, hs));
   HIP_TRY(hipStreamSynchronize(hs));
   return 0;
 }
@@ -608,7 +586,7 @@ int landing_riccati_gains_batch(landing_ctx* ctx, int B, int n, const double* d_
   }
   std::lock_guard<std::mutex> lock(ctx->mu);
   constexpr size_t VBL_N = 576 + 576 + 12;
-  if (!ctx->d_vbl) HIP_TRY(hipMalloc((void**)&ctx->d_vbl, VBL_N * sizeof(double)));
+  if (!ctx->d_vbl) HIP_TRY(ctx->d_vbl.alloc(VBL_N));
   // The weights travel through a PINNED staging block owned by the context, so the upload is a true asynchronous copy and the call returns
   // without blocking the caller's stream (VERDICT r3 item 11: a stack buffer forced a hipStreamSynchronize here).  The block is re-written
   // by the next call only after the copy that read it has completed: `vbl_copied` is recorded behind the copy and waited for on the HOST
@@ -622,9 +600,9 @@ int landing_riccati_gains_batch(landing_ctx* ctx, int B, int n, const double* d_
   for (int i = 0; i < 576; ++i) { host[i] = Q[i]; host[576 + i] = F ? F[i] : 0.0; }
   for (int i = 0; i < 12; ++i) host[1152 + i] = 1.0 / r_diag[i];
   HIP_TRY(scratch_acquire(ctx, (hipStream_t)stream));      // the previous call's kernel (any stream) still reads Q / F / 1/R from the device block
-  HIP_TRY(hipMemcpyAsync(ctx->d_vbl, host, VBL_N * sizeof(double), hipMemcpyHostToDevice, (hipStream_t)stream));
+  HIP_TRY(hipMemcpyAsync(ctx->d_vbl.get(), host, VBL_N * sizeof(double), hipMemcpyHostToDevice, (hipStream_t)stream));
   HIP_TRY(hipEventRecord(ctx->vbl_copied, (hipStream_t)stream));
-  a.Q = ctx->d_vbl; a.F = ctx->d_vbl + 576; a.rinv = ctx->d_vbl + 1152;
+  a.Q = ctx->d_vbl.get(); a.F = a.Q + 576; a.rinv = a.Q + 1152;
   hipLaunchKernelGGL(landing::landing_rde_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
   HIP_TRY(scratch_release(ctx, (hipStream_t)stream));
@@ -652,13 +630,13 @@ int landing_rbd_set_model(landing_ctx* ctx, const landing_rbd_model* model) {
   for (int l = 0; l < 4; ++l) if (model->b_foot[l] < 3 || model->b_foot[l] > 18) return fail(LANDING_E_ARG, "landing_rbd_set_model: foot bodies are the third link of a leg chain");
   HIP_TRY(hipSetDevice(ctx->device));
   std::lock_guard<std::mutex> lock(ctx->mu);
-  if (!ctx->d_rbd) HIP_TRY(hipMalloc((void**)&ctx->d_rbd, sizeof(landing::RbdModel)));
-  HIP_TRY(hipMemcpy(ctx->d_rbd, model, sizeof(landing::RbdModel), hipMemcpyHostToDevice));
+  if (!ctx->d_rbd) HIP_TRY(ctx->d_rbd.alloc(1));
+  HIP_TRY(hipMemcpy(ctx->d_rbd.get(), model, sizeof(landing::RbdModel), hipMemcpyHostToDevice));
   if (ctx->d_kd_pairs) {      // the Hessian pair table of the kinodynamic NLP was probed with the previous model (kd_ensure_pairs): built again at the next use
     HIP_TRY(hipDeviceSynchronize());      // (a launch of an earlier call may still read it)
-    (void)hipFree(ctx->d_kd_pairs); ctx->d_kd_pairs = nullptr; ctx->kd_npair = 0;
+    ctx->d_kd_pairs.reset(); ctx->kd_npair = 0;
   }
-  if (ctx->d_kd_jpat) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(ctx->d_kd_jpat); ctx->d_kd_jpat = nullptr; }      // (kd_ensure_jpat: the same)
+  if (ctx->d_kd_jpat) { HIP_TRY(hipDeviceSynchronize()); ctx->d_kd_jpat.reset(); }      // (kd_ensure_jpat: the same)
   { bool arrow = true;       // parent = [0 1 2 3 4 5 | 6 7 8 | 6 10 11 | 6 13 14 | 6 16 17]
     for (int i = 0; i < 6; ++i) arrow = arrow && model->parent[i] == i;
     for (int l = 0; l < 4; ++l) arrow = arrow && model->parent[6 + 3 * l] == 6 && model->parent[7 + 3 * l] == 7 + 3 * l && model->parent[8 + 3 * l] == 8 + 3 * l;
@@ -681,7 +659,7 @@ int landing_fb_dynamics_batch(landing_ctx* ctx, int npts, const double* d_q, con
   if (!ctx->d_rbd) return fail(LANDING_E_ARG, "landing_fb_dynamics_batch: no model (landing_rbd_set_model)");
   if ((d_qdd || d_A) && !d_tau) return fail(LANDING_E_ARG, "landing_fb_dynamics_batch: qdd / A need tau");
   HIP_TRY(hipSetDevice(ctx->device));
-  landing::FbArgs a{ctx->d_rbd, npts, d_q, d_qd, d_tau, d_f_foot, d_H, d_C, d_qdd, d_A, d_Hinv, fd_h > 0.0 ? fd_h : 1e-6, ctx->rbd_arrow ? 1 : 0};
+  landing::FbArgs a{ctx->d_rbd.get(), npts, d_q, d_qd, d_tau, d_f_foot, d_H, d_C, d_qdd, d_A, d_Hinv, fd_h > 0.0 ? fd_h : 1e-6, ctx->rbd_arrow ? 1 : 0};
   if (d_H || d_C || (d_qdd && !(d_A && fd_h <= 0.0))) hipLaunchKernelGGL(landing::landing_fb_hc_kernel, dim3((npts + 63) / 64), dim3(64), 0, (hipStream_t)stream, a);
   if (d_A && fd_h <= 0.0) {
     // exact linearisation (forward mode): pass 1 leaves qdd and H^-1 per knot in the caller's buffers or in a context scratch
@@ -689,17 +667,11 @@ int landing_fb_dynamics_batch(landing_ctx* ctx, int npts, const double* d_q, con
     double* qs = d_qdd; double* hs = d_Hinv;
     std::lock_guard<std::mutex> lock(ctx->mu);      // the scratch belongs to the context (host threads sharing it are serialised here)
     if (!qs || !hs) {
-      const size_t need = (size_t)npts * (18 + 324);
-      if (ctx->fb_scratch_n < need) {
-        if (ctx->d_fb_scratch) HIP_TRY(hipFree(ctx->d_fb_scratch));      // hipFree waits for the device: no launch still reads the old block
-        ctx->d_fb_scratch = nullptr; ctx->fb_scratch_n = 0;
-        HIP_TRY(hipMalloc((void**)&ctx->d_fb_scratch, need * sizeof(double)));
-        ctx->fb_scratch_n = need;
-      }
-      if (!qs) qs = ctx->d_fb_scratch;
-      if (!hs) hs = ctx->d_fb_scratch + (size_t)npts * 18;
+      HIP_TRY(ctx->d_fb_scratch.grow((size_t)npts * (18 + 324)));      // hipFree waits for the device: no launch still reads the old block
+      if (!qs) qs = ctx->d_fb_scratch.get();
+      if (!hs) hs = ctx->d_fb_scratch.get() + (size_t)npts * 18;
     }
-    const bool own = (qs == ctx->d_fb_scratch) || (hs == ctx->d_fb_scratch + (size_t)npts * 18);
+    const bool own = (qs == ctx->d_fb_scratch.get()) || (hs == ctx->d_fb_scratch.get() + (size_t)npts * 18);
     if (own) HIP_TRY(scratch_acquire(ctx, (hipStream_t)stream));
     hipLaunchKernelGGL(landing::landing_fb_lin_exact_prep_kernel, dim3((npts + 63) / 64), dim3(64), 0, (hipStream_t)stream, a, qs, hs);
     const long long n = 36LL * npts;
@@ -720,7 +692,7 @@ int landing_leg_ik_batch(landing_ctx* ctx, int npts, const double* d_q6, const d
   if (!ctx || npts < 0 || !d_q6 || !d_c || !d_jpos || !jpos_min3 || !jpos_max3 || iters < 1) return fail(LANDING_E_ARG, "landing_leg_ik_batch: bad argument");
   if (!ctx->d_rbd) return fail(LANDING_E_ARG, "landing_leg_ik_batch: no model (landing_rbd_set_model)");
   HIP_TRY(hipSetDevice(ctx->device));
-  landing::IkArgs a{ctx->d_rbd, npts, d_q6, d_c, d_jpos, d_res, iters, {jpos_min3[0], jpos_min3[1], jpos_min3[2]}, {jpos_max3[0], jpos_max3[1], jpos_max3[2]}};
+  landing::IkArgs a{ctx->d_rbd.get(), npts, d_q6, d_c, d_jpos, d_res, iters, {jpos_min3[0], jpos_min3[1], jpos_min3[2]}, {jpos_max3[0], jpos_max3[1], jpos_max3[2]}};
   const long long n = 4LL * npts;
   hipLaunchKernelGGL(landing::landing_leg_ik_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
@@ -733,7 +705,7 @@ int landing_kinodyn_rows_batch(landing_ctx* ctx, int npts, const double* d_q6, c
   if (!ctx || npts < 0 || !d_q6 || !d_jpos || (d_fk_err && !d_c) || (d_tau && !d_f)) return fail(LANDING_E_ARG, "landing_kinodyn_rows_batch: bad argument");
   if (!ctx->d_rbd) return fail(LANDING_E_ARG, "landing_kinodyn_rows_batch: no model (landing_rbd_set_model)");
   HIP_TRY(hipSetDevice(ctx->device));
-  landing::KdArgs a{ctx->d_rbd, npts, d_q6, d_c, d_f, d_jpos, d_fk, d_fk_err, d_tau};
+  landing::KdArgs a{ctx->d_rbd.get(), npts, d_q6, d_c, d_f, d_jpos, d_fk, d_fk_err, d_tau};
   hipLaunchKernelGGL(landing::landing_kinodyn_rows_kernel, dim3((npts + 63) / 64), dim3(64), 0, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -783,7 +755,7 @@ int landing_kinodyn_nlp_eval(landing_ctx* ctx, int B, int N, const double* d_x, 
   HIP_TRY(hipSetDevice(ctx->device));
   landing::KdNlpArgs a;
   a.sx = a.sg = a.sj = a.sh = 0; a.skip = nullptr;
-  a.model = ctx->d_rbd; a.B = B; a.N = N; a.x = d_x; a.g = d_g; a.jac = d_jac; a.lam = nullptr; a.hess = nullptr;
+  a.model = ctx->d_rbd.get(); a.B = B; a.N = N; a.x = d_x; a.g = d_g; a.jac = d_jac; a.lam = nullptr; a.hess = nullptr;
   for (int k = 0; k < 64; ++k) a.P.dt[k] = k < N ? prm->dt[k] : 0.0;
   a.P.mass = prm->mass; a.P.mu = prm->mu; a.P.std_base = ctx->rbd_std_base;
   for (int i = 0; i < 3; ++i) { a.P.Ib[i] = prm->Ib[i]; a.P.Ibi[i] = prm->Ib_inv[i]; }
@@ -818,25 +790,23 @@ static int kd_ensure_pairs(landing_ctx* ctx, const landing::KdNlpParams& P) {
   auto rnd = [&]() { sdd = sdd * 6364136223846793005ull + 1442695040888963407ull; return (double)((sdd >> 11) & 0xFFFFFFFFFFFFFull) / 4503599627370496.0; };      // [0, 1)
   for (auto& v : hx) v = rnd() - 0.5;
   for (auto& v : hl) v = (0.5 + rnd()) * (rnd() < 0.5 ? -1.0 : 1.0);
-  unsigned char* d_full = nullptr; double *d_x = nullptr, *d_l = nullptr, *d_h = nullptr;
-  auto cleanup = [&]() { for (void* q : {(void*)d_full, (void*)d_x, (void*)d_l, (void*)d_h}) if (q) (void)hipFree(q); };
-#define KP_TRY(e) do { hipError_t e_ = (e); if (e_ != hipSuccess) { cleanup(); return fail(LANDING_E_HIP, std::string(#e) + ": " + hipGetErrorString(e_)); } } while (0)
-  KP_TRY(hipMalloc((void**)&d_full, sizeof(host))); KP_TRY(hipMemcpy(d_full, host, sizeof(host), hipMemcpyHostToDevice));
-  KP_TRY(hipMalloc((void**)&d_x, hx.size() * sizeof(double))); KP_TRY(hipMemcpy(d_x, hx.data(), hx.size() * sizeof(double), hipMemcpyHostToDevice));
-  KP_TRY(hipMalloc((void**)&d_l, hl.size() * sizeof(double))); KP_TRY(hipMemcpy(d_l, hl.data(), hl.size() * sizeof(double), hipMemcpyHostToDevice));
-  KP_TRY(hipMalloc((void**)&d_h, nh * sizeof(double))); KP_TRY(hipMemset(d_h, 0, nh * sizeof(double)));
+  DevBuf<unsigned char> d_full; DevBuf<double> d_x, d_l, d_h;
+  HIP_TRY(d_full.alloc(sizeof(host))); HIP_TRY(hipMemcpy(d_full.get(), host, sizeof(host), hipMemcpyHostToDevice));
+  HIP_TRY(d_x.alloc(hx.size())); HIP_TRY(hipMemcpy(d_x.get(), hx.data(), hx.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(d_l.alloc(hl.size())); HIP_TRY(hipMemcpy(d_l.get(), hl.data(), hl.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(d_h.alloc(nh)); HIP_TRY(hipMemset(d_h.get(), 0, nh * sizeof(double)));
   landing::KdNlpArgs a;
   a.sx = a.sg = a.sj = a.sh = 0; a.skip = nullptr;
-  a.model = ctx->d_rbd; a.B = B; a.N = N; a.x = d_x; a.g = nullptr; a.jac = nullptr; a.lam = d_l; a.hess = d_h; a.P = P;
+  a.model = ctx->d_rbd.get(); a.B = B; a.N = N; a.x = d_x.get(); a.g = nullptr; a.jac = nullptr; a.lam = d_l.get(); a.hess = d_h.get(); a.P = P;
   // The structure must not depend on the caller's parameter VALUES (ADVICE r5: with Ib = (0.03, 0.03, 0.03) the omega-omega entries of omega x I omega vanish and a later
   // call with the real inertia got 36 wrong zeros): the probe runs with fixed generic constants -- distinct inertias, mu > 0, unit mass, a uniform grid -- so that only the model
   // (landing_rbd_set_model invalidates the table) and the formulation decide which pairs are kept.
   for (int k = 0; k < 64; ++k) a.P.dt[k] = k < N ? 0.03 : 0.0;
   a.P.mass = 1.0; a.P.mu = 0.7; a.P.Ib[0] = 0.05; a.P.Ib[1] = 0.2; a.P.Ib[2] = 0.3; a.P.Ibi[0] = 17.0; a.P.Ibi[1] = 4.3; a.P.Ibi[2] = 3.6;
   const long long n = (long long)B * N * NP;
-  kd_launch_hess(ctx, a, B, N, (const unsigned char*)d_full, (const unsigned char*)d_full + NP, NP, (hipStream_t)nullptr);
-  KP_TRY(hipGetLastError());
-  KP_TRY(hipMemcpy(hh.data(), d_h, nh * sizeof(double), hipMemcpyDeviceToHost));
+  kd_launch_hess(ctx, a, B, N, d_full.get(), d_full.get() + NP, NP, (hipStream_t)nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(hh.data(), d_h.get(), nh * sizeof(double), hipMemcpyDeviceToHost));
   unsigned char keep[2 * landing::KD_NPAIR]; int nk = 0;
   for (int q = 0; q < NP; ++q) {
     const int i = host[q], j = host[NP + q];
@@ -844,7 +814,7 @@ static int kd_ensure_pairs(landing_ctx* ctx, const landing::KdNlpParams& P) {
     for (int b = 0; b < B && !nz; ++b) for (int k = 0; k < N && !nz; ++k) { const double v = hh[(((size_t)b * N + k) * NW + i) * NW + j]; nz = v != 0.0 || v != v; }
     if (nz) { keep[nk] = (unsigned char)i; keep[NP + nk] = (unsigned char)j; ++nk; }
   }
-  if (nk < 1) { cleanup(); return fail(LANDING_E_ARG, "kinodynamic NLP: empty pair table"); }
+  if (nk < 1) return fail(LANDING_E_ARG, "kinodynamic NLP: empty pair table");
   // Wavefront-pure order: a lane's pair decides which legs' kinematic rows it evaluates (kd_stage_rows' legmask: all four for a pair inside the base, one for a pair
   // that involves a leg), and a wavefront runs the rows of every leg any of its lanes needs.  The pairs of the base fill their own wavefront(s), then leg by leg,
   // each class padded to a multiple of 64 with empty entries (255: the lane leaves at once).
@@ -858,12 +828,10 @@ static int kd_ensure_pairs(landing_ctx* ctx, const landing::KdNlpParams& P) {
     for (int q = 0; q < np_; ++q) { packed[q] = oi[q]; packed[np_ + q] = oj[q]; }
   }
   nk = np_;
-  unsigned char* d_pairs = nullptr;
-  KP_TRY(hipMalloc((void**)&d_pairs, (size_t)2 * nk));
-  { hipError_t e_ = hipMemcpy(d_pairs, packed, (size_t)2 * nk, hipMemcpyHostToDevice); if (e_ != hipSuccess) { (void)hipFree(d_pairs); cleanup(); return fail(LANDING_E_HIP, "hipMemcpy (pair table)"); } }
-#undef KP_TRY
-  cleanup();
-  ctx->d_kd_pairs = d_pairs; ctx->kd_npair = nk;
+  DevBuf<unsigned char> d_pairs;
+  HIP_TRY(d_pairs.alloc((size_t)2 * nk));
+  HIP_TRY(hipMemcpy(d_pairs.get(), packed, (size_t)2 * nk, hipMemcpyHostToDevice));
+  ctx->d_kd_pairs = std::move(d_pairs); ctx->kd_npair = nk;
   return 0;
 }
 
@@ -880,22 +848,20 @@ static int kd_ensure_jpat(landing_ctx* ctx) {
   unsigned long long sdd = 0x2545F4914F6CDD1Dull;
   auto rnd = [&]() { sdd = sdd * 6364136223846793005ull + 1442695040888963407ull; return (double)((sdd >> 11) & 0xFFFFFFFFFFFFFull) / 4503599627370496.0; };      // [0, 1)
   for (auto& v : hx) v = rnd() - 0.4;
-  double *d_x = nullptr, *d_j = nullptr;
-  auto cleanup = [&]() { if (d_x) (void)hipFree(d_x); if (d_j) (void)hipFree(d_j); };
-#define KJ_TRY(e) do { hipError_t e_ = (e); if (e_ != hipSuccess) { cleanup(); return fail(LANDING_E_HIP, std::string(#e) + ": " + hipGetErrorString(e_)); } } while (0)
-  KJ_TRY(hipMalloc((void**)&d_x, hx.size() * sizeof(double))); KJ_TRY(hipMemcpy(d_x, hx.data(), hx.size() * sizeof(double), hipMemcpyHostToDevice));
-  KJ_TRY(hipMalloc((void**)&d_j, nj * sizeof(double))); KJ_TRY(hipMemset(d_j, 0, nj * sizeof(double)));
+  DevBuf<double> d_x, d_j;
+  HIP_TRY(d_x.alloc(hx.size())); HIP_TRY(hipMemcpy(d_x.get(), hx.data(), hx.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(d_j.alloc(nj)); HIP_TRY(hipMemset(d_j.get(), 0, nj * sizeof(double)));
   landing::KdNlpArgs a;
   a.sx = a.sg = a.sj = a.sh = 0; a.skip = nullptr;
-  a.model = ctx->d_rbd; a.B = B; a.N = N; a.x = d_x; a.g = nullptr; a.jac = d_j; a.lam = nullptr; a.hess = nullptr;
+  a.model = ctx->d_rbd.get(); a.B = B; a.N = N; a.x = d_x.get(); a.g = nullptr; a.jac = d_j.get(); a.lam = nullptr; a.hess = nullptr;
   for (int k = 0; k < 64; ++k) a.P.dt[k] = k < N ? 0.03 : 0.0;
   a.P.mass = 1.0; a.P.mu = 0.7; a.P.Ib[0] = 0.05; a.P.Ib[1] = 0.2; a.P.Ib[2] = 0.3; a.P.Ibi[0] = 17.0; a.P.Ibi[1] = 4.3; a.P.Ibi[2] = 3.6; a.P.std_base = ctx->rbd_std_base;
   kd_launch_jac(ctx, a, B, N, (hipStream_t)nullptr);
-  KJ_TRY(hipGetLastError());
-  KJ_TRY(hipMemcpy(hj.data(), d_j, nj * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(hj.data(), d_j.get(), nj * sizeof(double), hipMemcpyDeviceToHost));
   auto nz = [&](int k, int r, int c) { for (int b = 0; b < B; ++b) { const double v = hj[(((size_t)b * N + k) * NR + r) * NW + c]; if (v != 0.0 || v != v) return true; } return false; };
   for (int r = 12; r < NR; ++r) for (int c = 0; c < NW; ++c)
-    if (nz(0, r, c) != nz(1, r, c) || nz(1, r, c) != nz(2, r, c)) { cleanup(); return fail(LANDING_E_ARG, "kinodynamic NLP: the Jacobian blocks of two middle intervals differ in structure"); }
+    if (nz(0, r, c) != nz(1, r, c) || nz(1, r, c) != nz(2, r, c)) return fail(LANDING_E_ARG, "kinodynamic NLP: the Jacobian blocks of two middle intervals differ in structure");
   std::vector<landing::KdJPat> T(1);
   memset(T.data(), 0, sizeof(landing::KdJPat));
   std::vector<landing::KdCPat> Cp(1);
@@ -910,7 +876,7 @@ static int kd_ensure_jpat(landing_ctx* ctx) {
     int n = 0;
     for (int j = 0; j < nrow; ++j) {
       const std::vector<int>& cj = cols[order[j]];
-      if ((int)cj.size() > landing::KD_JP_MAX || n + (int)cj.size() > landing::KD_JP_NNZ - landing::KD_JP_MAX) { cleanup(); return fail(LANDING_E_ARG, "kinodynamic NLP: Jacobian block denser than the table of its non-zeros"); }
+      if ((int)cj.size() > landing::KD_JP_MAX || n + (int)cj.size() > landing::KD_JP_NNZ - landing::KD_JP_MAX) return fail(LANDING_E_ARG, "kinodynamic NLP: Jacobian block denser than the table of its non-zeros");
       T[0].perm[lp][j] = (unsigned char)(12 + order[j]); T[0].rp[lp][j] = (unsigned short)n;
       for (int c : cj) T[0].cl[lp][n++] = (unsigned char)c;
     }
@@ -923,7 +889,7 @@ static int kd_ensure_jpat(landing_ctx* ctx) {
       for (int j = 0; j < nrow; ++j) for (int t = T[0].rp[lp][j]; t < T[0].rp[lp][j + 1]; ++t) colv[T[0].cl[lp][t]].push_back(((unsigned)T[0].perm[lp][j] << 16) | (unsigned)(landing::KD_JC_DEF + t));
       for (int c = 0; c < NW; ++c) {
         std::sort(colv[c].begin(), colv[c].end());      // (by row: the kernel emits the rows of a column in rising order)
-        if ((int)colv[c].size() >= landing::KD_JCOL) { cleanup(); return fail(LANDING_E_ARG, "kinodynamic NLP: a column of the Jacobian block has more entries than its list holds"); }
+        if ((int)colv[c].size() >= landing::KD_JCOL) return fail(LANDING_E_ARG, "kinodynamic NLP: a column of the Jacobian block has more entries than its list holds");
         for (size_t i = 0; i < colv[c].size(); ++i) Cp[0].jcol[lp][c][i] = colv[c][i];
         for (int i = (int)colv[c].size(); i < landing::KD_JCOL; ++i) Cp[0].jcol[lp][c][i] = 0xffff0000u;
       }
@@ -937,7 +903,7 @@ static int kd_ensure_jpat(landing_ctx* ctx) {
       for (int ta = T[0].rp[lp][j]; ta < T[0].rp[lp][j + 1]; ++ta) {
         Cp[0].erow[lp][ta] = (unsigned char)j;
         const int va = vof(T[0].cl[lp][ta]);
-        if (va < 0 || va >= nv) { cleanup(); return fail(LANDING_E_ARG, "kinodynamic NLP: an inequality row depends on a variable outside its stage"); }
+        if (va < 0 || va >= nv) return fail(LANDING_E_ARG, "kinodynamic NLP: an inequality row depends on a variable outside its stage");
         rhs[va].push_back((unsigned)ta | ((unsigned)j << 10));
         for (int tb = T[0].rp[lp][j]; tb < T[0].rp[lp][j + 1]; ++tb) {
           const int vb = vof(T[0].cl[lp][tb]);
@@ -948,7 +914,7 @@ static int kd_ensure_jpat(landing_ctx* ctx) {
     std::stable_sort(dl.begin(), dl.end(), [](const auto& p, const auto& q) { return p.second.size() > q.second.size(); });      // lanes of a wavefront: destinations of similar length
     int nd = 0, nt = 0;
     for (const auto& e : dl) {
-      if (nd >= landing::KD_CP_ND || nt + (int)e.second.size() > landing::KD_CP_NT) { cleanup(); return fail(LANDING_E_ARG, "kinodynamic NLP: condensation table too small"); }
+      if (nd >= landing::KD_CP_ND || nt + (int)e.second.size() > landing::KD_CP_NT) return fail(LANDING_E_ARG, "kinodynamic NLP: condensation table too small");
       Cp[0].drp[lp][nd] = (unsigned short)nt; Cp[0].dab[lp][nd] = (unsigned short)(e.first.first | (e.first.second << 8));
       for (unsigned w : e.second) Cp[0].dterm[lp][nt++] = w;
       ++nd;
@@ -958,16 +924,13 @@ static int kd_ensure_jpat(landing_ctx* ctx) {
     for (int v = 0; v < landing::KD_NV; ++v) { Cp[0].rrp[lp][v] = (unsigned short)nr; for (unsigned w : rhs[v]) Cp[0].rterm[lp][nr++] = w; }
     Cp[0].rrp[lp][landing::KD_NV] = (unsigned short)nr;
   }
-  void* d_t = nullptr;      // [KdJPat | KdCPat]
+  DevBuf<unsigned char> d_t;      // [KdJPat | KdCPat]
   constexpr size_t JP8 = (sizeof(landing::KdJPat) + 15) / 16 * 16;
-  KJ_TRY(hipMalloc(&d_t, JP8 + sizeof(landing::KdCPat)));
-  { hipError_t e_ = hipMemcpy(d_t, T.data(), sizeof(landing::KdJPat), hipMemcpyHostToDevice);
-    if (e_ == hipSuccess) e_ = hipMemcpy((char*)d_t + JP8, Cp.data(), sizeof(landing::KdCPat), hipMemcpyHostToDevice);
-    if (e_ != hipSuccess) { (void)hipFree(d_t); cleanup(); return fail(LANDING_E_HIP, "hipMemcpy (Jacobian non-zero tables)"); } }
+  HIP_TRY(d_t.alloc(JP8 + sizeof(landing::KdCPat)));
+  HIP_TRY(hipMemcpy(d_t.get(), T.data(), sizeof(landing::KdJPat), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_t.get() + JP8, Cp.data(), sizeof(landing::KdCPat), hipMemcpyHostToDevice));
   ctx->kd_cpat_off = JP8;
-#undef KJ_TRY
-  cleanup();
-  ctx->d_kd_jpat = d_t;
+  ctx->d_kd_jpat = std::move(d_t);
   return 0;
 }
 
@@ -978,7 +941,7 @@ int landing_kinodyn_nlp_hess(landing_ctx* ctx, int B, int N, const double* d_x, 
   HIP_TRY(hipSetDevice(ctx->device));
   landing::KdNlpArgs a;
   a.sx = a.sg = a.sj = a.sh = 0; a.skip = nullptr;
-  a.model = ctx->d_rbd; a.B = B; a.N = N; a.x = d_x; a.g = nullptr; a.jac = nullptr; a.lam = d_lam_g; a.hess = d_hess;
+  a.model = ctx->d_rbd.get(); a.B = B; a.N = N; a.x = d_x; a.g = nullptr; a.jac = nullptr; a.lam = d_lam_g; a.hess = d_hess;
   for (int k = 0; k < 64; ++k) a.P.dt[k] = k < N ? prm->dt[k] : 0.0;
   a.P.mass = prm->mass; a.P.mu = prm->mu; a.P.std_base = ctx->rbd_std_base;
   for (int i = 0; i < 3; ++i) { a.P.Ib[i] = prm->Ib[i]; a.P.Ibi[i] = prm->Ib_inv[i]; }
@@ -987,7 +950,7 @@ int landing_kinodyn_nlp_hess(landing_ctx* ctx, int B, int N, const double* d_x, 
   const long long n = (long long)B * N * ctx->kd_npair;
   if (n > 0x7fffffffLL * 64) return fail(LANDING_E_ARG, "landing_kinodyn_nlp_hess: batch too large for one launch");
   HIP_TRY(hipMemsetAsync(d_hess, 0, (size_t)B * N * landing::KD_NW * landing::KD_NW * sizeof(double), (hipStream_t)stream));
-  kd_launch_hess(ctx, a, B, N, (const unsigned char*)ctx->d_kd_pairs, (const unsigned char*)ctx->d_kd_pairs + ctx->kd_npair, ctx->kd_npair, (hipStream_t)stream);
+  kd_launch_hess(ctx, a, B, N, ctx->d_kd_pairs.get(), ctx->d_kd_pairs.get() + ctx->kd_npair, ctx->kd_npair, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -1026,7 +989,7 @@ int landing_wb_rollout(landing_ctx* ctx, int B, int N, int nalpha, const double*
   if (!ctx->d_rbd) return fail(LANDING_E_ARG, "landing_wb_rollout: no model (landing_rbd_set_model)");
   HIP_TRY(hipSetDevice(ctx->device));
   landing::WbRollArgs a;
-  a.model = ctx->d_rbd; a.B = B; a.N = N; a.nalpha = nalpha; a.dt = dt; a.semi = ctx->wb_semi; a.alphas = d_alphas; a.x = d_x; a.u = d_u; a.xref = d_xref; a.f_foot = d_f_foot;
+  a.model = ctx->d_rbd.get(); a.B = B; a.N = N; a.nalpha = nalpha; a.dt = dt; a.semi = ctx->wb_semi; a.alphas = d_alphas; a.x = d_x; a.u = d_u; a.xref = d_xref; a.f_foot = d_f_foot;
   a.K = d_K; a.kff = d_kff; a.skip = ctx->wb_skip; ctx->wb_skip = nullptr;
   a.arrow = ctx->rbd_arrow ? 1 : 0;
   for (int i = 0; i < 36; ++i) { a.Q[i] = Q36[i]; a.QN[i] = QN36[i]; }

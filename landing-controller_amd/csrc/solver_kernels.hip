@@ -65,19 +65,10 @@ constexpr int CX_SR = NZ_TOT + 48, CX_ONE = CX_SR + 208, CX_MONE = CX_ONE + 1, C
 constexpr int ATAB_TB = 6, ATAB_LTMAX = 6;       // terms per batch; longest per-thread list (a multiple of ATAB_TB): the 1 138..1 234 terms of a stage give 5 per thread
 constexpr int ASM_NSLOT = 512;                   // partial-sum slots of one stage
 
-struct SolverWorkspace {
-  double* buf = nullptr; size_t cap = 0;
-  int* d_order = nullptr; int order_cap = 0;
-  hipEvent_t done = nullptr;     // recorded behind every solve launch: the next launch (any stream) and any re-allocation wait for it
-  int* d_tab = nullptr; int* d_stage_tab = nullptr; int n_tab = 0;
-  int* d_rterm = nullptr; int rlen = 0;
-  int *d_ctab = nullptr, *d_ctype = nullptr, *d_ccomb = nullptr; int c_ml = 0, c_mid = 0;     // packed per-stage-type assembly tables (aterm_pack): [type][c_ml][256], most frequent type
-  static size_t member_stride(const Layout& L) {
-    return (size_t)4 * L.nx + (size_t)14 * L.ng + L.nnz_jac + L.nnz_hess + (size_t)L.N * RUNC + (size_t)(L.N + 1) * RIC_STRIDE + (size_t)L.N * RCG;
-  }
-  int ensure(const Layout& L, int B, hipStream_t stream);
-  void release();
-};
+// doubles of one member's block of the solver workspace (landing::SolverWorkspace, capi.hip)
+inline size_t member_stride(const Layout& L) {
+  return (size_t)4 * L.nx + (size_t)14 * L.ng + L.nnz_jac + L.nnz_hess + (size_t)L.N * RUNC + (size_t)(L.N + 1) * RIC_STRIDE + (size_t)L.N * RCG;
+}
 
 // optional per-member phase timers (wall_clock64 ticks, 100 MHz) -- enabled when SolveArgs.prof != nullptr
 enum { PH_EVAL = 0, PH_ERR, PH_SIGRHO, PH_BACK, PH_FWD, PH_DUAL, PH_LS, PH_ACCEPT, PH_NFACT, PH_NTRIAL, PH_NITER, PH_NSTAGE_OK, PH_B_ASM, PH_NSTAGE, PH_B_ELIM, PH_B_POST,

@@ -93,8 +93,10 @@ void landing_stream_destroy(landing_stream* s) {
   delete s;
 }
 
-// Host arrays, any number of members: the batch is cut into chunks of `chunk` members (0 = 1024) that go through a stream of `lanes` lanes with the
-// copies of chunk i + 1 (pinned staging, H2D) and of chunk i - 1 (D2H) under the solve of chunk i.  Same results as landing_solve_batch_host.
+// Host arrays, any number of members: the batch is cut into chunks of `chunk` members (0 = 1024) that go through a stream of `lanes` lanes.  Every
+// lane slot has device buffers for one chunk and a copy stream of its own: the upload of chunk i + 1 and the download of chunk i - 1 are queued there
+// while chunk i solves.  The copies go straight to and from the caller's pageable host arrays (no pinned staging), so they overlap the solves only as
+// far as the runtime's own staging of pageable memory lets them.  Same results as landing_solve_batch_host.
 int landing_solve_stream_host(landing_ctx* ctx, int B, int chunk, int lanes, const double* p, const double* x0, const landing_solver_opts* opts,
                               double* x, double* f, double* lam_g, int* status, int* iters, double* kkt) {
   if (!ctx || B < 0 || (B > 0 && (!p || !x0 || !x))) return fail(LANDING_E_ARG, "landing_solve_stream_host: bad argument");
@@ -108,15 +110,15 @@ int landing_solve_stream_host(landing_ctx* ctx, int B, int chunk, int lanes, con
   landing_stream* s = ctx->hs_obj;      // kept by the context: the child contexts of the lanes and their workspaces are built once
   if (!s) return LANDING_E_HIP;
   const int K = (int)s->lane.size();
-  struct Slot { DevBuf p, x0, x, f, l, k, si; hipStream_t cp = nullptr; hipEvent_t up = nullptr; };
+  struct Slot { DevBuf<double> p, x0, x, f, l, k; DevBuf<int> si; hipStream_t cp = nullptr; };      // si: status | iters
   std::vector<Slot> slot(K);
   int rc = 0;
   auto bail = [&](int code, const char* what) { rc = fail(code, what); };
   for (int i = 0; i < K && !rc; ++i) {
     Slot& q = slot[i]; const size_t c = (size_t)chunk;
     if (q.p.alloc(c * L.np) != hipSuccess || q.x0.alloc(c * L.nx) != hipSuccess || q.x.alloc(c * L.nx) != hipSuccess || q.f.alloc(c) != hipSuccess ||
-        q.l.alloc(c * L.ng) != hipSuccess || q.k.alloc(c * 3) != hipSuccess || q.si.alloc(c) != hipSuccess ||
-        hipStreamCreateWithFlags(&q.cp, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&q.up, hipEventDisableTiming) != hipSuccess)
+        q.l.alloc(c * L.ng) != hipSuccess || q.k.alloc(c * 3) != hipSuccess || q.si.alloc(2 * c) != hipSuccess ||
+        hipStreamCreateWithFlags(&q.cp, hipStreamNonBlocking) != hipSuccess)
       bail(LANDING_E_HIP, "landing_solve_stream_host: allocation failed");
   }
   const int nchunk = (B + chunk - 1) / chunk;
@@ -124,29 +126,29 @@ int landing_solve_stream_host(landing_ctx* ctx, int B, int chunk, int lanes, con
   auto download = [&](int ci) {      // D2H of chunk ci on its slot's copy stream, ordered behind its solve
     Slot& q = slot[ci % K]; const size_t b0 = (size_t)ci * chunk, nb = std::min<size_t>(chunk, (size_t)B - b0);
     if (landing_stream_wait(s, tk[ci], (void*)q.cp)) { rc = LANDING_E_HIP; return; }
-    int* ds = reinterpret_cast<int*>(q.si.p); int* di = ds + chunk;
-    hipError_t e = hipMemcpyAsync(x + b0 * L.nx, q.x.p, nb * L.nx * 8, hipMemcpyDeviceToHost, q.cp);
-    if (e == hipSuccess && f) e = hipMemcpyAsync(f + b0, q.f.p, nb * 8, hipMemcpyDeviceToHost, q.cp);
-    if (e == hipSuccess && lam_g) e = hipMemcpyAsync(lam_g + b0 * L.ng, q.l.p, nb * L.ng * 8, hipMemcpyDeviceToHost, q.cp);
+    int* ds = q.si.get(); int* di = ds + chunk;
+    hipError_t e = hipMemcpyAsync(x + b0 * L.nx, q.x.get(), nb * L.nx * 8, hipMemcpyDeviceToHost, q.cp);
+    if (e == hipSuccess && f) e = hipMemcpyAsync(f + b0, q.f.get(), nb * 8, hipMemcpyDeviceToHost, q.cp);
+    if (e == hipSuccess && lam_g) e = hipMemcpyAsync(lam_g + b0 * L.ng, q.l.get(), nb * L.ng * 8, hipMemcpyDeviceToHost, q.cp);
     if (e == hipSuccess && status) e = hipMemcpyAsync(status + b0, ds, nb * sizeof(int), hipMemcpyDeviceToHost, q.cp);
     if (e == hipSuccess && iters) e = hipMemcpyAsync(iters + b0, di, nb * sizeof(int), hipMemcpyDeviceToHost, q.cp);
-    if (e == hipSuccess && kkt) e = hipMemcpyAsync(kkt + b0 * 3, q.k.p, nb * 3 * 8, hipMemcpyDeviceToHost, q.cp);
+    if (e == hipSuccess && kkt) e = hipMemcpyAsync(kkt + b0 * 3, q.k.get(), nb * 3 * 8, hipMemcpyDeviceToHost, q.cp);
     if (e != hipSuccess) bail(LANDING_E_HIP, "landing_solve_stream_host: download failed");
   };
   for (int ci = 0; ci < nchunk && !rc; ++ci) {
     Slot& q = slot[ci % K]; const size_t b0 = (size_t)ci * chunk, nb = std::min<size_t>(chunk, (size_t)B - b0);
     if (ci >= K) { download(ci - K); if (rc) break; if (hipStreamSynchronize(q.cp) != hipSuccess) { bail(LANDING_E_HIP, "landing_solve_stream_host: copy failed"); break; } }      // the slot's buffers are free again
-    if (hipMemcpyAsync(q.p.p, p + b0 * L.np, nb * L.np * 8, hipMemcpyHostToDevice, q.cp) != hipSuccess ||
-        hipMemcpyAsync(q.x0.p, x0 + b0 * L.nx, nb * L.nx * 8, hipMemcpyHostToDevice, q.cp) != hipSuccess) { bail(LANDING_E_HIP, "landing_solve_stream_host: upload failed"); break; }
-    int* ds = reinterpret_cast<int*>(q.si.p); int* di = ds + chunk;
-    const long long t = landing_stream_submit(s, (int)nb, q.p.p, q.x0.p, opts, q.x.p, q.f.p, q.l.p, ds, di, q.k.p, (void*)q.cp);
+    if (hipMemcpyAsync(q.p.get(), p + b0 * L.np, nb * L.np * 8, hipMemcpyHostToDevice, q.cp) != hipSuccess ||
+        hipMemcpyAsync(q.x0.get(), x0 + b0 * L.nx, nb * L.nx * 8, hipMemcpyHostToDevice, q.cp) != hipSuccess) { bail(LANDING_E_HIP, "landing_solve_stream_host: upload failed"); break; }
+    int* ds = q.si.get(); int* di = ds + chunk;
+    const long long t = landing_stream_submit(s, (int)nb, q.p.get(), q.x0.get(), opts, q.x.get(), q.f.get(), q.l.get(), ds, di, q.k.get(), (void*)q.cp);
     if (t < 0) { rc = (int)t; break; }
     tk[ci] = t;
   }
   for (int ci = std::max(0, nchunk - K); ci < nchunk && !rc; ++ci) if (tk[ci] >= 0) download(ci);
   for (int i = 0; i < K; ++i) if (slot[i].cp) { if (hipStreamSynchronize(slot[i].cp) != hipSuccess && !rc) bail(LANDING_E_HIP, "landing_solve_stream_host: kernel failed"); }
   (void)landing_stream_sync(s, nullptr);
-  for (int i = 0; i < K; ++i) { if (slot[i].up) (void)hipEventDestroy(slot[i].up); if (slot[i].cp) (void)hipStreamDestroy(slot[i].cp); }
+  for (int i = 0; i < K; ++i) if (slot[i].cp) (void)hipStreamDestroy(slot[i].cp);
   return rc;
 }
 

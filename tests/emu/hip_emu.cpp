@@ -1,8 +1,35 @@
-// hip_emu.cpp -- TEST INFRASTRUCTURE (see hip_emu.h): fiber scheduler for emulated thread blocks.
+// hip_emu.cpp -- TEST INFRASTRUCTURE (see hip_emu.h): allocation accounting and the fiber scheduler for emulated thread blocks.
 #include "hip_emu.h"
+
+#include <atomic>
 
 emu_idx threadIdx, blockIdx;
 dim3 blockDim, gridDim;
+
+// Allocation accounting of hipMalloc / hipHostMalloc: the blocks that are live, and a failure forced onto the k-th allocation after
+// hip_emu_fail_alloc(k) (k <= 0: none), which returns the number of allocations made since its previous call.
+namespace {
+std::atomic<long long> g_live{0}, g_allocs{0}, g_fail_at{0};
+}
+hipError_t hip_emu::mem_alloc(void** p, size_t n) {
+  *p = nullptr;
+  if (++g_allocs == g_fail_at) return 2;      // (hipErrorOutOfMemory)
+  *p = std::malloc(n ? n : 1);
+  if (!*p) return 2;
+  ++g_live;
+  return 0;
+}
+hipError_t hip_emu::mem_free(void* p) {
+  if (p) --g_live;
+  std::free(p);
+  return 0;
+}
+extern "C" long long hip_emu_live_blocks(void) { return g_live; }
+extern "C" long long hip_emu_fail_alloc(long long k) {
+  const long long n = g_allocs.exchange(0);
+  g_fail_at = k;
+  return n;
+}
 
 namespace hip_emu {
 namespace {

@@ -41,12 +41,17 @@ typedef void* hipEvent_t;
 #define hipMemcpyHostToDevice 1
 #define hipMemcpyDeviceToHost 2
 #define hipMemcpyDeviceToDevice 3
-inline hipError_t hipMalloc(void** p, size_t n) { *p = std::malloc(n ? n : 1); return *p ? 0 : 2; }
+// device and pinned blocks are counted (hip_emu.cpp: hip_emu_live_blocks, hip_emu_fail_alloc)
+namespace hip_emu {
+hipError_t mem_alloc(void** p, size_t n);
+hipError_t mem_free(void* p);
+}
+inline hipError_t hipMalloc(void** p, size_t n) { return hip_emu::mem_alloc(p, n); }
 template <typename T> inline hipError_t hipMalloc(T** p, size_t n) { return hipMalloc((void**)p, n); }
-inline hipError_t hipFree(void* p) { std::free(p); return 0; }
+inline hipError_t hipFree(void* p) { return hip_emu::mem_free(p); }
 #define hipHostMallocDefault 0
-inline hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = std::malloc(n ? n : 1); return *p ? 0 : 2; }
-inline hipError_t hipHostFree(void* p) { std::free(p); return 0; }
+inline hipError_t hipHostMalloc(void** p, size_t n, unsigned) { return hip_emu::mem_alloc(p, n); }
+inline hipError_t hipHostFree(void* p) { return hip_emu::mem_free(p); }
 inline hipError_t hipMemcpy(void* d, const void* s, size_t n, int) { std::memcpy(d, s, n); return 0; }
 inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, int, hipStream_t) { std::memcpy(d, s, n); return 0; }
 inline hipError_t hipMemset(void* d, int v, size_t n) { std::memset(d, v, n); return 0; }
