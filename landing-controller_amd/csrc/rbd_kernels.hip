@@ -28,41 +28,88 @@ struct RbdModel {                    // host-built (landing-controller_amd/rbd.p
   double l1, l2, l3, l4;             // leg lengths of get_foot_jacobians_mc.m:5-8
 };
 
-struct V3d { double x, y, z; };
-__device__ __forceinline__ V3d mk3(double x, double y, double z) { V3d v; v.x = x; v.y = y; v.z = z; return v; }
-__device__ __forceinline__ V3d add3(V3d a, V3d b) { return mk3(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ V3d sub3(V3d a, V3d b) { return mk3(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ V3d scl3(double s, V3d a) { return mk3(s * a.x, s * a.y, s * a.z); }
-__device__ __forceinline__ V3d crs3(V3d a, V3d b) { return mk3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-__device__ __forceinline__ V3d mul3(const double* E, V3d v) { return mk3(E[0] * v.x + E[1] * v.y + E[2] * v.z, E[3] * v.x + E[4] * v.y + E[5] * v.z, E[6] * v.x + E[7] * v.y + E[8] * v.z); }
-__device__ __forceinline__ V3d mulT3(const double* E, V3d v) { return mk3(E[0] * v.x + E[3] * v.y + E[6] * v.z, E[1] * v.x + E[4] * v.y + E[7] * v.z, E[2] * v.x + E[5] * v.y + E[8] * v.z); }
-__device__ __forceinline__ V3d sym3(const double* I, V3d v) { return mk3(I[0] * v.x + I[1] * v.y + I[2] * v.z, I[1] * v.x + I[3] * v.y + I[4] * v.z, I[2] * v.x + I[4] * v.y + I[5] * v.z); }
-struct SV { V3d a, l; };             // spatial vector: angular / linear (motion) or moment / force
+// ---- scalars and spatial algebra, shared by every routine of this file and wb_kernels.hip ---------------------------
+// Three scalar types run through the same code: double for values, Dual (value, derivative) for one tangent direction (forward mode), HDual for
+// a pair of directions (second order).  Constants enter a T expression lifted by lit(), the way each routine was first written for its own
+// scalar: lit(x, c) * y and c * y are different arithmetic for Dual, and the derivative kernels must not change their iterates.
+struct Dual { double v, d; };
+__device__ __forceinline__ Dual D_(double v, double d = 0.0) { Dual o; o.v = v; o.d = d; return o; }
+__device__ __forceinline__ Dual operator+(Dual a, Dual b) { return D_(a.v + b.v, a.d + b.d); }
+__device__ __forceinline__ Dual operator-(Dual a, Dual b) { return D_(a.v - b.v, a.d - b.d); }
+__device__ __forceinline__ Dual operator-(Dual a) { return D_(-a.v, -a.d); }
+__device__ __forceinline__ Dual operator*(Dual a, Dual b) { return D_(a.v * b.v, fma(a.v, b.d, a.d * b.v)); }
+__device__ __forceinline__ Dual operator*(double a, Dual b) { return D_(a * b.v, a * b.d); }
+__device__ __forceinline__ Dual operator/(Dual a, Dual b) { const double q = a.v / b.v; return D_(q, (a.d - q * b.d) / b.v); }
+__device__ __forceinline__ Dual operator*(Dual a, double b) { return D_(a.v * b, a.d * b); }
+__device__ __forceinline__ Dual operator+(Dual a, double b) { return D_(a.v + b, a.d); }
+__device__ __forceinline__ Dual operator-(Dual a, double b) { return D_(a.v - b, a.d); }
+// second-order forward mode: value, two first-order parts and the mixed second-order part along directions (e_i, e_j); the same stage
+// function instantiated on this scalar gives d^2 rows / dw_i dw_j exactly (hyper-dual numbers)
+struct HDual { double v, a, b, ab; };
+__device__ __forceinline__ HDual H_(double v, double a = 0.0, double b = 0.0, double ab = 0.0) { HDual o; o.v = v; o.a = a; o.b = b; o.ab = ab; return o; }
+__device__ __forceinline__ HDual operator+(HDual x, HDual y) { return H_(x.v + y.v, x.a + y.a, x.b + y.b, x.ab + y.ab); }
+__device__ __forceinline__ HDual operator-(HDual x, HDual y) { return H_(x.v - y.v, x.a - y.a, x.b - y.b, x.ab - y.ab); }
+__device__ __forceinline__ HDual operator*(HDual x, HDual y) { return H_(x.v * y.v, x.a * y.v + x.v * y.a, x.b * y.v + x.v * y.b, x.ab * y.v + x.a * y.b + x.b * y.a + x.v * y.ab); }
+__device__ __forceinline__ HDual operator*(HDual x, double s) { return H_(x.v * s, x.a * s, x.b * s, x.ab * s); }
+__device__ __forceinline__ HDual operator*(double s, HDual x) { return H_(x.v * s, x.a * s, x.b * s, x.ab * s); }
+__device__ __forceinline__ HDual operator+(HDual x, double s) { return H_(x.v + s, x.a, x.b, x.ab); }
+__device__ __forceinline__ HDual operator-(HDual x, double s) { return H_(x.v - s, x.a, x.b, x.ab); }
+__device__ __forceinline__ HDual operator/(HDual x, HDual y) {
+  const double f = 1.0 / y.v, f1 = -f * f, f2 = -2.0 * f * f1;
+  return x * H_(f, f1 * y.a, f1 * y.b, f2 * y.a * y.b + f1 * y.ab);
+}
+__device__ __forceinline__ void sincos_t(double x, double& s, double& c) { sincos(x, &s, &c); }
+__device__ __forceinline__ void sincos_t(Dual x, Dual& s, Dual& c) { double sv, cv; sincos(x.v, &sv, &cv); s = D_(sv, cv * x.d); c = D_(cv, -sv * x.d); }
+__device__ __forceinline__ void sincos_t(HDual x, HDual& s, HDual& c) {
+  double sv, cv; sincos(x.v, &sv, &cv);
+  s = H_(sv, cv * x.a, cv * x.b, -sv * x.a * x.b + cv * x.ab); c = H_(cv, -sv * x.a, -sv * x.b, -cv * x.a * x.b - sv * x.ab);
+}
+// the constant v as a number of the scalar type of the first argument
+__device__ __forceinline__ double lit(double, double v) { return v; }
+__device__ __forceinline__ Dual lit(Dual, double v) { return D_(v); }
+__device__ __forceinline__ HDual lit(HDual, double v) { return H_(v); }
+
+template <class T> struct V3 { T x, y, z; };
+template <class T> __device__ __forceinline__ V3<T> mk3(T x, T y, T z) { V3<T> v; v.x = x; v.y = y; v.z = z; return v; }
+template <class T> __device__ __forceinline__ V3<T> cst3(const T& like, const double* p) { return mk3(lit(like, p[0]), lit(like, p[1]), lit(like, p[2])); }   // constants, lifted
+template <class T> __device__ __forceinline__ V3<T> add3(V3<T> a, V3<T> b) { return mk3(a.x + b.x, a.y + b.y, a.z + b.z); }
+template <class T> __device__ __forceinline__ V3<T> sub3(V3<T> a, V3<T> b) { return mk3(a.x - b.x, a.y - b.y, a.z - b.z); }
+template <class T> __device__ __forceinline__ V3<T> scl3(double s, V3<T> a) { return mk3(s * a.x, s * a.y, s * a.z); }
+template <class T> __device__ __forceinline__ V3<T> crs3(V3<T> a, V3<T> b) { return mk3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+template <class T> __device__ __forceinline__ V3<T> mul3(const T* E, V3<T> v) { return mk3(E[0] * v.x + E[1] * v.y + E[2] * v.z, E[3] * v.x + E[4] * v.y + E[5] * v.z, E[6] * v.x + E[7] * v.y + E[8] * v.z); }
+template <class T> __device__ __forceinline__ V3<T> mulT3(const T* E, V3<T> v) { return mk3(E[0] * v.x + E[3] * v.y + E[6] * v.z, E[1] * v.x + E[4] * v.y + E[7] * v.z, E[2] * v.x + E[5] * v.y + E[8] * v.z); }
+template <class T> __device__ __forceinline__ V3<T> sym3(const double* I, V3<T> v) { return mk3(I[0] * v.x + I[1] * v.y + I[2] * v.z, I[1] * v.x + I[3] * v.y + I[4] * v.z, I[2] * v.x + I[4] * v.y + I[5] * v.z); }
+template <class T> struct SV { V3<T> a, l; };      // spatial vector: angular / linear (motion) or moment / force
+template <class T> __device__ __forceinline__ SV<T> addS(SV<T> p, SV<T> q) { SV<T> o; o.a = add3(p.a, q.a); o.l = add3(p.l, q.l); return o; }
 
 // joint transform applied on top of Xtree: Xup = XJ * plux(E, r)   (jcalc.m:22-40, plux.m)
 // The axis is a template parameter (joint_xform below dispatches): with a run-time axis the rows of E are addressed through computed indices, and
 // the callers' per-body E arrays then cannot live in registers (round 4: 8.9 KB -> 1.3 KB of scratch in the tangent kernel, 7.6 KB in the hyper-dual one).
-template <int JT>
-__device__ __forceinline__ void joint_xform_t(double q, const double* Et, const double* rt, double* E, double* r) {
+template <int JT, class T>
+__device__ __forceinline__ void joint_xform_t(T q, const double* Et, const double* rt, T* E, T* r) {
   if (JT < 3) {
-    double s, c; sincos(q, &s, &c);
+    T S, Cc; sincos_t(q, S, Cc);
     // rows of rx/ry/rz (coordinate transforms): rx = [1 0 0; 0 c s; 0 -s c], ry = [c 0 -s; 0 1 0; s 0 c], rz = [c s 0; -s c 0; 0 0 1]
+    // (the second rotated row has two spellings: the contraction into an FMA rounds the other product in each, and the value and derivative
+    // kernels keep the rounding they were written with)
     constexpr int a = JT < 3 ? JT : 0, b = (a + 1) % 3, d = (a + 2) % 3;
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-      E[3 * a + j] = Et[3 * a + j];
-      E[3 * b + j] = c * Et[3 * b + j] + s * Et[3 * d + j];
-      E[3 * d + j] = -s * Et[3 * b + j] + c * Et[3 * d + j];
+      E[3 * a + j] = lit(q, Et[3 * a + j]);
+      E[3 * b + j] = Et[3 * b + j] * Cc + Et[3 * d + j] * S;
+      if constexpr (std::is_same<T, double>::value) E[3 * d + j] = -S * Et[3 * b + j] + Cc * Et[3 * d + j];
+      else E[3 * d + j] = Et[3 * d + j] * Cc - Et[3 * b + j] * S;
     }
-    r[0] = rt[0]; r[1] = rt[1]; r[2] = rt[2];
+    r[0] = lit(q, rt[0]); r[1] = lit(q, rt[1]); r[2] = lit(q, rt[2]);
   } else {   // xlt(q e_a) * plux(E, r) = plux(E, r + E' (q e_a))
     constexpr int a = JT >= 3 ? JT - 3 : 0;
 #pragma unroll
-    for (int j = 0; j < 9; ++j) E[j] = Et[j];
-    r[0] = rt[0] + Et[3 * a] * q; r[1] = rt[1] + Et[3 * a + 1] * q; r[2] = rt[2] + Et[3 * a + 2] * q;
+    for (int j = 0; j < 9; ++j) E[j] = lit(q, Et[j]);
+    r[0] = lit(q, rt[0]) + Et[3 * a] * q; r[1] = lit(q, rt[1]) + Et[3 * a + 1] * q; r[2] = lit(q, rt[2]) + Et[3 * a + 2] * q;
   }
 }
-__device__ __forceinline__ void joint_xform(int jt, double q, const double* Et, const double* rt, double* E, double* r) {
+template <class T>
+__device__ __forceinline__ void joint_xform(int jt, T q, const double* Et, const double* rt, T* E, T* r) {
   switch (jt) {
     case 0: joint_xform_t<0>(q, Et, rt, E, r); break;
     case 1: joint_xform_t<1>(q, Et, rt, E, r); break;
@@ -72,47 +119,100 @@ __device__ __forceinline__ void joint_xform(int jt, double q, const double* Et, 
     default: joint_xform_t<5>(q, Et, rt, E, r); break;
   }
 }
-__device__ __forceinline__ SV xmotion(const double* E, const double* r, SV v) {      // X v
-  const V3d rr = mk3(r[0], r[1], r[2]);
-  SV o; o.a = mul3(E, v.a); o.l = mul3(E, sub3(v.l, crs3(rr, v.a))); return o;
+template <class T>
+__device__ __forceinline__ void plux_compose(const T* Eu, const T* ru, T* Ea, T* ra) {      // (Ea, ra) <- plux(Eu, ru) * plux(Ea, ra)
+  const V3<T> t = mulT3(Ea, mk3(ru[0], ru[1], ru[2]));
+  T En[9];
+  for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) En[3 * a + b] = Eu[3 * a] * Ea[b] + Eu[3 * a + 1] * Ea[3 + b] + Eu[3 * a + 2] * Ea[6 + b];
+  for (int j = 0; j < 9; ++j) Ea[j] = En[j];
+  ra[0] = ra[0] + t.x; ra[1] = ra[1] + t.y; ra[2] = ra[2] + t.z;
 }
-__device__ __forceinline__ SV xforceT(const double* E, const double* r, SV f) {      // X' f  (child -> parent)
-  const V3d rr = mk3(r[0], r[1], r[2]);
-  SV o; o.l = mulT3(E, f.l); o.a = add3(mulT3(E, f.a), crs3(rr, o.l)); return o;
+// world -> base transform of the tree: the six base joints (bodies 1..6) at the coordinates q[0..5] (an array or a view of T), composed joint by joint
+// from the identity; (Ej, rj): the caller's scratch for one joint transform
+template <class T, class Q>
+__device__ __forceinline__ void base_chain(const RbdModel& M, Q q, T* E0, T* r0, T* Ej, T* rj) {
+  for (int j = 0; j < 9; ++j) E0[j] = lit(T(), (j % 4 == 0) ? 1.0 : 0.0);
+  r0[0] = r0[1] = r0[2] = lit(T(), 0.0);
+  for (int i = 0; i < 6; ++i) { joint_xform(M.jtype[i], q[i], M.E[i], M.r[i], Ej, rj); plux_compose(Ej, rj, E0, r0); }
 }
-__device__ __forceinline__ SV crm_mul(SV v, SV w) { SV o; o.a = crs3(v.a, w.a); o.l = add3(crs3(v.a, w.l), crs3(v.l, w.a)); return o; }
-__device__ __forceinline__ SV crf_mul(SV v, SV f) { SV o; o.a = add3(crs3(v.a, f.a), crs3(v.l, f.l)); o.l = crs3(v.a, f.l); return o; }
-__device__ __forceinline__ SV inertia_mul(double m, const double* h, const double* I, SV v) {
-  const V3d hh = mk3(h[0], h[1], h[2]);
-  SV o; o.a = add3(sym3(I, v.a), crs3(hh, v.l)); o.l = sub3(scl3(m, v.l), crs3(hh, v.a)); return o;
+template <class T> __device__ __forceinline__ SV<T> xmotion(const T* E, const T* r, SV<T> v) {      // X v
+  const V3<T> rr = mk3(r[0], r[1], r[2]);
+  SV<T> o; o.a = mul3(E, v.a); o.l = mul3(E, sub3(v.l, crs3(rr, v.a))); return o;
 }
-__device__ __forceinline__ double sdot(int jt, SV f) { return jt == 0 ? f.a.x : (jt == 1 ? f.a.y : (jt == 2 ? f.a.z : (jt == 3 ? f.l.x : (jt == 4 ? f.l.y : f.l.z)))); }
-__device__ __forceinline__ SV sunit(int jt, double s) {
-  SV o; o.a = mk3(jt == 0 ? s : 0.0, jt == 1 ? s : 0.0, jt == 2 ? s : 0.0); o.l = mk3(jt == 3 ? s : 0.0, jt == 4 ? s : 0.0, jt == 5 ? s : 0.0); return o;
+template <class T> __device__ __forceinline__ SV<T> xforceT(const T* E, const T* r, SV<T> f) {      // X' f  (child -> parent)
+  const V3<T> rr = mk3(r[0], r[1], r[2]);
+  SV<T> o; o.l = mulT3(E, f.l); o.a = add3(mulT3(E, f.a), crs3(rr, o.l)); return o;
 }
+template <class T> __device__ __forceinline__ SV<T> crm_mul(SV<T> v, SV<T> w) { SV<T> o; o.a = crs3(v.a, w.a); o.l = add3(crs3(v.a, w.l), crs3(v.l, w.a)); return o; }
+template <class T> __device__ __forceinline__ SV<T> crf_mul(SV<T> v, SV<T> f) { SV<T> o; o.a = add3(crs3(v.a, f.a), crs3(v.l, f.l)); o.l = crs3(v.a, f.l); return o; }
+template <class T> __device__ __forceinline__ SV<T> inertia_mul(double m, const double* h, const double* I, SV<T> v) {
+  const V3<T> hh = cst3(v.a.x, h);
+  SV<T> o; o.a = add3(sym3(I, v.a), crs3(hh, v.l)); o.l = sub3(scl3(m, v.l), crs3(hh, v.a)); return o;
+}
+template <class T> __device__ __forceinline__ T sdot(int jt, SV<T> f) { return jt == 0 ? f.a.x : (jt == 1 ? f.a.y : (jt == 2 ? f.a.z : (jt == 3 ? f.l.x : (jt == 4 ? f.l.y : f.l.z)))); }
+template <class T> __device__ __forceinline__ SV<T> sunit(int jt, T s) {
+  const T z = lit(s, 0.0);
+  SV<T> o; o.a = mk3(jt == 0 ? s : z, jt == 1 ? s : z, jt == 2 ? s : z); o.l = mk3(jt == 3 ? s : z, jt == 4 ? s : z, jt == 5 ? s : z); return o;
+}
+
+// external force at a foot (casadi_compatible_dynamics.m:53-60): the world-frame force fw at the point foot_r of the body whose world transform is
+// plux(E, r), as a spatial force in body coordinates, X0^* f = [E (n - r x f); E f] with n the moment about the world origin -- the recursion subtracts it
+template <class T>
+__device__ __forceinline__ SV<T> foot_force(const T* E, const T* r, const double* foot_r, const double* fw3) {
+  const V3<T> rb = mk3(r[0], r[1], r[2]);
+  const V3<T> pf = add3(rb, mulT3(E, cst3(r[0], foot_r)));
+  const V3<T> fw = cst3(r[0], fw3);
+  const V3<T> nb = crs3(sub3(pf, rb), fw);
+  SV<T> o; o.a = mul3(E, nb); o.l = mul3(E, fw); return o;
+}
+
+
+// Cholesky factor (lower triangle, in place) of the 18 x 18 matrix H(18 i + j), and the solve with it: H is an accessor (a private array or the strided
+// LDS view of wb_kernels.hip).  chol_factor18 returns false if H is not positive definite.
+template <class A>
+__device__ __forceinline__ bool chol_factor18(const A& H) {
+  for (int j = 0; j < RB_NB; ++j) {
+    double d = H(j * RB_NB + j);
+    for (int k = 0; k < j; ++k) { const double l = H(j * RB_NB + k); d -= l * l; }
+    if (!(d > 0.0)) return false;
+    d = sqrt(d); H(j * RB_NB + j) = d;
+    for (int i = j + 1; i < RB_NB; ++i) {
+      double s = H(i * RB_NB + j);
+      for (int k = 0; k < j; ++k) s -= H(i * RB_NB + k) * H(j * RB_NB + k);
+      H(i * RB_NB + j) = s / d;
+    }
+  }
+  return true;
+}
+template <class A, class X>
+__device__ __forceinline__ void chol_subst18(const A& H, const X& x) {      // x <- H^-1 x with the factor of chol_factor18
+  for (int i = 0; i < RB_NB; ++i) { double s = x(i); for (int k = 0; k < i; ++k) s -= H(i * RB_NB + k) * x(k); x(i) = s / H(i * RB_NB + i); }
+  for (int i = RB_NB - 1; i >= 0; --i) { double s = x(i); for (int k = i + 1; k < RB_NB; ++k) s -= H(k * RB_NB + i) * x(k); x(i) = s / H(i * RB_NB + i); }
+}
+struct PrivArr { double* p; __device__ __forceinline__ double& operator()(int i) const { return p[i]; } };      // a private array as such an accessor
 
 // H (row-major 18 x 18, may be null) and C (18) for one configuration; f_foot: 12 world-frame foot forces or null
 __device__ void hand_c(const RbdModel& M, const double* q, const double* qd, const double* f_foot, double* H, double* C) {
   double E[RB_NB][9], r[RB_NB][3];
-  SV v[RB_NB], fvp[RB_NB];
+  SV<double> v[RB_NB], fvp[RB_NB];
   double E0[9], r0[3];                       // transform from the world to the current chain body (only the 4 foot bodies need it)
   double E0f[4][9], r0f[4][3];
   {
-    SV avp[RB_NB];
+    SV<double> avp[RB_NB];
     for (int i = 0; i < RB_NB; ++i) {
       joint_xform(M.jtype[i], q[i], M.E[i], M.r[i], E[i], r[i]);
-      const SV vJ = sunit(M.jtype[i], qd[i]);
+      const SV<double> vJ = sunit(M.jtype[i], qd[i]);
       const int pa = M.parent[i];
       if (pa == 0) {
-        SV g; g.a = mk3(0, 0, 0); g.l = mk3(0, 0, 9.81);      // -a_grav
+        SV<double> g; g.a = mk3(0.0, 0.0, 0.0); g.l = mk3(0.0, 0.0, 9.81);      // -a_grav
         v[i] = vJ; avp[i] = xmotion(E[i], r[i], g);
       } else {
-        const SV vp = xmotion(E[i], r[i], v[pa - 1]);
+        const SV<double> vp = xmotion(E[i], r[i], v[pa - 1]);
         v[i].a = add3(vp.a, vJ.a); v[i].l = add3(vp.l, vJ.l);
-        const SV ap = xmotion(E[i], r[i], avp[pa - 1]), cv = crm_mul(v[i], vJ);
+        const SV<double> ap = xmotion(E[i], r[i], avp[pa - 1]), cv = crm_mul(v[i], vJ);
         avp[i].a = add3(ap.a, cv.a); avp[i].l = add3(ap.l, cv.l);
       }
-      const SV Ia = inertia_mul(M.m[i], M.h[i], M.I[i], avp[i]), Iv = inertia_mul(M.m[i], M.h[i], M.I[i], v[i]), cf = crf_mul(v[i], Iv);
+      const SV<double> Ia = inertia_mul(M.m[i], M.h[i], M.I[i], avp[i]), Iv = inertia_mul(M.m[i], M.h[i], M.I[i], v[i]), cf = crf_mul(v[i], Iv);
       fvp[i].a = add3(Ia.a, cf.a); fvp[i].l = add3(Ia.l, cf.l);
     }
   }
@@ -120,30 +220,21 @@ __device__ void hand_c(const RbdModel& M, const double* q, const double* qd, con
     // world transforms of the four foot bodies: the base chain (bodies 1..6) then the leg (3 bodies)
     for (int j = 0; j < 9; ++j) E0[j] = (j % 4 == 0) ? 1.0 : 0.0;
     r0[0] = r0[1] = r0[2] = 0.0;
-    auto compose = [](const double* Eu, const double* ru, double* Ea, double* ra) {   // (Ea, ra) <- plux(Eu, ru) * plux(Ea, ra)
-      const V3d t = mulT3(Ea, mk3(ru[0], ru[1], ru[2]));
-      double En[9];
-      for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) En[3 * a + b] = Eu[3 * a] * Ea[b] + Eu[3 * a + 1] * Ea[3 + b] + Eu[3 * a + 2] * Ea[6 + b];
-      for (int j = 0; j < 9; ++j) Ea[j] = En[j];
-      ra[0] += t.x; ra[1] += t.y; ra[2] += t.z;
-    };
-    for (int i = 0; i < 6; ++i) compose(E[i], r[i], E0, r0);
+    for (int i = 0; i < 6; ++i) plux_compose(E[i], r[i], E0, r0);
     for (int leg = 0; leg < 4; ++leg) {
       for (int j = 0; j < 9; ++j) E0f[leg][j] = E0[j];
       for (int j = 0; j < 3; ++j) r0f[leg][j] = r0[j];
       const int jb = M.b_foot[leg] - 1;
-      for (int i = jb - 2; i <= jb; ++i) compose(E[i], r[i], E0f[leg], r0f[leg]);
+      for (int i = jb - 2; i <= jb; ++i) plux_compose(E[i], r[i], E0f[leg], r0f[leg]);
       // foot point in world coordinates, spatial force about the world origin, moved into body coordinates: X0^* f = [E0 (n - r0 x f); E0 f]
-      const V3d pf = add3(mk3(r0f[leg][0], r0f[leg][1], r0f[leg][2]), mulT3(E0f[leg], mk3(M.foot_r[leg][0], M.foot_r[leg][1], M.foot_r[leg][2])));
-      const V3d fw = mk3(f_foot[3 * leg], f_foot[3 * leg + 1], f_foot[3 * leg + 2]);
-      const V3d nb = crs3(sub3(pf, mk3(r0f[leg][0], r0f[leg][1], r0f[leg][2])), fw);
-      fvp[jb].a = sub3(fvp[jb].a, mul3(E0f[leg], nb)); fvp[jb].l = sub3(fvp[jb].l, mul3(E0f[leg], fw));
+      const SV<double> fe = foot_force(E0f[leg], r0f[leg], M.foot_r[leg], f_foot + 3 * leg);
+      fvp[jb].a = sub3(fvp[jb].a, fe.a); fvp[jb].l = sub3(fvp[jb].l, fe.l);
     }
   }
   for (int i = RB_NB - 1; i >= 0; --i) {
     C[i] = sdot(M.jtype[i], fvp[i]);
     const int pa = M.parent[i];
-    if (pa != 0) { const SV t = xforceT(E[i], r[i], fvp[i]); fvp[pa - 1].a = add3(fvp[pa - 1].a, t.a); fvp[pa - 1].l = add3(fvp[pa - 1].l, t.l); }
+    if (pa != 0) { const SV<double> t = xforceT(E[i], r[i], fvp[i]); fvp[pa - 1].a = add3(fvp[pa - 1].a, t.a); fvp[pa - 1].l = add3(fvp[pa - 1].l, t.l); }
   }
   if (!H) return;
   // composite rigid-body inertias in (m, h, Ibar) form: parent += X' I X with X = plux(E, r):
@@ -154,8 +245,8 @@ __device__ void hand_c(const RbdModel& M, const double* q, const double* qd, con
     const int pa = M.parent[i];
     if (pa == 0) continue;
     const double* Ei = E[i];
-    const V3d hp = mulT3(Ei, mk3(ch[i][0], ch[i][1], ch[i][2])), rr = mk3(r[i][0], r[i][1], r[i][2]);
-    const V3d hn = add3(hp, scl3(cm[i], rr));
+    const V3<double> hp = mulT3(Ei, mk3(ch[i][0], ch[i][1], ch[i][2])), rr = mk3(r[i][0], r[i][1], r[i][2]);
+    const V3<double> hn = add3(hp, scl3(cm[i], rr));
     // E' Ibar E (symmetric)
     double T[9];
     { const double* I6 = cI[i];
@@ -165,7 +256,7 @@ __device__ void hand_c(const RbdModel& M, const double* q, const double* qd, con
       for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) T[3 * a + b] = Ei[a] * A[b] + Ei[3 + a] * A[3 + b] + Ei[6 + a] * A[6 + b];                   // E' (Ibar E)
     }
     // - skew(r) skew(hp) - skew(hn) skew(r):  skew(a) skew(b) = b a' - (a.b) 1
-    auto add_ss = [&](V3d a, V3d b, double sgn) {
+    auto add_ss = [&](V3<double> a, V3<double> b, double sgn) {
       const double d = a.x * b.x + a.y * b.y + a.z * b.z;
       const double av[3] = {a.x, a.y, a.z}, bv[3] = {b.x, b.y, b.z};
       for (int x = 0; x < 3; ++x) for (int y = 0; y < 3; ++y) T[3 * x + y] += sgn * (bv[x] * av[y] - (x == y ? d : 0.0));
@@ -177,7 +268,7 @@ __device__ void hand_c(const RbdModel& M, const double* q, const double* qd, con
   }
   for (int i = 0; i < RB_NB * RB_NB; ++i) H[i] = 0.0;
   for (int i = 0; i < RB_NB; ++i) {
-    SV fh = inertia_mul(cm[i], ch[i], cI[i], sunit(M.jtype[i], 1.0));
+    SV<double> fh = inertia_mul(cm[i], ch[i], cI[i], sunit(M.jtype[i], 1.0));
     H[i * RB_NB + i] = sdot(M.jtype[i], fh);
     int j = i;
     while (M.parent[j] > 0) {
@@ -191,19 +282,8 @@ __device__ void hand_c(const RbdModel& M, const double* q, const double* qd, con
 
 // in-place Cholesky solve of the 18 x 18 system H x = b (H destroyed); returns false if H is not positive definite
 __device__ bool chol_solve18(double* H, double* b) {
-  for (int j = 0; j < RB_NB; ++j) {
-    double d = H[j * RB_NB + j];
-    for (int k = 0; k < j; ++k) d -= H[j * RB_NB + k] * H[j * RB_NB + k];
-    if (!(d > 0.0)) return false;
-    d = sqrt(d); H[j * RB_NB + j] = d;
-    for (int i = j + 1; i < RB_NB; ++i) {
-      double s = H[i * RB_NB + j];
-      for (int k = 0; k < j; ++k) s -= H[i * RB_NB + k] * H[j * RB_NB + k];
-      H[i * RB_NB + j] = s / d;
-    }
-  }
-  for (int i = 0; i < RB_NB; ++i) { double s = b[i]; for (int k = 0; k < i; ++k) s -= H[i * RB_NB + k] * b[k]; b[i] = s / H[i * RB_NB + i]; }
-  for (int i = RB_NB - 1; i >= 0; --i) { double s = b[i]; for (int k = i + 1; k < RB_NB; ++k) s -= H[k * RB_NB + i] * b[k]; b[i] = s / H[i * RB_NB + i]; }
+  if (!chol_factor18(PrivArr{H})) return false;
+  chol_subst18(PrivArr{H}, PrivArr{b});
   return true;
 }
 
@@ -273,87 +353,17 @@ __global__ void __launch_bounds__(64) landing_fb_lin_kernel(FbArgs a) {
 // differentiation of the same recursion (casadi_compatible_dynamics.m is called on SX symbols); here every thread pushes ONE tangent
 // direction through the recursion with dual numbers (value, derivative) -- exact to rounding, one O(n) pass per column instead of the
 // two O(n^2..n^3) forward-dynamics evaluations of the central-difference kernel above.
-struct Dual { double v, d; };
-__device__ __forceinline__ Dual D_(double v, double d = 0.0) { Dual o; o.v = v; o.d = d; return o; }
-__device__ __forceinline__ Dual operator+(Dual a, Dual b) { return D_(a.v + b.v, a.d + b.d); }
-__device__ __forceinline__ Dual operator-(Dual a, Dual b) { return D_(a.v - b.v, a.d - b.d); }
-__device__ __forceinline__ Dual operator-(Dual a) { return D_(-a.v, -a.d); }
-__device__ __forceinline__ Dual operator*(Dual a, Dual b) { return D_(a.v * b.v, fma(a.v, b.d, a.d * b.v)); }
-__device__ __forceinline__ Dual operator*(double a, Dual b) { return D_(a * b.v, a * b.d); }
-struct V3D { Dual x, y, z; };
-__device__ __forceinline__ V3D mk3D(Dual x, Dual y, Dual z) { V3D v; v.x = x; v.y = y; v.z = z; return v; }
-__device__ __forceinline__ V3D mk3D(double x, double y, double z) { return mk3D(D_(x), D_(y), D_(z)); }
-__device__ __forceinline__ V3D add3(V3D a, V3D b) { return mk3D(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ V3D sub3(V3D a, V3D b) { return mk3D(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ V3D scl3(double s, V3D a) { return mk3D(s * a.x, s * a.y, s * a.z); }
-__device__ __forceinline__ V3D crs3(V3D a, V3D b) { return mk3D(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-__device__ __forceinline__ V3D mul3(const Dual* E, V3D v) { return mk3D(E[0] * v.x + E[1] * v.y + E[2] * v.z, E[3] * v.x + E[4] * v.y + E[5] * v.z, E[6] * v.x + E[7] * v.y + E[8] * v.z); }
-__device__ __forceinline__ V3D mulT3(const Dual* E, V3D v) { return mk3D(E[0] * v.x + E[3] * v.y + E[6] * v.z, E[1] * v.x + E[4] * v.y + E[7] * v.z, E[2] * v.x + E[5] * v.y + E[8] * v.z); }
-__device__ __forceinline__ V3D sym3(const double* I, V3D v) { return mk3D(I[0] * v.x + I[1] * v.y + I[2] * v.z, I[1] * v.x + I[3] * v.y + I[4] * v.z, I[2] * v.x + I[4] * v.y + I[5] * v.z); }
-struct SVD { V3D a, l; };
-__device__ __forceinline__ SVD addS(SVD p, SVD q) { SVD o; o.a = add3(p.a, q.a); o.l = add3(p.l, q.l); return o; }
-// (the axis is a template parameter: with a run-time axis the rows of E are addressed through computed indices and the callers' E arrays
-// cannot live in registers)
-template <int JT>
-__device__ __forceinline__ void joint_xform_t(Dual q, const double* Et, const double* rt, Dual* E, Dual* r) {
-  if (JT < 3) {
-    double s, c; sincos(q.v, &s, &c);
-    const Dual S = D_(s, c * q.d), Cc = D_(c, -s * q.d);
-    constexpr int a = JT < 3 ? JT : 0, b = (a + 1) % 3, d = (a + 2) % 3;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      E[3 * a + j] = D_(Et[3 * a + j]);
-      E[3 * b + j] = Et[3 * b + j] * Cc + Et[3 * d + j] * S;
-      E[3 * d + j] = Et[3 * d + j] * Cc - Et[3 * b + j] * S;
-    }
-    r[0] = D_(rt[0]); r[1] = D_(rt[1]); r[2] = D_(rt[2]);
-  } else {
-    constexpr int a = JT >= 3 ? JT - 3 : 0;
-#pragma unroll
-    for (int j = 0; j < 9; ++j) E[j] = D_(Et[j]);
-    r[0] = D_(rt[0]) + Et[3 * a] * q; r[1] = D_(rt[1]) + Et[3 * a + 1] * q; r[2] = D_(rt[2]) + Et[3 * a + 2] * q;
-  }
-}
-__device__ __forceinline__ void joint_xform(int jt, Dual q, const double* Et, const double* rt, Dual* E, Dual* r) {
-  switch (jt) {
-    case 0: joint_xform_t<0>(q, Et, rt, E, r); break;
-    case 1: joint_xform_t<1>(q, Et, rt, E, r); break;
-    case 2: joint_xform_t<2>(q, Et, rt, E, r); break;
-    case 3: joint_xform_t<3>(q, Et, rt, E, r); break;
-    case 4: joint_xform_t<4>(q, Et, rt, E, r); break;
-    default: joint_xform_t<5>(q, Et, rt, E, r); break;
-  }
-}
-__device__ __forceinline__ SVD xmotion(const Dual* E, const Dual* r, SVD v) {
-  const V3D rr = mk3D(r[0], r[1], r[2]);
-  SVD o; o.a = mul3(E, v.a); o.l = mul3(E, sub3(v.l, crs3(rr, v.a))); return o;
-}
-__device__ __forceinline__ SVD xforceT(const Dual* E, const Dual* r, SVD f) {
-  const V3D rr = mk3D(r[0], r[1], r[2]);
-  SVD o; o.l = mulT3(E, f.l); o.a = add3(mulT3(E, f.a), crs3(rr, o.l)); return o;
-}
-__device__ __forceinline__ SVD crm_mul(SVD v, SVD w) { SVD o; o.a = crs3(v.a, w.a); o.l = add3(crs3(v.a, w.l), crs3(v.l, w.a)); return o; }
-__device__ __forceinline__ SVD crf_mul(SVD v, SVD f) { SVD o; o.a = add3(crs3(v.a, f.a), crs3(v.l, f.l)); o.l = crs3(v.a, f.l); return o; }
-__device__ __forceinline__ SVD inertia_mul(double m, const double* h, const double* I, SVD v) {
-  const V3D hh = mk3D(h[0], h[1], h[2]);
-  SVD o; o.a = add3(sym3(I, v.a), crs3(hh, v.l)); o.l = sub3(scl3(m, v.l), crs3(hh, v.a)); return o;
-}
-__device__ __forceinline__ Dual sdot(int jt, SVD f) { return jt == 0 ? f.a.x : (jt == 1 ? f.a.y : (jt == 2 ? f.a.z : (jt == 3 ? f.l.x : (jt == 4 ? f.l.y : f.l.z)))); }
-__device__ __forceinline__ SVD sunit(int jt, Dual s) {
-  const Dual z = D_(0.0);
-  SVD o; o.a = mk3D(jt == 0 ? s : z, jt == 1 ? s : z, jt == 2 ? s : z); o.l = mk3D(jt == 3 ? s : z, jt == 4 ? s : z, jt == 5 ? s : z); return o;
-}
 // derivative of tau = ID(q, qd, qdd, f_foot) along the direction (dir < 18: q_dir, else qd_{dir-18}); dtau[18]
 __device__ void rnea_tangent(const RbdModel& M, const double* q, const double* qd, const double* qdd, const double* f_foot, int dir, double* dtau) {
   Dual E[RB_NB][9], r[RB_NB][3];
-  SVD v[RB_NB], fvp[RB_NB], avp[RB_NB];
+  SV<Dual> v[RB_NB], fvp[RB_NB], avp[RB_NB];
   for (int i = 0; i < RB_NB; ++i) {
     const Dual qi = D_(q[i], dir == i ? 1.0 : 0.0), qdi = D_(qd[i], dir == RB_NB + i ? 1.0 : 0.0);
     joint_xform(M.jtype[i], qi, M.E[i], M.r[i], E[i], r[i]);
-    const SVD vJ = sunit(M.jtype[i], qdi), aJ = sunit(M.jtype[i], D_(qdd[i]));
+    const SV<Dual> vJ = sunit(M.jtype[i], qdi), aJ = sunit(M.jtype[i], D_(qdd[i]));
     const int pa = M.parent[i];
     if (pa == 0) {
-      SVD g; g.a = mk3D(0.0, 0.0, 0.0); g.l = mk3D(0.0, 0.0, 9.81);
+      SV<Dual> g; g.a = mk3(D_(0.0), D_(0.0), D_(0.0)); g.l = mk3(D_(0.0), D_(0.0), D_(9.81));
       v[i] = vJ; avp[i] = addS(xmotion(E[i], r[i], g), aJ);
     } else {
       v[i] = addS(xmotion(E[i], r[i], v[pa - 1]), vJ);
@@ -365,25 +375,15 @@ __device__ void rnea_tangent(const RbdModel& M, const double* q, const double* q
     Dual E0[9], r0[3];
     for (int j = 0; j < 9; ++j) E0[j] = D_((j % 4 == 0) ? 1.0 : 0.0);
     r0[0] = r0[1] = r0[2] = D_(0.0);
-    auto compose = [](const Dual* Eu, const Dual* ru, Dual* Ea, Dual* ra) {
-      const V3D t = mulT3(Ea, mk3D(ru[0], ru[1], ru[2]));
-      Dual En[9];
-      for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) En[3 * a + b] = Eu[3 * a] * Ea[b] + Eu[3 * a + 1] * Ea[3 + b] + Eu[3 * a + 2] * Ea[6 + b];
-      for (int j = 0; j < 9; ++j) Ea[j] = En[j];
-      ra[0] = ra[0] + t.x; ra[1] = ra[1] + t.y; ra[2] = ra[2] + t.z;
-    };
-    for (int i = 0; i < 6; ++i) compose(E[i], r[i], E0, r0);
+    for (int i = 0; i < 6; ++i) plux_compose(E[i], r[i], E0, r0);
     for (int leg = 0; leg < 4; ++leg) {
       Dual Ef[9], rf[3];
       for (int j = 0; j < 9; ++j) Ef[j] = E0[j];
       for (int j = 0; j < 3; ++j) rf[j] = r0[j];
       const int jb = M.b_foot[leg] - 1;
-      for (int i = jb - 2; i <= jb; ++i) compose(E[i], r[i], Ef, rf);
-      const V3D rb = mk3D(rf[0], rf[1], rf[2]);
-      const V3D pf = add3(rb, mulT3(Ef, mk3D(M.foot_r[leg][0], M.foot_r[leg][1], M.foot_r[leg][2])));
-      const V3D fw = mk3D(f_foot[3 * leg], f_foot[3 * leg + 1], f_foot[3 * leg + 2]);
-      const V3D nb = crs3(sub3(pf, rb), fw);
-      fvp[jb].a = sub3(fvp[jb].a, mul3(Ef, nb)); fvp[jb].l = sub3(fvp[jb].l, mul3(Ef, fw));
+      for (int i = jb - 2; i <= jb; ++i) plux_compose(E[i], r[i], Ef, rf);
+      const SV<Dual> fe = foot_force(Ef, rf, M.foot_r[leg], f_foot + 3 * leg);
+      fvp[jb].a = sub3(fvp[jb].a, fe.a); fvp[jb].l = sub3(fvp[jb].l, fe.l);
     }
   }
   for (int i = RB_NB - 1; i >= 0; --i) {
@@ -399,52 +399,41 @@ __device__ void rnea_tangent(const RbdModel& M, const double* q, const double* q
 // the next one starts; the base chain's transforms are formed again on the way back instead of being kept.  Same operations in the same order per
 // body as rnea_tangent: the results agree to rounding.
 __device__ void rnea_tangent_quad(const RbdModel& M, const double* q, const double* qd, const double* qdd, const double* f_foot, int dir, double* dtau) {
-  SVD fb[6], v, a;
+  SV<Dual> fb[6], v, a;
   Dual E0[9], r0[3];
 #pragma unroll
   for (int j = 0; j < 9; ++j) E0[j] = D_((j % 4 == 0) ? 1.0 : 0.0);
   r0[0] = r0[1] = r0[2] = D_(0.0);
-  auto compose = [](const Dual* Eu, const Dual* ru, Dual* Ea, Dual* ra) {
-    const V3D t = mulT3(Ea, mk3D(ru[0], ru[1], ru[2]));
-    Dual En[9];
-#pragma unroll
-    for (int aa = 0; aa < 3; ++aa)
-#pragma unroll
-      for (int bb = 0; bb < 3; ++bb) En[3 * aa + bb] = Eu[3 * aa] * Ea[bb] + Eu[3 * aa + 1] * Ea[3 + bb] + Eu[3 * aa + 2] * Ea[6 + bb];
-#pragma unroll
-    for (int j = 0; j < 9; ++j) Ea[j] = En[j];
-    ra[0] = ra[0] + t.x; ra[1] = ra[1] + t.y; ra[2] = ra[2] + t.z;
-  };
   // ---- base chain, forward
 #pragma unroll
   for (int i = 0; i < 6; ++i) {
     Dual E[9], r[3];
     const Dual qi = D_(q[i], dir == i ? 1.0 : 0.0), qdi = D_(qd[i], dir == RB_NB + i ? 1.0 : 0.0);
     joint_xform(M.jtype[i], qi, M.E[i], M.r[i], E, r);
-    const SVD vJ = sunit(M.jtype[i], qdi), aJ = sunit(M.jtype[i], D_(qdd[i]));
+    const SV<Dual> vJ = sunit(M.jtype[i], qdi), aJ = sunit(M.jtype[i], D_(qdd[i]));
     if (i == 0) {
-      SVD g; g.a = mk3D(0.0, 0.0, 0.0); g.l = mk3D(0.0, 0.0, 9.81);
+      SV<Dual> g; g.a = mk3(D_(0.0), D_(0.0), D_(0.0)); g.l = mk3(D_(0.0), D_(0.0), D_(9.81));
       v = vJ; a = addS(xmotion(E, r, g), aJ);
     } else {
-      const SVD vn = addS(xmotion(E, r, v), vJ);
+      const SV<Dual> vn = addS(xmotion(E, r, v), vJ);
       a = addS(addS(xmotion(E, r, a), crm_mul(vn, vJ)), aJ);
       v = vn;
     }
     fb[i] = addS(inertia_mul(M.m[i], M.h[i], M.I[i], a), crf_mul(v, inertia_mul(M.m[i], M.h[i], M.I[i], v)));
-    if (f_foot) compose(E, r, E0, r0);
+    if (f_foot) plux_compose(E, r, E0, r0);
   }
   // ---- the four legs, one after the other
 #pragma unroll 1
   for (int leg = 0; leg < 4; ++leg) {
     Dual El[3][9], rl[3][3];
-    SVD fl[3], vv = v, aa = a;
+    SV<Dual> fl[3], vv = v, aa = a;
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       const int i = 6 + 3 * leg + j;
       const Dual qi = D_(q[i], dir == i ? 1.0 : 0.0), qdi = D_(qd[i], dir == RB_NB + i ? 1.0 : 0.0);
       joint_xform(M.jtype[i], qi, M.E[i], M.r[i], El[j], rl[j]);
-      const SVD vJ = sunit(M.jtype[i], qdi), aJ = sunit(M.jtype[i], D_(qdd[i]));
-      const SVD vn = addS(xmotion(El[j], rl[j], vv), vJ);
+      const SV<Dual> vJ = sunit(M.jtype[i], qdi), aJ = sunit(M.jtype[i], D_(qdd[i]));
+      const SV<Dual> vn = addS(xmotion(El[j], rl[j], vv), vJ);
       aa = addS(addS(xmotion(El[j], rl[j], aa), crm_mul(vn, vJ)), aJ);
       vv = vn;
       fl[j] = addS(inertia_mul(M.m[i], M.h[i], M.I[i], aa), crf_mul(vv, inertia_mul(M.m[i], M.h[i], M.I[i], vv)));
@@ -456,12 +445,9 @@ __device__ void rnea_tangent_quad(const RbdModel& M, const double* q, const doub
 #pragma unroll
       for (int j = 0; j < 3; ++j) rf[j] = r0[j];
 #pragma unroll
-      for (int j = 0; j < 3; ++j) compose(El[j], rl[j], Ef, rf);
-      const V3D rb = mk3D(rf[0], rf[1], rf[2]);
-      const V3D pf = add3(rb, mulT3(Ef, mk3D(M.foot_r[leg][0], M.foot_r[leg][1], M.foot_r[leg][2])));
-      const V3D fw = mk3D(f_foot[3 * leg], f_foot[3 * leg + 1], f_foot[3 * leg + 2]);
-      const V3D nb = crs3(sub3(pf, rb), fw);
-      fl[2].a = sub3(fl[2].a, mul3(Ef, nb)); fl[2].l = sub3(fl[2].l, mul3(Ef, fw));
+      for (int j = 0; j < 3; ++j) plux_compose(El[j], rl[j], Ef, rf);
+      const SV<Dual> fe = foot_force(Ef, rf, M.foot_r[leg], f_foot + 3 * leg);
+      fl[2].a = sub3(fl[2].a, fe.a); fl[2].l = sub3(fl[2].l, fe.l);
     }
 #pragma unroll
     for (int j = 2; j >= 0; --j) {
@@ -542,25 +528,16 @@ __global__ void __launch_bounds__(64) landing_kinodyn_rows_kernel(KdArgs a) {
   const RbdModel& M = *a.model;
   const double* q6 = a.q6 + (size_t)pt * 6; const double* jp = a.jpos + (size_t)pt * 12;
   double E0[9], r0[3];
-  for (int j = 0; j < 9; ++j) E0[j] = (j % 4 == 0) ? 1.0 : 0.0;
-  r0[0] = r0[1] = r0[2] = 0.0;
-  auto compose = [](const double* Eu, const double* ru, double* Ea, double* ra) {
-    const V3d t = mulT3(Ea, mk3(ru[0], ru[1], ru[2]));
-    double En[9];
-    for (int x = 0; x < 3; ++x) for (int y = 0; y < 3; ++y) En[3 * x + y] = Eu[3 * x] * Ea[y] + Eu[3 * x + 1] * Ea[3 + y] + Eu[3 * x + 2] * Ea[6 + y];
-    for (int j = 0; j < 9; ++j) Ea[j] = En[j];
-    ra[0] += t.x; ra[1] += t.y; ra[2] += t.z;
-  };
   double E[9], r[3];
-  for (int i = 0; i < 6; ++i) { joint_xform(M.jtype[i], q6[i], M.E[i], M.r[i], E, r); compose(E, r, E0, r0); }
+  base_chain(M, q6, E0, r0, E, r);
   // R_world_to_body = E0 (the coordinate transform world -> body accumulated by the chain = (rx' ry' rz')')
   for (int leg = 0; leg < 4; ++leg) {
     double El[9], rl[3];
     for (int j = 0; j < 9; ++j) El[j] = E0[j];
     for (int j = 0; j < 3; ++j) rl[j] = r0[j];
     const int jb = M.b_foot[leg] - 1;
-    for (int i = jb - 2; i <= jb; ++i) { joint_xform(M.jtype[i], jp[3 * leg + (i - (jb - 2))], M.E[i], M.r[i], E, r); compose(E, r, El, rl); }
-    const V3d pf = add3(mk3(rl[0], rl[1], rl[2]), mulT3(El, mk3(M.foot_r[leg][0], M.foot_r[leg][1], M.foot_r[leg][2])));
+    for (int i = jb - 2; i <= jb; ++i) { joint_xform(M.jtype[i], jp[3 * leg + (i - (jb - 2))], M.E[i], M.r[i], E, r); plux_compose(E, r, El, rl); }
+    const V3<double> pf = add3(mk3(rl[0], rl[1], rl[2]), mulT3(El, mk3(M.foot_r[leg][0], M.foot_r[leg][1], M.foot_r[leg][2])));
     const double pfv[3] = {pf.x, pf.y, pf.z};
     for (int j = 0; j < 3; ++j) {
       if (a.fk) a.fk[(size_t)pt * 12 + 3 * leg + j] = pfv[j];
@@ -574,7 +551,7 @@ __global__ void __launch_bounds__(64) landing_kinodyn_rows_kernel(KdArgs a) {
       const double J[3][3] = {{0.0, M.l3 * c23 + M.l2 * c2, M.l3 * c23},
                               {M.l3 * c1 * c23 + M.l2 * c1 * c2 - l14 * s1 * ss, -M.l3 * s1 * s23 - M.l2 * s1 * s2, -M.l3 * s1 * s23},
                               {M.l3 * s1 * c23 + M.l2 * c2 * s1 + l14 * ss * c1, M.l3 * c1 * s23 + M.l2 * c1 * s2, M.l3 * c1 * s23}};
-      const V3d fb = mul3(E0, mk3(-a.f[(size_t)pt * 12 + 3 * leg], -a.f[(size_t)pt * 12 + 3 * leg + 1], -a.f[(size_t)pt * 12 + 3 * leg + 2]));
+      const V3<double> fb = mul3(E0, mk3(-a.f[(size_t)pt * 12 + 3 * leg], -a.f[(size_t)pt * 12 + 3 * leg + 1], -a.f[(size_t)pt * 12 + 3 * leg + 2]));
       for (int j = 0; j < 3; ++j) a.tau[(size_t)pt * 12 + 3 * leg + j] = J[0][j] * fb.x + J[1][j] * fb.y + J[2][j] * fb.z;
     }
   }
@@ -596,84 +573,7 @@ constexpr int KD_NW = 72, KD_ROWS = 141, KD_ROWS_LAST = 117, KD_BND = 48;
 __host__ __device__ inline int kd_ng(int N) { return KD_BND + (N - 1) * KD_ROWS + KD_ROWS_LAST; }
 __host__ __device__ inline int kd_nx(int N) { return 12 * (N + 1) + 12 * N + 24 * N; }
 
-__device__ __forceinline__ Dual operator/(Dual a, Dual b) { const double q = a.v / b.v; return D_(q, (a.d - q * b.d) / b.v); }
-__device__ __forceinline__ Dual operator*(Dual a, double b) { return D_(a.v * b, a.d * b); }
-__device__ __forceinline__ Dual operator+(Dual a, double b) { return D_(a.v + b, a.d); }
-__device__ __forceinline__ Dual operator-(Dual a, double b) { return D_(a.v - b, a.d); }
-__device__ __forceinline__ void sincos_t(double x, double& s, double& c) { sincos(x, &s, &c); }
-__device__ __forceinline__ void sincos_t(Dual x, Dual& s, Dual& c) { double sv, cv; sincos(x.v, &sv, &cv); s = D_(sv, cv * x.d); c = D_(cv, -sv * x.d); }
-__device__ __forceinline__ double lit(double, double v) { return v; }
-__device__ __forceinline__ Dual lit(Dual, double v) { return D_(v); }
-__device__ __forceinline__ V3D mk3(Dual x, Dual y, Dual z) { return mk3D(x, y, z); }
-template <class T> struct KdVec { typedef V3d type; };
-template <> struct KdVec<Dual> { typedef V3D type; };
-// second-order forward mode: value, two first-order parts and the mixed second-order part along directions (e_i, e_j); the same stage
-// function instantiated on this scalar gives d^2 rows / dw_i dw_j exactly (hyper-dual numbers)
-struct HDual { double v, a, b, ab; };
-__device__ __forceinline__ HDual H_(double v, double a = 0.0, double b = 0.0, double ab = 0.0) { HDual o; o.v = v; o.a = a; o.b = b; o.ab = ab; return o; }
-__device__ __forceinline__ HDual operator+(HDual x, HDual y) { return H_(x.v + y.v, x.a + y.a, x.b + y.b, x.ab + y.ab); }
-__device__ __forceinline__ HDual operator-(HDual x, HDual y) { return H_(x.v - y.v, x.a - y.a, x.b - y.b, x.ab - y.ab); }
-__device__ __forceinline__ HDual operator*(HDual x, HDual y) { return H_(x.v * y.v, x.a * y.v + x.v * y.a, x.b * y.v + x.v * y.b, x.ab * y.v + x.a * y.b + x.b * y.a + x.v * y.ab); }
-__device__ __forceinline__ HDual operator*(HDual x, double s) { return H_(x.v * s, x.a * s, x.b * s, x.ab * s); }
-__device__ __forceinline__ HDual operator*(double s, HDual x) { return H_(x.v * s, x.a * s, x.b * s, x.ab * s); }
-__device__ __forceinline__ HDual operator+(HDual x, double s) { return H_(x.v + s, x.a, x.b, x.ab); }
-__device__ __forceinline__ HDual operator-(HDual x, double s) { return H_(x.v - s, x.a, x.b, x.ab); }
-__device__ __forceinline__ HDual operator/(HDual x, HDual y) {
-  const double f = 1.0 / y.v, f1 = -f * f, f2 = -2.0 * f * f1;
-  return x * H_(f, f1 * y.a, f1 * y.b, f2 * y.a * y.b + f1 * y.ab);
-}
-__device__ __forceinline__ void sincos_t(HDual x, HDual& s, HDual& c) {
-  double sv, cv; sincos(x.v, &sv, &cv);
-  s = H_(sv, cv * x.a, cv * x.b, -sv * x.a * x.b + cv * x.ab); c = H_(cv, -sv * x.a, -sv * x.b, -cv * x.a * x.b - sv * x.ab);
-}
-__device__ __forceinline__ HDual lit(HDual, double v) { return H_(v); }
-struct V3H { HDual x, y, z; };
-__device__ __forceinline__ V3H mk3(HDual x, HDual y, HDual z) { V3H v; v.x = x; v.y = y; v.z = z; return v; }
-__device__ __forceinline__ V3H add3(V3H a, V3H b) { return mk3(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ V3H sub3(V3H a, V3H b) { return mk3(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ V3H crs3(V3H a, V3H b) { return mk3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-__device__ __forceinline__ V3H mul3(const HDual* E, V3H v) { return mk3(E[0] * v.x + E[1] * v.y + E[2] * v.z, E[3] * v.x + E[4] * v.y + E[5] * v.z, E[6] * v.x + E[7] * v.y + E[8] * v.z); }
-__device__ __forceinline__ V3H mulT3(const HDual* E, V3H v) { return mk3(E[0] * v.x + E[3] * v.y + E[6] * v.z, E[1] * v.x + E[4] * v.y + E[7] * v.z, E[2] * v.x + E[5] * v.y + E[8] * v.z); }
-template <> struct KdVec<HDual> { typedef V3H type; };
-template <int JT>
-__device__ __forceinline__ void joint_xform_t(HDual q, const double* Et, const double* rt, HDual* E, HDual* r) {
-  if (JT < 3) {
-    HDual S, Cc; sincos_t(q, S, Cc);
-    constexpr int a = JT < 3 ? JT : 0, b = (a + 1) % 3, d = (a + 2) % 3;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      E[3 * a + j] = H_(Et[3 * a + j]);
-      E[3 * b + j] = Et[3 * b + j] * Cc + Et[3 * d + j] * S;
-      E[3 * d + j] = Et[3 * d + j] * Cc - Et[3 * b + j] * S;
-    }
-    r[0] = H_(rt[0]); r[1] = H_(rt[1]); r[2] = H_(rt[2]);
-  } else {
-    constexpr int a = JT >= 3 ? JT - 3 : 0;
-#pragma unroll
-    for (int j = 0; j < 9; ++j) E[j] = H_(Et[j]);
-    r[0] = H_(rt[0]) + Et[3 * a] * q; r[1] = H_(rt[1]) + Et[3 * a + 1] * q; r[2] = H_(rt[2]) + Et[3 * a + 2] * q;
-  }
-}
-__device__ __forceinline__ void joint_xform(int jt, HDual q, const double* Et, const double* rt, HDual* E, HDual* r) {
-  switch (jt) {
-    case 0: joint_xform_t<0>(q, Et, rt, E, r); break;
-    case 1: joint_xform_t<1>(q, Et, rt, E, r); break;
-    case 2: joint_xform_t<2>(q, Et, rt, E, r); break;
-    case 3: joint_xform_t<3>(q, Et, rt, E, r); break;
-    case 4: joint_xform_t<4>(q, Et, rt, E, r); break;
-    default: joint_xform_t<5>(q, Et, rt, E, r); break;
-  }
-}
 
-
-template <class T>
-__device__ void kd_compose(const T* Eu, const T* ru, T* Ea, T* ra) {      // (Ea, ra) <- plux(Eu, ru) * plux(Ea, ra)
-  const typename KdVec<T>::type t = mulT3(Ea, mk3(ru[0], ru[1], ru[2]));
-  T En[9];
-  for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) En[3 * a + b] = Eu[3 * a] * Ea[b] + Eu[3 * a + 1] * Ea[3 + b] + Eu[3 * a + 2] * Ea[6 + b];
-  for (int j = 0; j < 9; ++j) Ea[j] = En[j];
-  ra[0] = ra[0] + t.x; ra[1] = ra[1] + t.y; ra[2] = ra[2] + t.z;
-}
 
 // (Ea, ra) <- plux(rot_A(q) Et, rt) * plux(Ea, ra) for a revolute joint about axis A whose sine / cosine the caller holds (the leg rows need them for the torque
 // rows anyway): t = Ea' rt and G = Et Ea cost products with the model's constants only, then two rows of G are rotated -- 12 products of T numbers instead of the 27 of
@@ -710,7 +610,7 @@ __device__ __forceinline__ void kd_rot_compose(int jt, const T& S, const T& Cc, 
 // code it put the in-kernel row evaluation of the interior-point solver at 253 VGPRs + 32 AGPRs of spill, one workgroup per CU.
 template <class T>
 __device__ __forceinline__ void kd_leg_kin(const RbdModel& M, int l, const T* w, const T* R, const T* E0, const T* r0, T* o7, T* fk3) {
-  typedef typename KdVec<T>::type V;
+  typedef V3<T> V;
   const T zero = lit(w[0], 0.0);
   const T* X = w; const T* c = w + 12; const T* f = w + 24; const T* jp = w + 36;
   const V pos = mk3(X[0], X[1], X[2]);
@@ -742,7 +642,7 @@ __device__ __forceinline__ void kd_leg_kin(const RbdModel& M, int l, const T* w,
       for (int u = 0; u < 3; ++u) {
         const int i = jb - 2 + u, jt = M.jtype[i];
         if (jt < 3) kd_rot_compose(jt, *Sj[u], *Cj[u], M.E[i], M.r[i], El, rl);      // (uniform: the model)
-        else { joint_xform(jt, jp[3 * l + u], M.E[i], M.r[i], Ej, rj); kd_compose(Ej, rj, El, rl); }
+        else { joint_xform(jt, jp[3 * l + u], M.E[i], M.r[i], Ej, rj); plux_compose(Ej, rj, El, rl); }
       }
     }
     const double fr0 = M.foot_r[l][0], fr1 = M.foot_r[l][1], fr2 = M.foot_r[l][2];      // (El' foot_r with the model's constants as plain doubles)
@@ -769,9 +669,7 @@ __device__ __noinline__ void kd_base_frames_d(const KdNlpParams& P, const RbdMod
     r0[0] = X[0]; r0[1] = X[1]; r0[2] = X[2];
   } else {
     double Ej[9], rj[3];
-    for (int j = 0; j < 9; ++j) E0[j] = (j % 4 == 0) ? 1.0 : 0.0;
-    r0[0] = r0[1] = r0[2] = 0.0;
-    for (int i = 0; i < 6; ++i) { joint_xform(M.jtype[i], X[i], M.E[i], M.r[i], Ej, rj); kd_compose(Ej, rj, E0, r0); }
+    base_chain(M, X, E0, r0, Ej, rj);
   }
 }
 
@@ -787,7 +685,7 @@ template <class T> struct KdRowArray { T* p; __device__ __forceinline__ void put
 // 0.348 against 0.335 s per batch), -1 = by P.std_base (the value paths)
 template <class T, class OUT, class WIN, int STDB = -1>
 __device__ void kd_stage_rows(const KdNlpParams& P, const RbdModel& M, int k, bool last, const WIN& w, OUT& out, int legmask = 15) {
-  typedef typename KdVec<T>::type V;
+  typedef V3<T> V;
   const T zero = lit(w[0], 0.0);
   const auto X = w + 0; const auto c = w + 12; const auto f = w + 24; const auto jp = w + 36; const auto Xn = w + 48; const auto cn = w + 60;
   const double dt = P.dt[k];
@@ -828,9 +726,10 @@ __device__ void kd_stage_rows(const KdNlpParams& P, const RbdModel& M, int k, bo
     for (int a = 0; a < 3; ++a) for (int b2 = 0; b2 < 3; ++b2) E0[3 * a + b2] = R[3 * b2 + a];
     r0[0] = pos.x; r0[1] = pos.y; r0[2] = pos.z;
   } else {
+    // (the chain inline, not base_chain: through the helper the register allocation of the non-standard-base derivative kernels changes)
     for (int j = 0; j < 9; ++j) E0[j] = lit(w[0], (j % 4 == 0) ? 1.0 : 0.0);
     r0[0] = r0[1] = r0[2] = zero;
-    for (int i = 0; i < 6; ++i) { joint_xform(M.jtype[i], X[i], M.E[i], M.r[i], Ej, rj); kd_compose(Ej, rj, E0, r0); }
+    for (int i = 0; i < 6; ++i) { joint_xform(M.jtype[i], X[i], M.E[i], M.r[i], Ej, rj); plux_compose(Ej, rj, E0, r0); }
   }
   T fkv[12];
   const double l14 = M.l1 + M.l4;
@@ -875,7 +774,7 @@ __device__ void kd_stage_rows(const KdNlpParams& P, const RbdModel& M, int k, bo
       for (int u = 0; u < 3; ++u) {
         const int i = jb - 2 + u, jt = M.jtype[i];
         if (jt < 3) kd_rot_compose(jt, *Sj[u], *Cj[u], M.E[i], M.r[i], El, rl);      // (uniform: the model)
-        else { joint_xform(jt, jp[3 * l + u], M.E[i], M.r[i], Ej, rj); kd_compose(Ej, rj, El, rl); }
+        else { joint_xform(jt, jp[3 * l + u], M.E[i], M.r[i], Ej, rj); plux_compose(Ej, rj, El, rl); }
       }
     }
     const double fr0 = M.foot_r[l][0], fr1 = M.foot_r[l][1], fr2 = M.foot_r[l][2];      // (El' foot_r with the model's constants as plain doubles)
@@ -1078,18 +977,14 @@ __global__ void __launch_bounds__(64, 1) landing_kinodyn_nlp_hess_kernel(KdNlpAr
 // landing_optimization.m:246-247 (the reference seeds its kinodynamic NLP the same way, through quadInverseKinematics / fsolve,
 // misc/inverse_kinematics.m:2).  One thread per (point, leg); res = |FK - c| after the last step.
 struct IkArgs { const RbdModel* model; int npts; const double* q6; const double* c; double* jpos; double* res; int iters; double jmin[3], jmax[3]; };
-__device__ __forceinline__ V3d leg_fk(const RbdModel& M, const double* E0, const double* r0, int leg, const double* q3) {
+__device__ __forceinline__ V3<double> leg_fk(const RbdModel& M, const double* E0, const double* r0, int leg, const double* q3) {
   double El[9], rl[3], E[9], r[3];
   for (int j = 0; j < 9; ++j) El[j] = E0[j];
   for (int j = 0; j < 3; ++j) rl[j] = r0[j];
   const int jb = M.b_foot[leg] - 1;
   for (int i = jb - 2; i <= jb; ++i) {
     joint_xform(M.jtype[i], q3[i - (jb - 2)], M.E[i], M.r[i], E, r);
-    const V3d t = mulT3(El, mk3(r[0], r[1], r[2]));
-    double En[9];
-    for (int x = 0; x < 3; ++x) for (int y = 0; y < 3; ++y) En[3 * x + y] = E[3 * x] * El[y] + E[3 * x + 1] * El[3 + y] + E[3 * x + 2] * El[6 + y];
-    for (int j = 0; j < 9; ++j) El[j] = En[j];
-    rl[0] += t.x; rl[1] += t.y; rl[2] += t.z;
+    plux_compose(E, r, El, rl);
   }
   return add3(mk3(rl[0], rl[1], rl[2]), mulT3(El, mk3(M.foot_r[leg][0], M.foot_r[leg][1], M.foot_r[leg][2])));
 }
@@ -1100,29 +995,20 @@ __global__ void __launch_bounds__(64) landing_leg_ik_kernel(IkArgs a) {
   const RbdModel& M = *a.model;
   const double* q6 = a.q6 + (size_t)pt * 6;
   double E0[9], r0[3], E[9], r[3];
-  for (int j = 0; j < 9; ++j) E0[j] = (j % 4 == 0) ? 1.0 : 0.0;
-  r0[0] = r0[1] = r0[2] = 0.0;
-  for (int i = 0; i < 6; ++i) {
-    joint_xform(M.jtype[i], q6[i], M.E[i], M.r[i], E, r);
-    const V3d t = mulT3(E0, mk3(r[0], r[1], r[2]));
-    double En[9];
-    for (int x = 0; x < 3; ++x) for (int y = 0; y < 3; ++y) En[3 * x + y] = E[3 * x] * E0[y] + E[3 * x + 1] * E0[3 + y] + E[3 * x + 2] * E0[6 + y];
-    for (int j = 0; j < 9; ++j) E0[j] = En[j];
-    r0[0] += t.x; r0[1] += t.y; r0[2] += t.z;
-  }
-  const V3d target = mk3(a.c[(size_t)pt * 12 + 3 * leg], a.c[(size_t)pt * 12 + 3 * leg + 1], a.c[(size_t)pt * 12 + 3 * leg + 2]);
+  base_chain(M, q6, E0, r0, E, r);
+  const V3<double> target = mk3(a.c[(size_t)pt * 12 + 3 * leg], a.c[(size_t)pt * 12 + 3 * leg + 1], a.c[(size_t)pt * 12 + 3 * leg + 2]);
   double q[3] = {0.0, -0.8, 1.6};
   double err = 0.0;
   for (int it = 0; it <= a.iters; ++it) {
-    const V3d e = sub3(leg_fk(M, E0, r0, leg, q), target);
+    const V3<double> e = sub3(leg_fk(M, E0, r0, leg, q), target);
     err = sqrt(e.x * e.x + e.y * e.y + e.z * e.z);
     if (it == a.iters || err < 1e-13) break;
     double J[3][3];
     const double h = 1e-6;
     for (int j = 0; j < 3; ++j) {
       const double qj = q[j];
-      q[j] = qj + h; const V3d fp = leg_fk(M, E0, r0, leg, q);
-      q[j] = qj - h; const V3d fm = leg_fk(M, E0, r0, leg, q);
+      q[j] = qj + h; const V3<double> fp = leg_fk(M, E0, r0, leg, q);
+      q[j] = qj - h; const V3<double> fm = leg_fk(M, E0, r0, leg, q);
       q[j] = qj;
       J[0][j] = (fp.x - fm.x) / (2 * h); J[1][j] = (fp.y - fm.y) / (2 * h); J[2][j] = (fp.z - fm.z) / (2 * h);
     }

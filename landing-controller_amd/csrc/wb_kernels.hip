@@ -185,15 +185,16 @@ struct WsView {
   double* base;
   __device__ __forceinline__ double& operator()(int i) const { return base[i * WB_TPB]; }
 };
-__device__ __forceinline__ SV ws_ld_sv(const WsView& W, int off, int i) { SV s; s.a = mk3(W(off + 6 * i), W(off + 6 * i + 1), W(off + 6 * i + 2)); s.l = mk3(W(off + 6 * i + 3), W(off + 6 * i + 4), W(off + 6 * i + 5)); return s; }
-__device__ __forceinline__ void ws_st_sv(const WsView& W, int off, int i, SV s) { W(off + 6 * i) = s.a.x; W(off + 6 * i + 1) = s.a.y; W(off + 6 * i + 2) = s.a.z; W(off + 6 * i + 3) = s.l.x; W(off + 6 * i + 4) = s.l.y; W(off + 6 * i + 5) = s.l.z; }
+__device__ __forceinline__ SV<double> ws_ld_sv(const WsView& W, int off, int i) { SV<double> s; s.a = mk3(W(off + 6 * i), W(off + 6 * i + 1), W(off + 6 * i + 2)); s.l = mk3(W(off + 6 * i + 3), W(off + 6 * i + 4), W(off + 6 * i + 5)); return s; }
+__device__ __forceinline__ void ws_st_sv(const WsView& W, int off, int i, SV<double> s) { W(off + 6 * i) = s.a.x; W(off + 6 * i + 1) = s.a.y; W(off + 6 * i + 2) = s.a.z; W(off + 6 * i + 3) = s.l.x; W(off + 6 * i + 4) = s.l.y; W(off + 6 * i + 5) = s.l.z; }
 __device__ __forceinline__ void ws_ld_xf(const WsView& W, int i, double* E, double* r) {
 #pragma unroll
   for (int j = 0; j < 9; ++j) E[j] = W(WS_E + 9 * i + j);
 #pragma unroll
   for (int j = 0; j < 3; ++j) r[j] = W(WS_R + 3 * i + j);
 }
-// H -> W(WS_H + 18 i + j), C -> W(WS_C + i); q = W(WS_X + i), qd = W(WS_X + 18 + i)   (hand_c of rbd_kernels.hip, line for line)
+// H -> W(WS_H + 18 i + j), C -> W(WS_C + i); q = W(WS_X + i), qd = W(WS_X + 18 + i).  The recursion of hand_c (rbd_kernels.hip) on the LDS arrays: the
+// algebra, plux_compose and foot_force are shared, the per-body order of operations is hand_c's
 __device__ void hand_c_lds(const RbdModel& M, const double* f_foot, const WsView& W) {
   double Ei[9], ri[3];
   for (int i = 0; i < RB_NB; ++i) {
@@ -202,57 +203,48 @@ __device__ void hand_c_lds(const RbdModel& M, const double* f_foot, const WsView
     for (int j = 0; j < 9; ++j) W(WS_E + 9 * i + j) = Ei[j];
 #pragma unroll
     for (int j = 0; j < 3; ++j) W(WS_R + 3 * i + j) = ri[j];
-    const SV vJ = sunit(M.jtype[i], W(WS_X + 18 + i));
+    const SV<double> vJ = sunit(M.jtype[i], W(WS_X + 18 + i));
     const int pa = M.parent[i];
-    SV vi, ai;
+    SV<double> vi, ai;
     if (pa == 0) {
-      SV g; g.a = mk3(0, 0, 0); g.l = mk3(0, 0, 9.81);
+      SV<double> g; g.a = mk3(0.0, 0.0, 0.0); g.l = mk3(0.0, 0.0, 9.81);
       vi = vJ; ai = xmotion(Ei, ri, g);
     } else {
-      const SV vp = xmotion(Ei, ri, ws_ld_sv(W, WS_V, pa - 1));
+      const SV<double> vp = xmotion(Ei, ri, ws_ld_sv(W, WS_V, pa - 1));
       vi.a = add3(vp.a, vJ.a); vi.l = add3(vp.l, vJ.l);
-      const SV ap = xmotion(Ei, ri, ws_ld_sv(W, WS_U, pa - 1)), cv = crm_mul(vi, vJ);
+      const SV<double> ap = xmotion(Ei, ri, ws_ld_sv(W, WS_U, pa - 1)), cv = crm_mul(vi, vJ);
       ai.a = add3(ap.a, cv.a); ai.l = add3(ap.l, cv.l);
     }
     ws_st_sv(W, WS_V, i, vi); ws_st_sv(W, WS_U, i, ai);
-    const SV Ia = inertia_mul(M.m[i], M.h[i], M.I[i], ai), Iv = inertia_mul(M.m[i], M.h[i], M.I[i], vi), cf = crf_mul(vi, Iv);
-    SV fi; fi.a = add3(Ia.a, cf.a); fi.l = add3(Ia.l, cf.l);
+    const SV<double> Ia = inertia_mul(M.m[i], M.h[i], M.I[i], ai), Iv = inertia_mul(M.m[i], M.h[i], M.I[i], vi), cf = crf_mul(vi, Iv);
+    SV<double> fi; fi.a = add3(Ia.a, cf.a); fi.l = add3(Ia.l, cf.l);
     ws_st_sv(W, WS_F, i, fi);
   }
   if (f_foot) {
     double E0[9], r0[3];
     for (int j = 0; j < 9; ++j) E0[j] = (j % 4 == 0) ? 1.0 : 0.0;
     r0[0] = r0[1] = r0[2] = 0.0;
-    auto compose = [](const double* Eu, const double* ru, double* Ea, double* ra) {
-      const V3d t = mulT3(Ea, mk3(ru[0], ru[1], ru[2]));
-      double En[9];
-      for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) En[3 * a + b] = Eu[3 * a] * Ea[b] + Eu[3 * a + 1] * Ea[3 + b] + Eu[3 * a + 2] * Ea[6 + b];
-      for (int j = 0; j < 9; ++j) Ea[j] = En[j];
-      ra[0] += t.x; ra[1] += t.y; ra[2] += t.z;
-    };
-    for (int i = 0; i < 6; ++i) { ws_ld_xf(W, i, Ei, ri); compose(Ei, ri, E0, r0); }
+    for (int i = 0; i < 6; ++i) { ws_ld_xf(W, i, Ei, ri); plux_compose(Ei, ri, E0, r0); }
     for (int leg = 0; leg < 4; ++leg) {
       double El[9], rl[3];
       for (int j = 0; j < 9; ++j) El[j] = E0[j];
       for (int j = 0; j < 3; ++j) rl[j] = r0[j];
       const int jb = M.b_foot[leg] - 1;
-      for (int i = jb - 2; i <= jb; ++i) { ws_ld_xf(W, i, Ei, ri); compose(Ei, ri, El, rl); }
-      const V3d pf = add3(mk3(rl[0], rl[1], rl[2]), mulT3(El, mk3(M.foot_r[leg][0], M.foot_r[leg][1], M.foot_r[leg][2])));
-      const V3d fw = mk3(f_foot[3 * leg], f_foot[3 * leg + 1], f_foot[3 * leg + 2]);
-      const V3d nb = crs3(sub3(pf, mk3(rl[0], rl[1], rl[2])), fw);
-      SV fj = ws_ld_sv(W, WS_F, jb);
-      fj.a = sub3(fj.a, mul3(El, nb)); fj.l = sub3(fj.l, mul3(El, fw));
+      for (int i = jb - 2; i <= jb; ++i) { ws_ld_xf(W, i, Ei, ri); plux_compose(Ei, ri, El, rl); }
+      const SV<double> fe = foot_force(El, rl, M.foot_r[leg], f_foot + 3 * leg);
+      SV<double> fj = ws_ld_sv(W, WS_F, jb);
+      fj.a = sub3(fj.a, fe.a); fj.l = sub3(fj.l, fe.l);
       ws_st_sv(W, WS_F, jb, fj);
     }
   }
   for (int i = RB_NB - 1; i >= 0; --i) {
-    const SV fi = ws_ld_sv(W, WS_F, i);
+    const SV<double> fi = ws_ld_sv(W, WS_F, i);
     W(WS_C + i) = sdot(M.jtype[i], fi);
     const int pa = M.parent[i];
     if (pa != 0) {
       ws_ld_xf(W, i, Ei, ri);
-      const SV t = xforceT(Ei, ri, fi);
-      SV fp = ws_ld_sv(W, WS_F, pa - 1);
+      const SV<double> t = xforceT(Ei, ri, fi);
+      SV<double> fp = ws_ld_sv(W, WS_F, pa - 1);
       fp.a = add3(fp.a, t.a); fp.l = add3(fp.l, t.l);
       ws_st_sv(W, WS_F, pa - 1, fp);
     }
@@ -265,8 +257,8 @@ __device__ void hand_c_lds(const RbdModel& M, const double* f_foot, const WsView
     if (pa == 0) continue;
     ws_ld_xf(W, i, Ei, ri);
     const double cmi = W(CM + i);
-    const V3d hp = mulT3(Ei, mk3(W(CH + 3 * i), W(CH + 3 * i + 1), W(CH + 3 * i + 2))), rr = mk3(ri[0], ri[1], ri[2]);
-    const V3d hn = add3(hp, scl3(cmi, rr));
+    const V3<double> hp = mulT3(Ei, mk3(W(CH + 3 * i), W(CH + 3 * i + 1), W(CH + 3 * i + 2))), rr = mk3(ri[0], ri[1], ri[2]);
+    const V3<double> hn = add3(hp, scl3(cmi, rr));
     double T[9];
     { double I6[6];
       for (int j = 0; j < 6; ++j) I6[j] = W(CI + 6 * i + j);
@@ -275,7 +267,7 @@ __device__ void hand_c_lds(const RbdModel& M, const double* f_foot, const WsView
       for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) A[3 * a + b] = Is[3 * a] * Ei[b] + Is[3 * a + 1] * Ei[3 + b] + Is[3 * a + 2] * Ei[6 + b];
       for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) T[3 * a + b] = Ei[a] * A[b] + Ei[3 + a] * A[3 + b] + Ei[6 + a] * A[6 + b];
     }
-    auto add_ss = [&](V3d a, V3d b, double sgn) {
+    auto add_ss = [&](V3<double> a, V3<double> b, double sgn) {
       const double d = a.x * b.x + a.y * b.y + a.z * b.z;
       const double av[3] = {a.x, a.y, a.z}, bv[3] = {b.x, b.y, b.z};
       for (int x = 0; x < 3; ++x) for (int y = 0; y < 3; ++y) T[3 * x + y] += sgn * (bv[x] * av[y] - (x == y ? d : 0.0));
@@ -290,7 +282,7 @@ __device__ void hand_c_lds(const RbdModel& M, const double* f_foot, const WsView
     double hh[3], II[6];
     for (int j = 0; j < 3; ++j) hh[j] = W(CH + 3 * i + j);
     for (int j = 0; j < 6; ++j) II[j] = W(CI + 6 * i + j);
-    SV fh = inertia_mul(W(CM + i), hh, II, sunit(M.jtype[i], 1.0));
+    SV<double> fh = inertia_mul(W(CM + i), hh, II, sunit(M.jtype[i], 1.0));
     W(WS_H + i * RB_NB + i) = sdot(M.jtype[i], fh);
     int j = i;
     while (M.parent[j] > 0) {
@@ -304,19 +296,9 @@ __device__ void hand_c_lds(const RbdModel& M, const double* f_foot, const WsView
 }
 // chol_solve18 on W(WS_H ..), W(WS_RHS ..)
 __device__ bool chol_solve18_lds(const WsView& W) {
-  for (int j = 0; j < RB_NB; ++j) {
-    double d = W(WS_H + j * RB_NB + j);
-    for (int k = 0; k < j; ++k) { const double l = W(WS_H + j * RB_NB + k); d -= l * l; }
-    if (!(d > 0.0)) return false;
-    d = sqrt(d); W(WS_H + j * RB_NB + j) = d;
-    for (int i = j + 1; i < RB_NB; ++i) {
-      double s = W(WS_H + i * RB_NB + j);
-      for (int k = 0; k < j; ++k) s -= W(WS_H + i * RB_NB + k) * W(WS_H + j * RB_NB + k);
-      W(WS_H + i * RB_NB + j) = s / d;
-    }
-  }
-  for (int i = 0; i < RB_NB; ++i) { double s = W(WS_RHS + i); for (int k = 0; k < i; ++k) s -= W(WS_H + i * RB_NB + k) * W(WS_RHS + k); W(WS_RHS + i) = s / W(WS_H + i * RB_NB + i); }
-  for (int i = RB_NB - 1; i >= 0; --i) { double s = W(WS_RHS + i); for (int k = i + 1; k < RB_NB; ++k) s -= W(WS_H + k * RB_NB + i) * W(WS_RHS + k); W(WS_RHS + i) = s / W(WS_H + i * RB_NB + i); }
+  const auto H = [&](int i) -> double& { return W(WS_H + i); };
+  if (!chol_factor18(H)) return false;
+  chol_subst18(H, [&](int i) -> double& { return W(WS_RHS + i); });
   return true;
 }
 // The joint-space inertia of the quadruped is block-arrow: the six base coordinates couple with everything, the 3 x 3 blocks of the four
