@@ -682,6 +682,69 @@ int landing_kinodyn_casadi_eval_host(landing_ctx* ctx, int N, const double* x, c
                                      double* f, double* g, double* grad_f, double* jac, double* hess, double* grad_gamma_x, double* grad_gamma_p);
 void landing_kinodyn_casadi_release(landing_ctx* ctx);
 
+/* ---- the drop-state chain: SRBM solve -> kinodynamic refinement -> warm re-solve, on the device ---------------------------------------------
+ * What every production caller of the reference runs per drop state (generate_data/generate_training_data_automated.m:121-219, main_scripts/
+ * landing_optimization.m:300-322,360-435): the SRBM solve; its [X*; U*] with the constant joint-angle guess seeds the kinodynamic solve of the function
+ * generate_landingCtrller_KNITRO.m builds; that solution seeds the `_ws` re-solve; the training pair [rpy0; qd0] -> [X*; U*; jpos*] is stored.  Here the
+ * hand-offs are kernels (csrc/pipeline_kernels.hip) and the chain is one call per batch; no member array leaves the device between the passes.
+ *   landing_pipeline_opts          by value: the three passes' options (defaults landing_solver_opts_default, landing_kinodyn_solver_opts_default,
+ *                                  landing_kinodyn_solver_opts_warm), the constraint literals (landing_kinodyn_form_knitro), the joint limits
+ *                                  (landing_optimization.m:246-247), the joint-angle guess (0, -pi/4, pi/2) per leg (:142); warm = 0 stops after the refinement.
+ *   landing_kinodyn_pose_batch     member b's refinement problem from its SRBM p and x*: d_lbg, d_ubg [B][ng] (row order of landing_kinodyn_bounds;
+ *                                  q_init, qd_init, q_min(3), q_term_*, qd_term_*, l_leg_max from p, c_init and the kinematic box from q_init / qd_init),
+ *                                  d_cost [B][24] = QN | Xref(:, end) from p, d_x0 [B][48N+12] = [X*; jpos_guess; U*].
+ *   landing_training_pairs_batch   the members with d_status_final == 0, compacted in member order: d_in [B][9] = [q_init(4:6); qd_init],
+ *                                  d_out [B][48N+12] = [X(:); U(:); jpos(:)] (generate_training_data_automated.m:204-219), d_index [B] = member of each
+ *                                  column (-1 behind the last), *d_count = number of columns; only the first *d_count columns are written.
+ *   landing_pipeline_refine_batch  pose, refinement (landing_kinodyn_solve_batch, opts->refine), re-solve from its x with the same bounds and cost
+ *                                  (opts->resolve, warm = 1), the final choice per member, the pairs.  d_x [B][48N+12], d_f [B], d_lam_g [B][ng] (may be
+ *                                  NULL), d_kkt [B][3]: the final result = the re-solve's if it converged, else the refinement's if that converged, else
+ *                                  the re-solve's (warm = 0: the refinement's).  d_status / d_iters [B][3]: one column per pass, SRBM | refinement | re-solve
+ *                                  (SRBM column from d_srbm_status / d_srbm_iters, -1 / 0 when those are NULL; re-solve column -1 / 0 when warm = 0).
+ *                                  Final status = landing_pipeline_final_status(refinement, re-solve).  The pair outputs go together or are all NULL.
+ *                                  dt, mass, Ib, Ib_inv, mu are read from member 0's p (one small device-to-host read); LANDING_E_ARG before any solve when
+ *                                  another member's differ, for contexts without a model, with run_cost != 0 or N > 64.  Every member is refined whatever
+ *                                  its SRBM status.  Intermediate arrays live in blocks of the context grown on demand; the only host reads are those
+ *                                  scalars and the solver's 4-byte counts of members still iterating.
+ *   landing_pipeline_batch         landing_solve_batch (opts->srbm) + the call above on one stream; d_x_srbm [B][36N+12] receives the SRBM solutions
+ *                                  (may be NULL).
+ *   landing_pipeline_21            B drop states in one call: the 21 arguments of landing_solve_21 (host, column-major, trailing batch axis); status /
+ *                                  iters [3 x B], kkt [3 x B], x [(48N+12) x B], f [B], lam_g [ng x B] (may be NULL); pair_in [9 x B], pair_out
+ *                                  [(48N+12) x B] valid for the first *n_kept columns (either may be NULL).                                          */
+typedef struct {
+  landing_solver_opts srbm, refine, resolve;
+  landing_kinodyn_form form;
+  double jpos_min[12], jpos_max[12], jpos_guess[3];
+  int warm;
+} landing_pipeline_opts;
+void landing_pipeline_opts_default(landing_pipeline_opts* o);
+int landing_pipeline_final_status(int refine_status, int resolve_status /* -1: not run */);
+int landing_kinodyn_pose_batch(landing_ctx* ctx, int B, const double* d_p, const double* d_x_srbm, const landing_pipeline_opts* opts,
+                               double* d_lbg, double* d_ubg, double* d_cost, double* d_x0, void* stream);
+int landing_training_pairs_batch(landing_ctx* ctx, int B, const double* d_p, const double* d_x_kd, const int* d_status_final,
+                                 double* d_in, double* d_out, int* d_index, int* d_count, void* stream);
+int landing_pipeline_refine_batch(landing_ctx* ctx, int B, const double* d_p, const double* d_x_srbm, const int* d_srbm_status, const int* d_srbm_iters,
+                                  const landing_pipeline_opts* opts, double* d_x, double* d_f, double* d_lam_g, int* d_status, int* d_iters, double* d_kkt,
+                                  double* d_in, double* d_out, int* d_index, int* d_count, void* stream);
+int landing_pipeline_batch(landing_ctx* ctx, int B, const double* d_p, const double* d_x0, const landing_pipeline_opts* opts, double* d_x_srbm,
+                           double* d_x, double* d_f, double* d_lam_g, int* d_status, int* d_iters, double* d_kkt,
+                           double* d_in, double* d_out, int* d_index, int* d_count, void* stream);
+int landing_pipeline_21(landing_ctx* ctx, int B, const double* Xref, const double* Uref, const double* dt,
+                        const double* q_min, const double* q_max, const double* qd_min, const double* qd_max,
+                        const double* q_init, const double* qd_init, const double* q_term_min, const double* q_term_max,
+                        const double* qd_term_min, const double* qd_term_max, const double* QN, const double* x0,
+                        const double* mu, const double* l_leg_max, const double* f_max, const double* mass,
+                        const double* Ib, const double* Ib_inv, const landing_pipeline_opts* opts,
+                        double* x, double* f, double* lam_g, int* status, int* iters, double* kkt, double* pair_in, double* pair_out, int* n_kept);
+/* ... the same as one FFI call (matlab/landing_pipeline_mex.c): a context per (N, device) with the 'mc3D' model, cached inside the library */
+int landing_pipeline_21_on(int device, int N, int B, const double* Xref, const double* Uref, const double* dt,
+                           const double* q_min, const double* q_max, const double* qd_min, const double* qd_max,
+                           const double* q_init, const double* qd_init, const double* q_term_min, const double* q_term_max,
+                           const double* qd_term_min, const double* qd_term_max, const double* QN, const double* x0,
+                           const double* mu, const double* l_leg_max, const double* f_max, const double* mass,
+                           const double* Ib, const double* Ib_inv, const landing_pipeline_opts* opts,
+                           double* x, double* f, double* lam_g, int* status, int* iters, double* kkt, double* pair_in, double* pair_out, int* n_kept);
+
 /* ---- SQP (Gauss-Newton / iLQR) loop on the 18-DoF model (BASELINE configs[3]) --------------------------------
  * Trajectory-tracking problem per member: state x = [q; qd] (36), control u = the 12 joint torques (base unactuated), known foot
  * forces f_k, explicit Euler  q+ = q + dt qd, qd+ = qd + dt qdd(q, qd, [0; u], f)  (the discretisation of the SRBM NLP,

@@ -34,6 +34,19 @@ class SolverOpts(C.Structure):
                 ("feas_back", C.c_double), ("feas_max", C.c_int), ("feas_delta_dec", C.c_double), ("feas_ret_push", C.c_double), ("feas_ret_mu", C.c_double), ("feas_resume", C.c_int), ("feas_polish", C.c_double)]
 
 
+class KinodynForm(C.Structure):
+    """landing_kinodyn_form of include/landing_nlp.h: the literals of the kinodynamic NLP's constraint set"""
+    _fields_ = [("comp_eps", C.c_double), ("slip_eps", C.c_double), ("fk_band", C.c_double), ("kin_box_x0", C.c_double), ("kin_box_y0", C.c_double),
+                ("kin_box_y_in", C.c_double), ("kin_box_z_lo", C.c_double), ("kin_box_z_hi", C.c_double), ("tau_max", C.c_double * 3)]
+
+
+class PipelineOpts(C.Structure):
+    """landing_pipeline_opts of include/landing_nlp.h (the drop-state chain): options of the SRBM solve, the refinement and the warm re-solve, the
+    refinement's constraint literals, joint limits and joint-angle guess; warm = 0 stops after the refinement"""
+    _fields_ = [("srbm", SolverOpts), ("refine", SolverOpts), ("resolve", SolverOpts), ("form", KinodynForm),
+                ("jpos_min", C.c_double * 12), ("jpos_max", C.c_double * 12), ("jpos_guess", C.c_double * 3), ("warm", C.c_int)]
+
+
 ARGS21 = ["Xref", "Uref", "dt", "q_min", "q_max", "qd_min", "qd_max", "q_init", "qd_init", "q_term_min", "q_term_max",
           "qd_term_min", "qd_term_max", "QN", "x0", "mu", "l_leg_max", "f_max", "mass", "Ib", "Ib_inv"]
 
@@ -124,6 +137,15 @@ def load(path=None):
         lib.landing_stream_wait.argtypes = [vp, C.c_longlong, vp]
         lib.landing_stream_sync.argtypes = [vp, vp]
         lib.landing_solve_stream_host.argtypes = [vp, C.c_int, C.c_int, C.c_int, _dp, _dp, C.POINTER(SolverOpts), _dp, _dp, _dp, _ip, _ip, _dp]
+    if hasattr(lib, "landing_pipeline_batch"):      # the drop-state chain
+        po = C.POINTER(PipelineOpts)
+        lib.landing_pipeline_opts_default.argtypes = [po]
+        lib.landing_pipeline_final_status.argtypes = [C.c_int, C.c_int]
+        lib.landing_kinodyn_pose_batch.argtypes = [vp, C.c_int, vp, vp, po] + [vp] * 4 + [vp]
+        lib.landing_training_pairs_batch.argtypes = [vp, C.c_int] + [vp] * 7 + [vp]
+        lib.landing_pipeline_refine_batch.argtypes = [vp, C.c_int, vp, vp, vp, vp, po] + [vp] * 10 + [vp]
+        lib.landing_pipeline_batch.argtypes = [vp, C.c_int, vp, vp, po, vp] + [vp] * 10 + [vp]
+        lib.landing_pipeline_21.argtypes = [vp, C.c_int] + [_dp] * 21 + [po, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _ip]
     return lib
 
 

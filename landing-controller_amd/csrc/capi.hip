@@ -28,6 +28,7 @@
 #include "rbd_kernels.hip"
 #include "wb_kernels.hip"
 #include "kd_solver_kernels.hip"
+#include "pipeline_kernels.hip"
 
 using landing::Layout;
 
@@ -102,6 +103,9 @@ struct landing_ctx {
   DevBuf<unsigned char> d_kd_jpat;      // [landing::KdJPat | landing::KdCPat at kd_cpat_off]: structural non-zeros of the kinodynamic NLP's Jacobian blocks (kd_ensure_jpat, solver_capi.inc)
   DevBuf<unsigned char> d_kd_pairs; int kd_npair = 0; int rbd_std_base = 0;      // structurally non-zero pairs of a Hessian block of the kinodynamic NLP ([2][kd_npair]: i | j; solver_capi.inc, kd_ensure_pairs)
   std::mutex kdc_mu; std::map<int, std::unique_ptr<KdCasadi, KdCasadiFree>> kdc;      // CasADi face of the kinodynamic NLP per N (kd_casadi_capi.inc)
+  // drop-state chain (pipeline_capi.inc): the hand-off arrays between its passes, grown to the largest batch seen; pl_done is recorded behind every
+  // chain call (the next call, on any stream, and a re-allocation wait for it); pl_mu serialises the chain calls on one context
+  DevBuf<double> d_pl; DevBuf<int> d_pl_int; hipEvent_t pl_done = nullptr; std::mutex pl_mu;
   const double* wb_skip = nullptr;      // landing_wb_skip_taken: consumed by the next landing_wb_rollout
   int wb_semi = 0;             // integrator of the whole-body loop: 0 explicit Euler, 1 semi-implicit Euler (landing_wb_set_integrator)
   bool rbd_arrow = false;      // the model set by landing_rbd_set_model is "six base joints + four 3-joint legs on the base": H is block-arrow (wb_kernels.hip)
@@ -328,6 +332,7 @@ void landing_destroy(landing_ctx* ctx) {
   for (int i = 0; i < 2; ++i) { if (ctx->aux[i]) (void)hipStreamDestroy(ctx->aux[i]); if (ctx->ev_join[i]) (void)hipEventDestroy(ctx->ev_join[i]); }
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->scratch_done) { (void)hipEventSynchronize(ctx->scratch_done); (void)hipEventDestroy(ctx->scratch_done); }
+  if (ctx->pl_done) { (void)hipEventSynchronize(ctx->pl_done); (void)hipEventDestroy(ctx->pl_done); }
   if (ctx->host_stream) (void)hipStreamDestroy(ctx->host_stream);
   delete ctx;      // (the device blocks and the CasADi-face cache free themselves)
 }
@@ -488,3 +493,4 @@ int landing_bounds_batch(landing_ctx* ctx, int B, const double* d_p, double* d_l
 #include "stream_capi.inc"
 #include "kd_capi.inc"
 #include "kd_casadi_capi.inc"
+#include "pipeline_capi.inc"

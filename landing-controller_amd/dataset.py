@@ -3,10 +3,12 @@
 generate_data/generate_training_data_automated.m:204-219 appends, per solved drop state,
     input  column = [q_init(4:6) ; qd_init(:)]            (9 values: rpy0, omega0, v0)
     output column = [X*(:) ; U*(:) ; jpos*(:)]
-to ``training_data`` and saves it after every sample.  The SRBM stage produces X* and U*; the joint
-trajectories jpos* come from the KNITRO kinodynamic refinement (out of scope), so they are optional here
-and the block is simply absent when not given.  Members whose status is not CONVERGED are skipped, as
-the interactive "Save trajectory for training?" prompt of the reference would.
+to ``training_data`` and saves it after every sample.  The SRBM stage alone produces X* and U* (pairs without
+the jpos* block); the joint trajectories jpos* come from the kinodynamic refinement and its warm re-solve,
+which the library chains behind the SRBM solve on the device (pipeline.RefineChain, include/landing_nlp.h
+landing_pipeline_*): ``generate_streamed(..., refine=True)`` writes [X*; U*; jpos*] shards as the reference
+does.  Members whose status is not CONVERGED are skipped, as the interactive "Save trajectory for training?"
+prompt of the reference would.
 """
 import numpy as np
 
@@ -133,14 +135,18 @@ def write_member_log(path, status, iters, kkt, f=None, extra=None):
             fh.write(json.dumps(rec) + "\n")
 
 
-def generate_streamed(N, n_batches, B, shard_path, seed0=0, T=0.6, dt_grid="uniform", law="main", opts=None, depth=2, device=0, log_path=None, **form):
+def generate_streamed(N, n_batches, B, shard_path, seed0=0, T=0.6, dt_grid="uniform", law="main", opts=None, depth=2, device=0, log_path=None, refine=False, **form):
     """The data-generation loop of generate_data/generate_training_data_automated.m:38-219 as a STREAM of batches through one GPU (round 6): the drop states of batch i + 1 are sampled on
     the host and queued (`pipeline.BatchPipeline` over the library's landing_stream_submit / _wait: one context, `depth` launches in flight) while batch i is solved; the converged members of
     every batch that leaves the pipeline are appended to the shard in the reference's layout (training_pairs / append_shard), every member is logged (write_member_log).  Returns the
-    counts per status and the number of samples written.  Results per batch are bit-identical to one solve at a time (tests/test_gpu_dataset.py)."""
+    counts per status and the number of samples written.  Results per batch are bit-identical to one solve at a time (tests/test_gpu_dataset.py).
+    refine=True: the whole chain per batch (SRBM solve, kinodynamic refinement, warm re-solve; `opts` a pipeline options struct, default
+    landing_pipeline_opts_default), shards of [X*; U*; jpos*] -- see _generate_refined."""
     import importlib
     problem = importlib.import_module(__package__ + ".problem"); pipeline = importlib.import_module(__package__ + ".pipeline")
     consts = problem.production_constants(law) if dt_grid == "reference" else None
+    if refine:
+        return _generate_refined(problem, pipeline, consts, N, n_batches, B, shard_path, seed0, T, dt_grid, law, opts, device, log_path)
     pipe = pipeline.BatchPipeline(N, depth=depth, device=device, opts=opts, **form)
     meta, counts, written = {}, {}, 0
 
@@ -165,4 +171,60 @@ def generate_streamed(N, n_batches, B, shard_path, seed0=0, T=0.6, dt_grid="unif
             take(done)
     finally:
         pipe.close()
+    return dict(status_counts=counts, samples_written=written, batches=n_batches)
+
+
+def _generate_refined(problem, pipeline, consts, N, n_batches, B, shard_path, seed0, T, dt_grid, law, opts, device, log_path):
+    """generate_streamed(refine=True): the SRBM solve of batch i + 1 is launched on its own stream before batch i is refined on another
+    (landing_pipeline_refine_batch; its host loop synchronises its own stream only, and the SRBM solver's workspace is not the refinement's, so the
+    two overlap on the GPU).  The SRBM outputs are double-buffered; a warm-up call with one iteration per pass sizes every workspace first, so that
+    no growth (and the device-wide synchronisation it needs) lands inside the loop.  Per batch the result is bit-identical to one
+    landing_pipeline_batch call.  Shards hold input [9, M] and output [48N + 12, M] = [X*(:); U*(:); jpos*(:)]; counts are of the final status."""
+    import torch
+    chain = pipeline.RefineChain(N, device=device, opts=opts)
+    dev, o = chain.dev, chain.opts
+    f64, i32 = dict(device=dev, dtype=torch.float64), dict(device=dev, dtype=torch.int32)
+    s_srbm, s_ref = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
+    slots = [dict(xs=torch.empty(B, chain.L.nx, **f64), st=torch.empty(B, **i32), it=torch.empty(B, **i32), ev=torch.cuda.Event()) for _ in range(2)]
+    out = chain.alloc(B)
+    counts, written = {}, 0
+
+    def batch(i):
+        return problem.make_batch(B, N, T, seed=seed0 + i, consts=consts, dt_grid=dt_grid, law=law)
+
+    def launch_srbm(i, P, X0):
+        s = slots[i % 2]
+        with torch.cuda.stream(s_srbm):
+            s["P"], s["X0"] = torch.as_tensor(P, **f64), torch.as_tensor(X0, **f64)
+            chain.L.solve_device(B, s["P"].data_ptr(), s["X0"].data_ptr(), o.srbm, s["xs"].data_ptr(), d_status=s["st"].data_ptr(), d_iters=s["it"].data_ptr(),
+                                 stream=s_srbm.cuda_stream)
+            s["ev"].record(s_srbm)
+
+    try:
+        batches = {0: batch(0)}
+        w = type(o).from_buffer_copy(o)      # warm-up: the shapes of the loop, one iteration per pass
+        w.srbm.max_iter = w.refine.max_iter = w.resolve.max_iter = 1
+        with torch.cuda.stream(s_ref):
+            chain.run_device(torch.as_tensor(batches[0][0], **f64), torch.as_tensor(batches[0][1], **f64), out=out, stream=s_ref, opts=w)
+        torch.cuda.synchronize(dev)
+        launch_srbm(0, *batches[0][:2])
+        for i in range(n_batches):
+            if i + 1 < n_batches:
+                batches[i + 1] = batch(i + 1)
+                launch_srbm(i + 1, *batches[i + 1][:2])      # batch i + 1's SRBM solve runs under batch i's refinement
+            s = slots[i % 2]
+            s_ref.wait_event(s["ev"])
+            chain.refine_device(s["P"], s["xs"], s["st"], s["it"], out=out, stream=s_ref)
+            s_ref.synchronize()
+            res = chain.to_host(out)
+            batches.pop(i)
+            if res["n_kept"]:
+                written = append_shard(shard_path, res["pair_in"], res["pair_out"])
+            if log_path:
+                write_member_log(log_path, res["final_status"], res["iters"].sum(axis=1), res["kkt"], res["f"], extra={"batch": i})
+            for v in res["final_status"]:
+                counts[int(v)] = counts.get(int(v), 0) + 1
+    finally:
+        torch.cuda.synchronize(dev)
+        chain.close()
     return dict(status_counts=counts, samples_written=written, batches=n_batches)

@@ -11,6 +11,12 @@ and this class is the host-array convenience around it: uploads on a copy stream
     for P, X0 in batches:                      # numpy [B, np], [B, nx]
         done = pipe.submit(P, X0)              # returns the results of the batch that left the pipeline, or None
     for res in pipe.drain(): ...
+
+RefineChain is the drop-state chain every production caller runs (SRBM solve -> kinodynamic refinement -> warm re-solve, the training pair;
+landing_pipeline_* of include/landing_nlp.h): one context with the robot model, one library call per batch.
+
+    chain = RefineChain(N=20)
+    res = chain.run_host(P, X0)                # numpy in / out: x [B, 48N+12], status / iters [B, 3], pair_in [9, M], pair_out [48N+12, M], ...
 """
 import importlib
 from collections import deque
@@ -57,3 +63,75 @@ class BatchPipeline:
 
     def close(self):
         self.S.sync(); self.S.close(); self.lib.close()
+
+
+def final_status(status3):
+    """final status of each member from the pass columns [B, 3] = SRBM | refinement | warm re-solve (landing_pipeline_final_status): the re-solve's
+    outcome if it converged, else the refinement's if that converged, else the re-solve's; the refinement's where the re-solve did not run (-1)"""
+    s = np.asarray(status3)
+    s1, s2 = s[:, 1], s[:, 2]
+    return np.where(s2 < 0, s1, np.where((s2 == 0) | (s1 == 0), 0, s2)).astype(np.int32)
+
+
+class RefineChain:
+    """The drop-state chain on one device: a context with the 'mc3D' model (rbd.Rbd) and the library's landing_pipeline_batch /
+    landing_pipeline_refine_batch.  Device tensors in / out (run_device, refine_device: torch tensors, no host copy inside), or numpy (run_host)."""
+
+    def __init__(self, N, device=0, opts=None):
+        capi = importlib.import_module(__package__ + ".capi"); rbd = importlib.import_module(__package__ + ".rbd")
+        self.N, self.dev = N, torch.device("cuda", device)
+        self.L = capi.LandingLib(N, device=device)
+        self.R = rbd.Rbd(self.L)
+        self.opts = opts if opts is not None else self.R.pipeline_opts()
+        self.nxk, self.ngk = 48 * N + 12, 48 + 141 * (N - 1) + 117
+
+    def alloc(self, B, lam=False):
+        """output tensors of one batch"""
+        f64, i32 = dict(device=self.dev, dtype=torch.float64), dict(device=self.dev, dtype=torch.int32)
+        return dict(x=torch.empty(B, self.nxk, **f64), f=torch.empty(B, **f64), kkt=torch.empty(B, 3, **f64), status=torch.empty(B, 3, **i32),
+                    iters=torch.empty(B, 3, **i32), pair_in=torch.empty(B, 9, **f64), pair_out=torch.empty(B, self.nxk, **f64), index=torch.empty(B, **i32),
+                    count=torch.zeros(1, **i32), lam_g=torch.empty(B, self.ngk, **f64) if lam else None)
+
+    def _outs(self, o):
+        return dict(d_lam=o["lam_g"].data_ptr() if o["lam_g"] is not None else 0, d_in=o["pair_in"].data_ptr(), d_out=o["pair_out"].data_ptr(),
+                    d_index=o["index"].data_ptr(), d_count=o["count"].data_ptr())
+
+    def run_device(self, P, X0, out=None, x_srbm=None, stream=None, opts=None):
+        """landing_pipeline_batch on device tensors P [B, np], X0 [B, 36N+12]; returns the output dict (queued on `stream`, not synchronised)"""
+        B = P.shape[0]
+        out = out or self.alloc(B)
+        st = stream if stream is not None else torch.cuda.current_stream(self.dev)
+        self.R.pipeline_device(B, P.data_ptr(), X0.data_ptr(), opts or self.opts, out["x"].data_ptr(), out["f"].data_ptr(), out["status"].data_ptr(),
+                               out["iters"].data_ptr(), out["kkt"].data_ptr(), d_x_srbm=x_srbm.data_ptr() if x_srbm is not None else 0, stream=st.cuda_stream,
+                               **self._outs(out))
+        return out
+
+    def refine_device(self, P, XS, srbm_status=None, srbm_iters=None, out=None, stream=None, opts=None):
+        """landing_pipeline_refine_batch behind SRBM solutions XS [B, 36N+12] already on the device (their status / iterations fill column 0)"""
+        B = P.shape[0]
+        out = out or self.alloc(B)
+        st = stream if stream is not None else torch.cuda.current_stream(self.dev)
+        self.R.pipeline_refine_device(B, P.data_ptr(), XS.data_ptr(), opts or self.opts, out["x"].data_ptr(), out["f"].data_ptr(), out["status"].data_ptr(),
+                                      out["iters"].data_ptr(), out["kkt"].data_ptr(), d_srbm_status=srbm_status.data_ptr() if srbm_status is not None else 0,
+                                      d_srbm_iters=srbm_iters.data_ptr() if srbm_iters is not None else 0, stream=st.cuda_stream, **self._outs(out))
+        return out
+
+    @staticmethod
+    def to_host(out):
+        """device outputs -> numpy; the pairs cut to the kept columns (pair_in [9, M], pair_out [48N+12, M], index [M])"""
+        r = {k: v.cpu().numpy() for k, v in out.items() if v is not None}
+        m = int(r.pop("count")[0])
+        r.update(pair_in=r["pair_in"][:m].T.copy(), pair_out=r["pair_out"][:m].T.copy(), index=r["index"][:m].copy(), n_kept=m)
+        r["final_status"] = final_status(r["status"])
+        return r
+
+    def run_host(self, P, X0, lam=False):
+        """numpy P [B, np], X0 [B, 36N+12] -> the chain's results as numpy (one batch, synchronised)"""
+        f64 = dict(device=self.dev, dtype=torch.float64)
+        dP, dX0 = torch.as_tensor(np.ascontiguousarray(P), **f64), torch.as_tensor(np.ascontiguousarray(X0), **f64)
+        out = self.run_device(dP, dX0, out=self.alloc(P.shape[0], lam))
+        torch.cuda.synchronize(self.dev)
+        return self.to_host(out)
+
+    def close(self):
+        self.L.close()

@@ -186,6 +186,52 @@ class Rbd:
         self.L._check(rc, "landing_solve_kinodyn_24")
         return dict(x=x, f=f, lam_g=lam, status=st, iters=it, kkt=kkt)
 
+    # ---- the drop-state chain: SRBM solve -> refinement -> warm re-solve (include/landing_nlp.h landing_pipeline_*; device pointers are integers) ----
+    def pipeline_opts(self):
+        """landing_pipeline_opts_default"""
+        from .capi import PipelineOpts
+        o = PipelineOpts()
+        self.L.lib.landing_pipeline_opts_default(C.byref(o))
+        return o
+
+    def kinodyn_pose_device(self, B, d_p, d_x_srbm, d_lbg, d_ubg, d_cost, d_x0, opts=None, stream=0):
+        """landing_kinodyn_pose_batch: member b's refinement problem from its SRBM p and x*"""
+        self.L._check(self.L.lib.landing_kinodyn_pose_batch(self.L.ctx, B, d_p, d_x_srbm, C.byref(opts) if opts is not None else None, d_lbg, d_ubg, d_cost, d_x0,
+                                                            stream or None), "landing_kinodyn_pose_batch")
+
+    def training_pairs_device(self, B, d_p, d_x_kd, d_status_final, d_in, d_out, d_index, d_count, stream=0):
+        """landing_training_pairs_batch: the converged members' training columns, compacted in member order"""
+        self.L._check(self.L.lib.landing_training_pairs_batch(self.L.ctx, B, d_p, d_x_kd, d_status_final, d_in, d_out, d_index, d_count, stream or None),
+                      "landing_training_pairs_batch")
+
+    def pipeline_refine_device(self, B, d_p, d_x_srbm, opts, d_x, d_f, d_status, d_iters, d_kkt, d_lam=0, d_in=0, d_out=0, d_index=0, d_count=0,
+                               d_srbm_status=0, d_srbm_iters=0, stream=0):
+        """landing_pipeline_refine_batch: pose, refinement, warm re-solve, final choice, pairs behind SRBM solutions already on the device"""
+        n = lambda v: v or None
+        self.L._check(self.L.lib.landing_pipeline_refine_batch(self.L.ctx, B, d_p, d_x_srbm, n(d_srbm_status), n(d_srbm_iters), C.byref(opts) if opts is not None else None,
+                                                               d_x, d_f, n(d_lam), d_status, d_iters, d_kkt, n(d_in), n(d_out), n(d_index), n(d_count), n(stream)),
+                      "landing_pipeline_refine_batch")
+
+    def pipeline_device(self, B, d_p, d_x0, opts, d_x, d_f, d_status, d_iters, d_kkt, d_lam=0, d_in=0, d_out=0, d_index=0, d_count=0, d_x_srbm=0, stream=0):
+        """landing_pipeline_batch: the SRBM solve and the chain above on one stream"""
+        n = lambda v: v or None
+        self.L._check(self.L.lib.landing_pipeline_batch(self.L.ctx, B, d_p, d_x0, C.byref(opts) if opts is not None else None, n(d_x_srbm), d_x, d_f, n(d_lam),
+                                                        d_status, d_iters, d_kkt, n(d_in), n(d_out), n(d_index), n(d_count), n(stream)), "landing_pipeline_batch")
+
+    def pipeline_21(self, args, opts=None, want_lam=False):
+        """landing_pipeline_21: the 21 MATLAB-shaped SRBM arguments (batch = last axis) -> the refined, re-solved batch and its training pairs (host arrays)"""
+        from .capi import ARGS21, matlab_args21
+        a, keep, B = matlab_args21(self.L.N, args)
+        N = self.L.N; nxk, ngk = 48 * N + 12, 48 + 141 * (N - 1) + 117
+        x = np.zeros((B, nxk)); f = np.zeros(B); lam = np.zeros((B, ngk)) if want_lam else None; st = np.zeros((B, 3), np.int32); it = np.zeros((B, 3), np.int32)
+        kkt = np.zeros((B, 3)); pin = np.zeros((B, 9)); pout = np.zeros((B, nxk)); kept = C.c_int(0)
+        dp = C.POINTER(C.c_double); ip = C.POINTER(C.c_int); P = lambda v: None if v is None else v.ctypes.data_as(dp)
+        rc = self.L.lib.landing_pipeline_21(self.L.ctx, B, *[getattr(a, n) for n in ARGS21], C.byref(opts) if opts is not None else None, P(x), P(f), P(lam),
+                                            st.ctypes.data_as(ip), it.ctypes.data_as(ip), P(kkt), P(pin), P(pout), C.byref(kept))
+        self.L._check(rc, "landing_pipeline_21")
+        m = kept.value
+        return dict(x=x, f=f, lam_g=lam, status=st, iters=it, kkt=kkt, pair_in=pin[:m].T.copy(), pair_out=pout[:m].T.copy(), n_kept=m)
+
     def kinodyn_bounds(self, N, B, q_init, qd_init, c_init, q_min, q_term_min, q_term_max, qd_term_min, qd_term_max, jpos_min, jpos_max, kin_box, l_leg_max):
         """landing_kinodyn_bounds (pure host code): arrays [B, n] -> lbg, ubg [B, ng]"""
         dp = C.POINTER(C.c_double)
