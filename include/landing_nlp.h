@@ -481,7 +481,7 @@ void landing_multi_release_cached(void);
  * One launch ends with its slowest member: a batch of 1024 takes 53 ms on the 512 resident slots of an MI355X while the slots are busy for 40 ms on
  * average; with the next batch's launch in flight behind it the freed slots are refilled at once (19.2 k -> 24-25 k NLPs/s, bench.py `streamed`).
  *   landing_stream_create   `lanes` launches may be in flight (0 = 2, 1..8); lane 0 is the context itself, every further lane a child context with the
- *                           same formulation and its own solver workspace (1.1 MB per member at N = 40); each lane has its own non-blocking HIP stream
+ *                           same formulation and its own solver workspace (1.3 MB per member at N = 40); each lane has its own non-blocking HIP stream
  *   landing_stream_submit   = landing_solve_batch on the next lane (round robin), asynchronous: returns a ticket >= 0 (or a negative LANDING_E_*).
  *                           `in_stream`: the stream on which d_p / d_x0 become ready (NULL = the default stream); the caller keeps inputs and outputs of
  *                           a submission alive and untouched until it has waited for the ticket; outputs of submissions in flight must not overlap

@@ -344,7 +344,7 @@ int build_tables(const Layout& L, std::vector<int>& data, std::vector<int>& stag
 }  // namespace
 
 namespace landing {
-// One solve is in flight per context at any time: the workspace (1.1 MB per member) and the tables belong to the context,
+// One solve is in flight per context at any time: the workspace (1.3 MB per member) and the tables belong to the context,
 // not to a stream.  `done` is recorded behind every launch; the next launch makes ITS stream wait for it, and the
 // workspace is only re-allocated after the event has completed.  Callers who want several batches in flight use one
 // context per stream (tools/bench_pipeline.py).
@@ -432,7 +432,7 @@ int landing_solve_batch(landing_ctx* ctx, int B, const double* d_p, const double
   // hard-first order: pointless while every member is resident from the start (2 workgroups on each of the 256 CUs), and the
   // all-pairs ranking kernel is O(B^2) -- skipped for the huge batches of a data-generation job (ADVICE r2)
   if (o.dispatch_order && B > 512 && B <= 16384) {
-    hipLaunchKernelGGL(landing::landing_order_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, ctx->L, B, d_p, ctx->ws.d_order.get());
+    hipLaunchKernelGGL(landing::landing_order_kernel, dim3((B + landing::ORDER_THREADS - 1) / landing::ORDER_THREADS), dim3(landing::ORDER_THREADS), 0, (hipStream_t)stream, ctx->L, B, d_p, ctx->ws.d_order.get());
     A.order = ctx->ws.d_order.get();
   }
   hipLaunchKernelGGL(landing::landing_ipm_kernel, dim3(B), dim3(landing::SOLVER_THREADS), 0, (hipStream_t)stream, A);

@@ -15,6 +15,7 @@
 // reference's CCS order; the assembly into stage blocks is table driven (solver_capi.inc).
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <type_traits>
 
 #include "../../include/landing_nlp.h"
 #include "ipm_core.hpp"
@@ -67,13 +68,38 @@ constexpr int ASM_NSLOT = 512;                   // partial-sum slots of one sta
 
 // doubles of one member's block of the solver workspace (landing::SolverWorkspace, capi.hip)
 inline size_t member_stride(const Layout& L) {
-  return (size_t)4 * L.nx + (size_t)14 * L.ng + L.nnz_jac + L.nnz_hess + (size_t)L.N * RUNC + (size_t)(L.N + 1) * RIC_STRIDE + (size_t)L.N * RCG;
+  return (size_t)4 * L.nx + (size_t)20 * L.ng + L.nnz_jac + L.nnz_hess + (size_t)L.N * RUNC + (size_t)(L.N + 1) * RIC_STRIDE + (size_t)L.N * RCG;
 }
 
 // optional per-member phase timers (wall_clock64 ticks, 100 MHz) -- enabled when SolveArgs.prof != nullptr
 enum { PH_EVAL = 0, PH_ERR, PH_SIGRHO, PH_BACK, PH_FWD, PH_DUAL, PH_LS, PH_ACCEPT, PH_NFACT, PH_NTRIAL, PH_NITER, PH_NSTAGE_OK, PH_B_ASM, PH_NSTAGE, PH_B_ELIM, PH_B_POST,
        PH_COUNT = 16 };   // 11 / 13: stage eliminations that succeeded / were attempted (stage-0 foot block included)
 #define PROF_ADD(slot, tstart) do { if (SH.prof_on) { const long long n_ = (long long)wall_clock64(); if (threadIdx.x == 0) { SH.prof[slot] += (double)(n_ - (tstart)); (tstart) = n_; } } } while (0)
+
+// Host emulation only (the CPU suite's build of this file; the product is compiled by hipcc): how each accepted step of a member came about,
+// counted per member of the last launch -- landing_emu_accept_counts().  The tests use it to see that the fused first trial really is the path
+// taken by ordinary iterations and is bypassed by the others.
+enum { EMU_ACC_FAST = 0, EMU_ACC_FAST_CLIP, EMU_ACC_FIRST_REJECTED, EMU_ACC_BACKTRACK, EMU_ACC_CORR, EMU_ACC_FALLBACK, EMU_ACC_FEAS, EMU_ACC_N };
+#ifndef __HIPCC__
+constexpr int EMU_ACC_MAXB = 64;
+static int emu_acc[EMU_ACC_MAXB][EMU_ACC_N];
+#define LANDING_EMU_COUNT(m, what) do { if ((m) < EMU_ACC_MAXB) emu_acc[m][what]++; } while (0)
+// 0: the first trial pass is never fused, every step goes through the accept pass over the rows (the path every step took before the fused
+// pass existed) -- the tests run members both ways and ask for equal bits
+static int emu_fused_on = 1;
+#define LANDING_EMU_FUSED_ON (emu_fused_on != 0)
+extern "C" void landing_emu_set_fused(int on) { emu_fused_on = on; }
+// counts[EMU_ACC_N] of member m: swap accepts (without / with the clip rule in force), first trial points that were not accepted as they stood,
+// row-pass accepts behind back-tracking / with the slack correction / of the fallback step, accepts inside the feasibility phase
+extern "C" int landing_emu_accept_counts(int m, int* counts) {
+  if (m < 0 || m >= EMU_ACC_MAXB || !counts) return -1;
+  for (int i = 0; i < EMU_ACC_N; ++i) counts[i] = emu_acc[m][i];
+  return 0;
+}
+#else
+#define LANDING_EMU_COUNT(m, what) ((void)0)
+#define LANDING_EMU_FUSED_ON true
+#endif
 
 struct SolveArgs {
   Layout L; int B; landing_solver_opts o; double* prof;
@@ -92,7 +118,17 @@ struct MemberMem {
   double *g, *gt, *s, *ds, *zL, *zU, *y, *yn, *sig, *rho;
   double *J, *H, *Hc, *ric, *cond;
   double *en, *ep, *wn, *wp;      // feasibility phase: violation variables of the lower / upper side of every inequality row and their multipliers
+  // shadow instance of the iterate's row arrays: the first trial pass of the line search writes the accepted point's values here, and accepting
+  // that point swaps the instances (mem_accept_swap); g / gt and x / xt are pairs of the same kind
+  // RULE for every pass that writes row arrays: the entries the fused first-trial pass never writes -- rows 0..11 of y / sigma / rho and s / zL / zU of
+  // the equality rows (lb == ub) -- must hold the SAME value in both instances at every swap (they are zero from the start: ipm_init_row, el_init_row);
+  // a pass that wrote one of them in the live instance alone would change results after an odd number of swaps.  The emulation build checks this at
+  // every swap (landing_ipm_kernel).
+  double *sig2, *rho2, *s2, *zL2, *zU2, *y2;
 };
+constexpr int MEMBER_MEM_PTRS = 29;
+static_assert(sizeof(MemberMem) == MEMBER_MEM_PTRS * sizeof(double*) && std::is_standard_layout<MemberMem>::value && std::is_trivially_copyable<MemberMem>::value,
+              "live_mem() walks MemberMem as an array of double*: nothing but double* members");
 
 __device__ __forceinline__ MemberMem carve(const Layout& L, double* w) {
   MemberMem M;
@@ -102,8 +138,20 @@ __device__ __forceinline__ MemberMem carve(const Layout& L, double* w) {
   M.y = w; w += L.ng; M.yn = w; w += L.ng;
   M.sig = w; w += L.ng; M.rho = w; w += L.ng;
   M.J = w; w += L.nnz_jac; M.H = w; w += L.nnz_hess; M.Hc = w; w += (size_t)L.N * RUNC; M.ric = w; w += (size_t)(L.N + 1) * RIC_STRIDE; M.cond = w; w += (size_t)L.N * RCG;
-  M.en = w; w += L.ng; M.ep = w; w += L.ng; M.wn = w; w += L.ng; M.wp = w;
+  M.en = w; w += L.ng; M.ep = w; w += L.ng; M.wn = w; w += L.ng; M.wp = w; w += L.ng;
+  M.sig2 = w; w += L.ng; M.rho2 = w; w += L.ng;      // ([sigma | rho] adjacent as in the first instance, and not at the end of the block: asm_issue reads up to 24 doubles behind rho)
+  M.s2 = w; w += L.ng; M.zL2 = w; w += L.ng; M.zU2 = w; w += L.ng; M.y2 = w;
   return M;
+}
+
+// Accepting the point the fused first-trial pass prepared: the shadow instance of (s, zL, zU, y, sigma, rho) becomes the live one, and so do
+// gt and xt.  What that pass does not write is the same in both instances from the start (rows 0..11, s / zL / zU of equality rows: zero).
+__host__ __device__ __forceinline__ void mem_accept_swap(MemberMem& M) {
+  double* t;
+#define LANDING_SWAP(a, b) t = M.a; M.a = M.b; M.b = t
+  LANDING_SWAP(s, s2); LANDING_SWAP(zL, zL2); LANDING_SWAP(zU, zU2); LANDING_SWAP(y, y2); LANDING_SWAP(sig, sig2); LANDING_SWAP(rho, rho2);
+  LANDING_SWAP(g, gt); LANDING_SWAP(x, xt);
+#undef LANDING_SWAP
 }
 
 // Scalar state of the interior-point loop, kept in LDS (S.ks: the fields both solvers keep, ipm_core.hpp IpmCtl) and never in registers
@@ -124,7 +172,7 @@ struct Lds {
                               // Ex (24 x ES): col 0 = gamma_u -> z, cols 1.. = I -> unit-lower inverse
   double Ah[2 * 12 * YS];      // A^ of the stage being eliminated and of the one being assembled (copy k & 1 belongs to stage k)
   double gam[48], pv[24], q[24], bv[2 * 12], sig[24], w[48], dinv[24];
-  double red[(SOLVER_THREADS / 64) * 6];
+  double red[(SOLVER_THREADS / 64) * 9];      // (the fused first-trial pass reduces 3 line-search sums + 6 quantities of the new point at once)
   double filt_th[FILT_CAP], filt_ph[FILT_CAP];
   double prof[32];
   int flag;
@@ -147,12 +195,31 @@ struct Lds {
   // control fields of this solver alone (written like ks): clip_k rule in force; jam_clip (landing_nlp.h): iterations in a row with a tiny step
   // to the boundary; what the stop test decided (ACT_*); no regularisation made the last step computable
   int clip_now, jamrun, action, fact_failed;
+  // fused first trial of the line search (interior-point mode): first_trial = the next trial point is the first of its iteration; fast = it was
+  // accepted as it stands, so accepting is a swap of instances; nxt = errors / sums of that point (what the accept pass leaves in ks.c_*)
+  int first_trial, fast;
+  double nxt[6];
   unsigned long long atab_mid[ATAB_LTMAX * SOLVER_THREADS];      // (behind everything the tables address: their offsets are 16 bits)
   unsigned long long acomb_mid[SOLVER_THREADS];
 };
 // One instance per workgroup (= per NLP).  Namespace scope keeps the LDS address space visible to every
 // phase function (ds_* instructions instead of flat_*).
 __shared__ Lds SH;
+// The member's arrays as they are NOW (the accept step swaps instances, so no phase keeps these pointers across iterations): SH.M by value,
+// every pointer moved to scalar registers -- they are the same for all lanes, and the row passes then address with scalar base + lane offset.
+__device__ __forceinline__ MemberMem live_mem() {
+  MemberMem M = SH.M;
+#if defined(__HIP_DEVICE_COMPILE__)
+  double** q = reinterpret_cast<double**>(&M);
+#pragma unroll
+  for (int i = 0; i < MEMBER_MEM_PTRS; ++i) {
+    const unsigned long long a = (unsigned long long)q[i];
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(a >> 32));
+    q[i] = (double*)((unsigned long long)lo | ((unsigned long long)hi << 32));
+  }
+#endif
+  return M;
+}
 // Packed terms of the assembly tables, with every place given as a BYTE OFFSET inside the LDS block (the host builds the tables with
 // offsetof: solver_capi.inc): value = [pa] * [pb] * [pc], summed into the open PIECE of a destination and stored to [d] (+ the
 // distance to the second copy of A^ when `ah` is set and the stage's copy is 1); the sum restarts behind the store unless `keep`
@@ -613,6 +680,7 @@ __device__ __noinline__ bool riccati_backward(double delta) {
   const int N = L.N, lane = threadIdx.x, NT = blockDim.x;
   (void)p; (void)N; (void)lane; (void)NT;
   bool ok = true;
+  int n_try = 0;      // stage eliminations attempted in this sweep (all but the last one succeeded, and that one iff ok): counted in S.prof once, at the end
   // terminal cost-to-go on sigma_N = X_N: diagonal (terminal rows are copies of X_N, gen:94-97)
   for (int e = lane; e < 24 * PS; e += NT) S.P[e] = 0.0;
   __syncthreads();
@@ -648,7 +716,7 @@ __device__ __noinline__ bool riccati_backward(double delta) {
     // ---- G + T^T P T, elimination of the controls: P_k, p_k, gains -> record k; the assembly of stage k - 1 rides along
     double* rec = M.ric + (size_t)k * RIC_STRIDE;
     ok = last ? riccati_step<12>(rec, delta, k) : riccati_step<24>(rec, delta, k);
-    if (lane == 0) { S.prof[PH_NSTAGE] += 1.0; if (ok) S.prof[PH_NSTAGE_OK] += 1.0; }
+    ++n_try;
     PROF_ADD(PH_B_ELIM, tb_);
   }
   if (ok) {
@@ -669,12 +737,13 @@ __device__ __noinline__ bool riccati_backward(double delta) {
     if (lane < 64) gauss_jordan_wave<12>(S.G, S.gam, S.A1, S.A1 + 24 * 24, &S.flag);
     __syncthreads();
     ok = S.flag != 0;
-    if (lane == 0) { S.prof[PH_NSTAGE] += 1.0; if (ok) S.prof[PH_NSTAGE_OK] += 1.0; }
+    ++n_try;
     if (ok) {
       if (lane < 12) S.sig[12 + lane] = -S.A1[24 * 24 + lane];
       __syncthreads();
     }
   }
+  if (lane == 0) { S.prof[PH_NSTAGE] += (double)n_try; S.prof[PH_NSTAGE_OK] += (double)(ok ? n_try : n_try - 1); }
   __syncthreads();
   return ok;
 }
@@ -892,20 +961,26 @@ __global__ void landing_mpc_shift_kernel(Layout L, int B, const double* __restri
 // Difficulty proxy = initial body height z0 = q_init(3) (it grows with |pitch| and the drop speed through the callers'
 // touch-down rule, generate_training_data_automated.m:52-60): correlation 0.65 with the iteration count on the bench
 // batches (round-2 measurement), as good as what a 30-iteration probe predicts.  rank = number of members with a larger
-// key (ties: lower index first) -- O(B^2) comparisons, deterministic, no atomics.  NaN keys sort last.
-__global__ void landing_order_kernel(Layout L, int B, const double* __restrict__ p, int* __restrict__ order) {
-  const int m = blockIdx.x * blockDim.x + threadIdx.x;
-  if (m >= B) return;
+// key (ties: lower index first) -- O(B^2) comparisons, deterministic, no atomics.  NaN keys sort last.  The keys lie np doubles apart: a
+// workgroup stages them in LDS, ORDER_THREADS at a time, instead of every thread walking the strided column itself.
+constexpr int ORDER_THREADS = 256;
+__global__ void __launch_bounds__(ORDER_THREADS) landing_order_kernel(Layout L, int B, const double* __restrict__ p, int* __restrict__ order) {
+  __shared__ double keys[ORDER_THREADS];
+  const int tid = threadIdx.x, m = blockIdx.x * ORDER_THREADS + tid;
   const int off = L.o_q_init + 2;
-  double key = p[(size_t)m * L.np + off];
+  double key = m < B ? p[(size_t)m * L.np + off] : 0.0;
   if (!(key == key)) key = -INFINITY;
   int rank = 0;
-  for (int j = 0; j < B; ++j) {
-    double kj = p[(size_t)j * L.np + off];
+  for (int j0 = 0; j0 < B; j0 += ORDER_THREADS) {
+    double kj = j0 + tid < B ? p[(size_t)(j0 + tid) * L.np + off] : 0.0;
     if (!(kj == kj)) kj = -INFINITY;
-    rank += (kj > key) || (kj == key && j < m);
+    keys[tid] = kj;
+    __syncthreads();
+    const int n = B - j0 < ORDER_THREADS ? B - j0 : ORDER_THREADS;
+    for (int j = 0; j < n; ++j) rank += (keys[j] > key) || (keys[j] == key && j0 + j < m);
+    __syncthreads();
   }
-  order[rank] = m;
+  if (m < B) order[rank] = m;
 }
 
 __global__ void __launch_bounds__(SOLVER_THREADS, SOLVER_MIN_WAVES) landing_ipm_kernel(SolveArgs A) {
@@ -916,14 +991,17 @@ __global__ void __launch_bounds__(SOLVER_THREADS, SOLVER_MIN_WAVES) landing_ipm_
   const int nx = L.nx, ng = L.ng;
   const double* p = A.p + (size_t)m * L.np;
   const landing_solver_opts& o = A.o;
+  // the layout of the member's block; which instance of a swapped array is live is in S.M alone (mem_accept_swap): the set-up below runs before
+  // any swap and uses M directly, everything from the main loop on takes the pointers from live_mem()
   const MemberMem M = carve(L, A.ws + (size_t)m * A.ws_stride);
   Lds& S = SH;
   const double INF = INFINITY;
-  // the workspace arrays never overlap: tell the compiler so that the row passes can batch their loads
   auto bidx = [N](int r) { if (r < 36) return r; const int k = (r - 36) / 104, q = (r - 36) - 104 * k; return 36 + (k == N - 1 ? 104 : 0) + q; };
-  double* __restrict__ r_g = M.g; double* __restrict__ r_gt = M.gt; double* __restrict__ r_s = M.s; double* __restrict__ r_ds = M.ds;
-  double* __restrict__ r_zL = M.zL; double* __restrict__ r_zU = M.zU;
-  double* __restrict__ r_y = M.y; double* __restrict__ r_yn = M.yn; double* __restrict__ r_sig = M.sig; double* __restrict__ r_rho = M.rho;
+  // the workspace arrays never overlap: tell the compiler so that the row passes can batch their loads
+#define ROW_PTRS(M) double* __restrict__ r_g = (M).g; double* __restrict__ r_gt = (M).gt; double* __restrict__ r_s = (M).s; double* __restrict__ r_ds = (M).ds; \
+  double* __restrict__ r_zL = (M).zL; double* __restrict__ r_zU = (M).zU; double* __restrict__ r_y = (M).y; double* __restrict__ r_yn = (M).yn; \
+  double* __restrict__ r_sig = (M).sig; double* __restrict__ r_rho = (M).rho; \
+  (void)r_g; (void)r_gt; (void)r_s; (void)r_ds; (void)r_zL; (void)r_zU; (void)r_y; (void)r_yn; (void)r_sig; (void)r_rho
   S.M = M; S.L = L; S.p = p; S.prof_on = A.prof != nullptr;
   S.ctab = A.ctab; S.ccomb = A.ccomb; S.c_ml = A.c_ml; S.c_mid = A.c_mid; S.rc_on = 0;
   if (lane < SOLVER_THREADS) S.acomb_mid[lane] = A.ccomb[A.c_mid * SOLVER_THREADS + lane];
@@ -931,6 +1009,9 @@ __global__ void __launch_bounds__(SOLVER_THREADS, SOLVER_MIN_WAVES) landing_ipm_
   for (int e = lane; e < A.c_ml * SOLVER_THREADS; e += NT) S.atab_mid[e] = A.ctab[(size_t)A.c_mid * A.c_ml * SOLVER_THREADS + e];      // term table of the most frequent stage type
   if (lane == 0) { S.jhl[CX_ONE] = 1.0; S.jhl[CX_MONE] = -1.0; S.jhl[CX_ZERO] = 0.0; }
   if (lane < 32) S.prof[lane] = 0.0;
+#ifndef __HIPCC__
+  if (lane == 0 && m < EMU_ACC_MAXB) for (int i = 0; i < EMU_ACC_N; ++i) emu_acc[m][i] = 0;
+#endif
   {   // condensation: segment bases of every stage, packed term table of the most frequent stage type
     const int nj = L.nnz_jac, nh = L.nnz_hess;
     for (int k = lane; k < N; k += NT) {
@@ -961,10 +1042,13 @@ __global__ void __launch_bounds__(SOLVER_THREADS, SOLVER_MIN_WAVES) landing_ipm_
   __syncthreads();
   // slacks pushed into the interior, z = 1, y = z_U - z_L, y_dyn = 0; back: at the point a feasibility phase hands back (ipm_init_row)
   auto init_slacks = [&](bool back, double mu_) {
+    const MemberMem M = live_mem();
     for (int r = lane; r < ng; r += NT) { const double lb = S.bnd_lb[bidx(r)], ub = S.bnd_ub[bidx(r)]; ipm_init_row(M, r, r >= 12 && lb != ub, lb, ub, o, back, mu_); }
     __syncthreads();
   };
   init_slacks(false, 0.0);
+  // the shadow instance starts as zeros: rows 0..11 and s / zL / zU of the equality rows, which no pass writes, then agree with the live instance for good
+  for (int r = lane; r < ng; r += NT) { M.s2[r] = 0.0; M.zL2[r] = 0.0; M.zU2[r] = 0.0; M.y2[r] = 0.0; M.sig2[r] = 0.0; M.rho2[r] = 0.0; }
   // primal / complementarity errors, Sigma and rho of the CURRENT point for barrier parameter mu_ (one pass over the
   // rows; the accept pass below produces the same quantities for the next iterate, so this runs only at the start,
   // after a multiplier reset and when mu changes)
@@ -983,6 +1067,8 @@ __global__ void __launch_bounds__(SOLVER_THREADS, SOLVER_MIN_WAVES) landing_ipm_
   // the same for the elastic problem of the feasibility phase (plain row loops: the phase is rare); also leaves the violation of the
   // inequality rows at x (max norm, 1-norm) and |z + w - rho_pen|_inf in K
   auto feas_point_pass = [&](double mu_) {
+    const MemberMem M = live_mem();
+    ROW_PTRS(M);
     ElAcc e{};
     for (int r = lane; r < ng; r += NT) {
       double sg = 0.0, rh = 0.0;
@@ -993,6 +1079,8 @@ __global__ void __launch_bounds__(SOLVER_THREADS, SOLVER_MIN_WAVES) landing_ipm_
   };
   auto point_pass = [&](double mu_) {
     if (K.feas) { feas_point_pass(mu_); return; }
+    const MemberMem M = live_mem();
+    ROW_PTRS(M);
     double pr = 0.0, co = 0.0, cm = 0.0, ys = 0.0, zs = 0.0, nz = 0.0;
     for (int rb = lane; rb < ng; rb += NT * RB) {
       double lbv[RB], ubv[RB], gv[RB], sv[RB], zlv[RB], zuv[RB], yv[RB];
@@ -1027,7 +1115,7 @@ __global__ void __launch_bounds__(SOLVER_THREADS, SOLVER_MIN_WAVES) landing_ipm_
   if (lane == 0) {
     ipm_init(K, o);
     K.tp = A.prof ? (long long)wall_clock64() : 0;
-    S.clip_now = 0; S.jamrun = 0; S.fact_failed = 0;
+    S.clip_now = 0; S.jamrun = 0; S.fact_failed = 0; S.first_trial = 0; S.fast = 0;
   }
   __syncthreads();
   // the lane = stage phases are called by the lanes that have work only: the callee-saved registers an out-of-line function touches
@@ -1036,6 +1124,7 @@ __global__ void __launch_bounds__(SOLVER_THREADS, SOLVER_MIN_WAVES) landing_ipm_
 
   for (;;) {
     // ---------------------------------------------------------------- derivatives at (x, y)
+    const MemberMem M = live_mem();      // (every block below that runs behind a possible swap or keeps row pointers takes its own)
     if (A.prof && lane == 0) K.tp = (long long)wall_clock64();
     // (round 2: the coalesced tile write-out of landing_sweep_kernel<0> was tried here for the Jacobian task -- eval_task_jac_tiled,
     // tiles in the dead G array -- and is slower: 0.049 vs 0.039 ms alone, 0.094 vs 0.085 under load; every lane then runs the
@@ -1146,6 +1235,8 @@ __global__ void __launch_bounds__(SOLVER_THREADS, SOLVER_MIN_WAVES) landing_ipm_
     // clip_k rule (landing_nlp.h): while the point is far from feasible the step length comes from the clip_k-th largest
     // ratio |ds| / distance; the slacks with a larger one stop at (1 - tau) of their distance (omt > 0 in the passes below)
     {
+      const MemberMem M = live_mem();
+      ROW_PTRS(M);
       const double mu = K.mu;
       const bool feas = K.feas != 0;
       const bool clip_now = !feas && K.clip_k_cur > 1 && (K.c_pr > o.clip_until || (o.jam_clip > 0 && S.jamrun >= o.jam_clip));      // far from feasible, or jammed (landing_nlp.h)
@@ -1228,18 +1319,29 @@ __global__ void __launch_bounds__(SOLVER_THREADS, SOLVER_MIN_WAVES) landing_ipm_
         if (K.th_max == 0.0) K.th_max = 1e4 * fmax(1.0, v[2]);
         // line search state
         K.alpha = a_pr; K.s_corr = 0.0; K.accepted = 0; K.armijo_step = 0; K.ls_done = a_pr > 1e-10 ? 0 : 1;
+        S.first_trial = (feas || !LANDING_EMU_FUSED_ON) ? 0 : 1; S.fast = 0;
       KS_END();
     }
     PROF_ADD(PH_DUAL, K.tp);
     // ================================================================ filter line search
+    // The FIRST trial point of an iteration is nearly always the one accepted (1.001 trial points per iteration on the bench batches), and what the
+    // accept pass computes for it -- s, zL, zU, y, Sigma, rho of the new point and its error sums -- depends on the step lengths and on gt only, not
+    // on the outcome of the test.  So in interior-point mode the first trial pass does the accept pass's work as well (same expressions, s_corr = 0),
+    // into the shadow instance; if ipm_ls_test takes the point as it stands, accepting it is a swap of instances (below) instead of a third walk
+    // over the rows.  A rejected first trial leaves the shadow values to be overwritten; back-tracking, the slack correction, the fallback step and
+    // the feasibility phase go through the accept pass as before.
     while (!K.ls_done) {
+      const MemberMem M = live_mem();
+      ROW_PTRS(M);
       const double alpha = K.alpha, omt = K.omt, mu = K.mu;
+      const bool fused = S.first_trial != 0;      // (uniform; cleared in the control section behind the reduction)
       if (lane == 0) S.prof[PH_NTRIAL] += 1.0;
       for (int i = lane; i < nx; i += NT) M.xt[i] = M.x[i] + alpha * M.dx[i];
       __syncthreads();
       if (lane < nst) member_eval_g(L, M.xt, p, M.gt);
       __syncthreads();
       double tht = 0.0, bt = 0.0, ft = 0.0;
+      double npr = 0.0, nco = 0.0, ncm = 0.0, nys = 0.0, nzs = 0.0, nnz = 0.0;      // (fused first trial: errors and sums of the new point)
       const bool feas = K.feas != 0;
       if (feas) {      // elastic rows at the trial step length: theta over all rows, merit = rho_pen (n + q) - mu sum of logs (mu applied below)
         const double frho = o.feas_rho;
@@ -1251,6 +1353,60 @@ __global__ void __launch_bounds__(SOLVER_THREADS, SOLVER_MIN_WAVES) landing_ipm_
           if (lb > -INF) { const double n0 = M.en[r]; const ElStep e = el_step(1.0, s0 - lb + n0, n0, r_zL[r], M.wn[r], mu, frho, ds); const double n = n0 + alpha * e.dn; bt -= log((s - lb + n) * n); ft += frho * n; }
           if (ub < INF) { const double q0 = M.ep[r]; const ElStep e = el_step(-1.0, ub + q0 - s0, q0, r_zU[r], M.wp[r], mu, frho, ds); const double q = q0 + alpha * e.dn; bt -= log((ub + q - s) * q); ft += frho * q; }
         }
+      } else if (fused) {
+        // trial pass + accept pass of this trial point in one walk: rows 12.. under the trial pass's ownership (rows lane + 12 + j NT); rows 0..11
+        // carry g only, which comes with the swap gt -> g, and Sigma = rho = 0 in both instances.  The dual step length is the one ipm_ls_end
+        // will leave if this point is accepted (alpha stays as it is).
+        const double a_du = o.dual_step_cap > 0.0 ? fmin(K.a_du, o.dual_step_cap * alpha) : K.a_du;
+        double* __restrict__ w_s = M.s2; double* __restrict__ w_zL = M.zL2; double* __restrict__ w_zU = M.zU2; double* __restrict__ w_y = M.y2;
+        double* __restrict__ w_sig = M.sig2; double* __restrict__ w_rho = M.rho2;
+        for (int rb = lane + 12; rb < ng; rb += NT * RB) {
+          double lbv[RB], ubv[RB], gv[RB], sv[RB], dsv[RB], zlv[RB], zuv[RB], yv[RB], ynv[RB];
+#pragma unroll
+          for (int j = 0; j < RB; ++j) {
+            const int r = rb + j * NT, rr = r < ng ? r : ng - 1;
+            lbv[j] = S.bnd_lb[bidx(rr)]; ubv[j] = S.bnd_ub[bidx(rr)]; gv[j] = r_gt[rr]; sv[j] = r_s[rr]; dsv[j] = r_ds[rr]; zlv[j] = r_zL[rr]; zuv[j] = r_zU[rr]; yv[j] = r_y[rr]; ynv[j] = r_yn[rr];
+          }
+#pragma unroll
+          for (int j = 0; j < RB; ++j) {
+            const int r = rb + j * NT;
+            if (r >= ng) continue;
+            const double lb = lbv[j], ub = ubv[j], g = gv[j];
+            double sg = 0.0, rh = 0.0;
+            if (lb == ub) {
+              tht += fabs(g - lb);
+              const double yn_ = yv[j] + alpha * (ynv[j] - yv[j]); w_y[r] = yn_; nys += fabs(yn_); npr = fmax(npr, fabs(g - lb));
+            } else {
+              const double so = sv[j], ds = dsv[j];
+              double s = so + alpha * ds;
+              if (omt > 0.0) { if (lb > -INF) s = fmax(s, fma(omt, so - lb, lb)); if (ub < INF) s = fmin(s, fma(-omt, ub - so, ub)); }
+              tht += fabs(g - s);
+              bt -= log((lb > -INF ? s - lb : 1.0) * (ub < INF ? ub - s : 1.0));
+              double zl = 0.0, zu = 0.0;
+              if (lb > -INF) {
+                const double dold = so - lb, ro = fast_rcp(dold), zo = zlv[j], dz = fma(-zo * ro, ds, mu * ro - zo), d = s - lb, rd = fast_rcp(d);
+                zl = fmin(fmax(zo + a_du * dz, 1e-10 * mu * rd), 1e10 * mu * rd);
+                nco = fmax(nco, d * zl); ncm = fmax(ncm, fabs(d * zl - mu)); sg += zl * rd; rh -= mu * rd; nzs += zl; nnz += 1.0;
+              }
+              if (ub < INF) {
+                const double dold = ub - so, ro = fast_rcp(dold), zo = zuv[j], dz = fma(zo * ro, ds, mu * ro - zo), d = ub - s, rd = fast_rcp(d);
+                zu = fmin(fmax(zo + a_du * dz, 1e-10 * mu * rd), 1e10 * mu * rd);
+                nco = fmax(nco, d * zu); ncm = fmax(ncm, fabs(d * zu - mu)); sg += zu * rd; rh += mu * rd; nzs += zu; nnz += 1.0;
+              }
+              npr = fmax(npr, fabs(g - s));
+              rh += sg * (g - s);
+              w_s[r] = s; w_zL[r] = zl; w_zU[r] = zu; w_y[r] = zu - zl; nys += fabs(zu - zl);
+            }
+            w_sig[r] = sg; w_rho[r] = rh;
+          }
+        }
+        // block_reduce pairs partial sums by thread id, and the accept pass owns rows lane + j NT: its thread t sums the rows this pass gives to
+        // thread t - 12 (mod NT; for t < 12 behind the rows 0..11, which add nothing).  Handing the two order-dependent sums of the new point to
+        // that thread keeps their association -- and with it every later bit -- what it was (maxima and the row count do not depend on it).
+        static_assert(ASM_NSLOT >= 2 * SOLVER_THREADS, "carry takes two partial sums per thread");
+        { const int t = lane + 12 < NT ? lane + 12 : lane + 12 - NT; S.carry[2 * t] = nys; S.carry[2 * t + 1] = nzs; }      // (carry is idle outside the backward sweep)
+        __syncthreads();
+        nys = S.carry[2 * lane]; nzs = S.carry[2 * lane + 1];
       } else
       for (int rb = lane + 12; rb < ng; rb += NT * RB) {
         double lbv[RB], ubv[RB], gv[RB], sv[RB], dsv[RB];
@@ -1269,8 +1425,19 @@ __global__ void __launch_bounds__(SOLVER_THREADS, SOLVER_MIN_WAVES) landing_ipm_
       }
       if (lane < 12 && !feas) { const double d = M.xt[12 * N + lane] - p[12 * N + lane]; ft = p[L.o_QN + lane] * d * d; }
       if (L.run_cost && !feas) ft += rc_f(M.xt);
-      { double v[3] = {tht, bt, ft}; const int op[3] = {RSUM, RSUM, RSUM}; block_reduce<3>(v, op, S.red); tht = v[0]; bt = v[1]; ft = v[2]; }
-      KS_BEGIN_SYNCED() ipm_ls_test(K, o, tht, ft, bt, S.filt_th, S.filt_ph); KS_END();
+      if (fused) {
+        double v[9] = {tht, bt, ft, npr, nco, ncm, nys, nzs, nnz}; const int op[9] = {RSUM, RSUM, RSUM, RMAX, RMAX, RMAX, RSUM, RSUM, RSUM};
+        block_reduce<9>(v, op, S.red);
+        KS_BEGIN_SYNCED()
+          ipm_ls_test(K, o, v[0], v[2], v[1], S.filt_th, S.filt_ph);
+          S.first_trial = 0; S.fast = K.accepted;      // accepted at once: alpha is the one the pass ran with, s_corr = 0
+          for (int i = 0; i < 6; ++i) S.nxt[i] = v[3 + i];
+          LANDING_EMU_COUNT(m, K.accepted ? (omt > 0.0 ? EMU_ACC_FAST_CLIP : EMU_ACC_FAST) : EMU_ACC_FIRST_REJECTED);
+        KS_END();
+      } else {
+        { double v[3] = {tht, bt, ft}; const int op[3] = {RSUM, RSUM, RSUM}; block_reduce<3>(v, op, S.red); tht = v[0]; bt = v[1]; ft = v[2]; }
+        KS_BEGIN_SYNCED() ipm_ls_test(K, o, tht, ft, bt, S.filt_th, S.filt_ph); KS_END();
+      }
       if (K.need_corr) {
         // slack correction (landing_nlp.h): the rejected first trial point once more with the inequality slacks moved to g(x_trial)
         double tht2 = 0.0, bt2 = 0.0;
@@ -1298,7 +1465,25 @@ __global__ void __launch_bounds__(SOLVER_THREADS, SOLVER_MIN_WAVES) landing_ipm_
     KS_BEGIN()
       ipm_ls_end(K, o, S.filt_th, S.filt_ph, FILT_CAP);
       if (o.jam_clip > 0) S.jamrun = (!S.clip_now && K.a_pr < 0.02) ? S.jamrun + 1 : 0;
+      if (S.fast) {      // accept = swap: the fused pass left the new point in the shadow instance
+#ifndef __HIPCC__
+        for (int r = 0; r < ng; ++r) {      // emulation build: the rule stated at MemberMem holds
+          const MemberMem& Q = S.M;
+          const bool eq = r >= 12 && S.bnd_lb[bidx(r)] == S.bnd_ub[bidx(r)];
+          if ((r < 12 && (Q.y[r] != Q.y2[r] || Q.sig[r] != Q.sig2[r] || Q.rho[r] != Q.rho2[r])) || (eq && (Q.s[r] != Q.s2[r] || Q.zL[r] != Q.zL2[r] || Q.zU[r] != Q.zU2[r]))) {
+            fprintf(stderr, "landing_ipm_kernel: member %d row %d differs between the two instances of the row arrays at a swap\n", m, r); abort();
+          }
+        }
+#endif
+        mem_accept_swap(S.M);
+        K.c_pr = S.nxt[0]; K.c_co = S.nxt[1]; K.c_cm = S.nxt[2]; K.c_ys = S.nxt[3]; K.c_zs = S.nxt[4]; K.c_nz = fmax(S.nxt[5], 1.0);
+        K.it++;
+      }
     KS_END();
+    if (S.fast) { PROF_ADD(PH_LS, K.tp); PROF_ADD(PH_ACCEPT, K.tp); continue; }
+    {
+    const MemberMem M = live_mem();
+    ROW_PTRS(M);
     if (K.fallback) {
       const double alpha = K.alpha;
       for (int i = lane; i < nx; i += NT) M.xt[i] = M.x[i] + alpha * M.dx[i];
@@ -1337,7 +1522,7 @@ __global__ void __launch_bounds__(SOLVER_THREADS, SOLVER_MIN_WAVES) landing_ipm_
       }
       __syncthreads();
       feas_point_pass(mu);
-      KS_BEGIN() K.it++; KS_END();
+      KS_BEGIN() K.it++; LANDING_EMU_COUNT(m, EMU_ACC_FEAS); KS_END();
     } else {
       const double alpha = K.alpha, a_du = K.a_du, omt = K.omt, mu = K.mu, s_corr = K.s_corr;
       double npr = 0.0, nco = 0.0, ncm = 0.0, nys = 0.0, nzs = 0.0, nnz = 0.0;
@@ -1389,15 +1574,19 @@ __global__ void __launch_bounds__(SOLVER_THREADS, SOLVER_MIN_WAVES) landing_ipm_
       KS_BEGIN_SYNCED()
         K.c_pr = v[0]; K.c_co = v[1]; K.c_cm = v[2]; K.c_ys = v[3]; K.c_zs = v[4]; K.c_nz = fmax(v[5], 1.0);
         K.it++;
+        LANDING_EMU_COUNT(m, K.fallback ? EMU_ACC_FALLBACK : (s_corr > 0.0 ? EMU_ACC_CORR : EMU_ACC_BACKTRACK));
       KS_END();
     }
     PROF_ADD(PH_ACCEPT, K.tp);
+    }
   }
   __syncthreads();
   if (A.prof && lane == 0) { S.prof[PH_NITER] = (double)K.it; for (int i = 0; i < PH_COUNT; ++i) A.prof[(size_t)m * PH_COUNT + i] = S.prof[i]; }
 
   // -------------------------------------------------------------------- outputs
   // multipliers of the initial-state rows from stationarity of X(:,1): lam = -(grad f + J^T y)
+  {
+  const MemberMem M = live_mem();
   double fo = 0.0;
   if (lane < 12) { M.y[lane] = -M.gx[lane]; const double d = M.x[12 * N + lane] - p[12 * N + lane]; fo = p[L.o_QN + lane] * d * d; }
   if (L.run_cost) fo += rc_f(M.x);
@@ -1421,6 +1610,8 @@ __global__ void __launch_bounds__(SOLVER_THREADS, SOLVER_MIN_WAVES) landing_ipm_
     if (A.iters) A.iters[m] = K.it;
     if (A.kkt) { A.kkt[3 * m] = kp; A.kkt[3 * m + 1] = K.e_du; A.kkt[3 * m + 2] = kc; }
   }
+  }
+#undef ROW_PTRS
 #undef KS_BEGIN
 #undef KS_BEGIN_SYNCED
 #undef KS_END

@@ -6,7 +6,7 @@
 // the next batch's workgroups fill the slots the previous batch frees: two launches in flight on two HIP streams, each with its own workspace.  Rounds 3-5
 // measured it from the outside (two contexts, two streams, two host threads: bench.py `two_batches_in_flight`, 25.0 k against 19.2 k NLPs/s); here the library
 // does it behind one call pattern -- submit, submit, ..., wait -- on the caller's one context and one thread.  Lane 0 is the context itself, lanes 1.. are
-// child contexts with the same formulation (their own solver workspace: 1.1 MB per member at N = 40), every lane has a non-blocking stream of its own;
+// child contexts with the same formulation (their own solver workspace: 1.3 MB per member at N = 40), every lane has a non-blocking stream of its own;
 // submission i goes to lane i mod lanes, ordered behind the caller's stream (the inputs are ready there) by an event.  Members are independent and a
 // lane runs the very launch landing_solve_batch would: results are bit-identical to one call at a time (tests/test_gpu_dataset.py).
 struct landing_stream {

@@ -1,6 +1,8 @@
 #!/bin/bash
 # Profiles of one round (run on the GPU box through gpurun): kernel-trace stats of bench.py + separate PMC passes
 # (never combined with tracing domains other than --kernel-trace).  Output: gpurun_out/prof_$1/*
+# The first step that fails (a fault, a time limit) ends the script: nothing more is started on the GPU behind it.
+set -e -o pipefail
 tag=${1:-r06}
 out=$PWD/gpurun_out/prof_$tag
 mkdir -p $out
@@ -19,7 +21,7 @@ timeout -k 5 400 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -
 cd $GRAFT_REPO_ROOT
 python3 tools/pmc_summary.py $tag $out/stats $out/fetch $out/write $out/sq $out/cal_fetch $out/cal_write > $out/summary.json 2> $out/summary.err
 python3 tools/pmc_sweep_summary.py $tag $out/sw_fetch $out/sw_write 23 > $out/summary_sweep.json 2> $out/summary_sweep.err
-cp profiles/${tag}_pmc_ipm.json profiles/${tag}_pmc_sweep.json $out/ 2>/dev/null
+cp profiles/${tag}_pmc_ipm.json profiles/${tag}_pmc_sweep.json $out/ 2>/dev/null || true
 find $out -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats.csv \;
 find $out -name "*_kernel_trace.csv" -delete; find $out -name "*agent_info.csv" -delete
 du -sh $out; tail -3 $out/*.err | tail -20
