@@ -149,7 +149,13 @@ typedef struct {
                             iterations and would otherwise set the batch time from the second wave); 0: batch order.  Results do
                             not depend on it (every member is solved independently).  Applied only to batches that do not fit the GPU at
                             once (more than 512 members) and up to 16 384 members (the ranking kernel compares all pairs)               */
-  double delta_init;     /* first trial regularisation when none was needed before (IPOPT first_hessian_perturbation, 1e-4) */
+  double delta_init;     /* first trial regularisation when none was needed before (IPOPT first_hessian_perturbation, 1e-4).
+                            WHERE delta_w GOES (this field, the schedule behind it and delta_floor): the Riccati sweep adds it to the diagonal
+                            of every STAGE block, over the stage's state (X_k, c_k) and its control (f_k, c_{k+1}).  The feet c_1 .. c_{N-1} are
+                            the control of stage k - 1 and the state of stage k, so they receive 2 delta_w; every other free variable (X_1 .. X_N,
+                            c_0, every f_k) receives delta_w.  The regularised matrix is H + delta_w diag(1, .., 2 on c_1 .. c_{N-1}, .., 1), not
+                            H + delta_w I.  The CPU port (oracle/landing_solver_cpu.c) does the same.  Pinned by tests/test_solver_step_cpu.py
+                            (test_plain_delta_identity_is_not_what_the_kernel_solves); a change is a solver change: every iterate moves.     */
   double delta_inc_first;/* growth factor while no regularised iteration happened yet (IPOPT 100; default 10)            */
   double delta_inc;      /* growth factor afterwards (IPOPT 8; default 4: finer steps over-regularise less, tools/strag.py) */
   double delta_dec;      /* first trial = delta_last * delta_dec (IPOPT 1/3; default 1/2: 5 % fewer stage eliminations at unchanged
@@ -262,7 +268,8 @@ typedef struct {
                             already starts at 1e-3 (44.9 instead of 40.1 iterations, one member of 65 536 lost) while 3e-4 and 5e-4 are
                             equivalent (72.7 / 71.3 ms per batch): the default is 3e-4, a factor 3 below that cliff (two hold-out sets of
                             131 072 drop states: all converged, worst member 167 iterations).  0 = the plain IPOPT schedule (first trial
-                            delta_w = 0)                                                                                                 */
+                            delta_w = 0).  Like every delta_w it counts twice on the feet c_1 .. c_{N-1} (see delta_init): the proximal term is
+                            (1/2) delta (|x - x_k|^2 + |c_1..N-1 - c_k,1..N-1|^2)                                                         */
   int jam_clip;          /* (round 4) the clip_k rule also NEAR feasibility once the classic fraction-to-the-boundary rule has allowed a step
                             to the boundary below 0.02 in this many iterations in a row (default 2; 0 = never): the slow members left after
                             the option changes of round 4 (65..78 iterations against a mean of 34) sit in a later barrier problem with
@@ -786,7 +793,19 @@ int landing_wb_select(landing_ctx* ctx, int B, int N, int nalpha, const double* 
  * factorisations, trial points, iterations); NULL disables. */
 int landing_set_profile_buffer(landing_ctx* ctx, double* d_prof);
 /* diagnostic: device pointer and per-member stride (doubles) of the solver workspace left by the last landing_solve_batch
- * (layout: landing-controller_amd/csrc/solver_kernels.hip, carve()) */
+ * (layout: landing-controller_amd/csrc/solver_kernels.hip, carve(); mirrored for Python by workspace_offsets() in
+ * landing-controller_amd/capi.py, which a test holds against this stride).  Member m's block starts at d_ws + m * stride, whatever
+ * order the launch ran the members in.  After a launch it holds, among others, dx, ds and yn of the LAST Newton step (yn: multipliers
+ * of the equality rows; its inequality rows are not meaningful) and both instances of the row arrays the accept step swaps
+ * (s / s2, zL / zL2, zU / zU2, y / y2, sig / sig2, rho / rho2).
+ * EXIT RECORD: the last 8 doubles of the block (behind y2), written once per member when the kernel returns, hold what otherwise
+ * exists in LDS only:
+ *   [0] mu       barrier parameter the last step was computed with
+ *   [1] delta    regularisation delta_w of the last factorisation tried (the successful one, if the step was computed)
+ *   [2] alpha    primal step length of the last accepted step          [3] a_du   its dual step length
+ *   [4] live     0: the first instance (s, zL, zU, y, sig, rho) holds the iterate; 1: the second one (s2, ...) does
+ *   [5] it       iterations counted (= iters)   [6] omt   > 0: the clip_k rule was in force in the last step   [7] s_corr
+ * tests/test_solver_step_cpu.py and tests/test_gpu_solver_step.py use it to check the step against an independent KKT solve. */
 int landing_debug_workspace(landing_ctx* ctx, double** d_ws, unsigned long long* stride);
 
 /* name of the dominant kernels (for profilers) and per-launch algorithmic bytes of the sweep */

@@ -79,6 +79,39 @@ EXPORTS = ["landing_last_error", "landing_form_default", "landing_solver_opts_de
            "landing_stream_create", "landing_stream_destroy", "landing_stream_lanes", "landing_stream_submit", "landing_stream_wait", "landing_stream_sync", "landing_solve_stream_host"]
 
 
+# Sizes the solver kernel's workspace layout is built from (csrc/solver_kernels.hip: RUNC, RIC_STRIDE, RCG, EXIT_REC)
+WS_RUNC, WS_RIC_STRIDE, WS_RCG, WS_EXIT_REC = 48, 1200, 36, 8
+EXIT_RECORD = ("mu", "delta", "alpha", "a_du", "live", "it", "omt", "s_corr")
+
+
+def workspace_offsets(N, nx=None, ng=None, nnz_jac=None, nnz_hess=None):
+    """The layout of one member's block of the solver workspace (landing_debug_workspace): dict name -> (offset, length) in doubles, in the
+    order of carve() in csrc/solver_kernels.hip, plus "total" -> the member stride.  x / xt, g / gt and the row arrays with a second instance
+    (s, zL, zU, y, sig, rho) swap roles when a first trial point is accepted: "rec" (EXIT_RECORD) says which instance is live at exit."""
+    nx = 36 * N + 12 if nx is None else nx
+    ng = 104 * N + 12 if ng is None else ng
+    nnz_jac = 36 + 385 * (N - 1) + 313 if nnz_jac is None else nnz_jac
+    nnz_hess = 177 * N + 12 * (N - 1) + 12 if nnz_hess is None else nnz_hess
+    parts = [(n, nx) for n in ("x", "xt", "dx", "gx")] + [(n, ng) for n in ("g", "gt", "s", "ds", "zL", "zU", "y", "yn", "sig", "rho")]
+    parts += [("J", nnz_jac), ("H", nnz_hess), ("Hc", N * WS_RUNC), ("ric", (N + 1) * WS_RIC_STRIDE), ("cond", N * WS_RCG)]
+    parts += [(n, ng) for n in ("en", "ep", "wn", "wp", "sig2", "rho2", "s2", "zL2", "zU2", "y2")] + [("rec", WS_EXIT_REC)]
+    off, out = 0, {}
+    for n, sz in parts:
+        out[n] = (off, sz)
+        off += sz
+    out["total"] = off
+    return out
+
+
+def _hip_runtime():
+    """the HIP runtime this process has already mapped (torch's own copy when torch is loaded): a second copy would know nothing of the allocations"""
+    with open("/proc/self/maps") as f:
+        for line in f:
+            if "libamdhip64" in line:
+                return C.CDLL(line.split()[-1])
+    return C.CDLL("libamdhip64.so")
+
+
 def load(path=None):
     path = path or os.path.join(HERE, LIB_NAME)
     try:  # torch ships its own libamdhip64: it must be the first HIP runtime loaded in the process,
@@ -291,6 +324,35 @@ class LandingLib:
         h = np.full((x.shape[0], self.lib.landing_nnz_hess_rc(self.N)), np.nan)
         self._check(self.lib.landing_eval_hess_rc_batch_host(self.ctx, x.shape[0], _p(x), _p(p), _p(lam_f), _p(lam_g), _p(h)), "landing_eval_hess_rc_batch_host")
         return h
+
+    def workspace_offsets(self):
+        return workspace_offsets(self.N, self.nx, self.ng, self.nnz_jac, self.nnz_hess)
+
+    def workspace_stride(self):
+        """doubles per member of the solver workspace, as the library lays it out"""
+        ptr = C.c_void_p(); st = C.c_ulonglong()
+        self.lib.landing_debug_workspace.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_ulonglong)]
+        self._check(self.lib.landing_debug_workspace(self.ctx, C.byref(ptr), C.byref(st)), "landing_debug_workspace")
+        return int(st.value)
+
+    def debug_workspace(self, B):
+        """landing_debug_workspace: the blocks of the first B members of the last solve as a host array [B, stride] (diagnostic; the caller has
+        synchronised with that solve -- the host entry points have).  Slice a row with workspace_offsets()."""
+        ptr = C.c_void_p(); st = C.c_ulonglong()
+        self.lib.landing_debug_workspace.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_ulonglong)]
+        self._check(self.lib.landing_debug_workspace(self.ctx, C.byref(ptr), C.byref(st)), "landing_debug_workspace")
+        if not ptr.value:
+            raise RuntimeError("landing_debug_workspace: no solve has run in this context")
+        out = np.empty((B, st.value))
+        if hasattr(self.lib, "landing_emu_set_fused"):      # host emulation: the workspace is host memory
+            C.memmove(out.ctypes.data, ptr.value, out.nbytes)
+        else:
+            hip = _hip_runtime()
+            hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+            rc = hip.hipMemcpy(out.ctypes.data, ptr.value, out.nbytes, 2)      # hipMemcpyDeviceToHost
+            if rc != 0:
+                raise RuntimeError("hipMemcpy of the solver workspace failed (%d)" % rc)
+        return out
 
     # ---- host-pointer entry points (numpy in / numpy out) --------------------------------------
     def eval_host(self, x, p, lam_f=None, lam_g=None, want=("f", "g", "grad_f", "jac", "hess", "grad_gamma_x", "grad_gamma_p")):

@@ -66,9 +66,12 @@ constexpr int CX_SR = NZ_TOT + 48, CX_ONE = CX_SR + 208, CX_MONE = CX_ONE + 1, C
 constexpr int ATAB_TB = 6, ATAB_LTMAX = 6;       // terms per batch; longest per-thread list (a multiple of ATAB_TB): the 1 138..1 234 terms of a stage give 5 per thread
 constexpr int ASM_NSLOT = 512;                   // partial-sum slots of one stage
 
+// exit record of a member (the last doubles of its block, behind y2; landing_nlp.h landing_debug_workspace): the scalars of the last step that live in
+// LDS only -- mu | delta | alpha | a_du | 1 when the second instance of the swapped row arrays is the live one | it | omt | s_corr
+constexpr int EXIT_REC = 8;
 // doubles of one member's block of the solver workspace (landing::SolverWorkspace, capi.hip)
 inline size_t member_stride(const Layout& L) {
-  return (size_t)4 * L.nx + (size_t)20 * L.ng + L.nnz_jac + L.nnz_hess + (size_t)L.N * RUNC + (size_t)(L.N + 1) * RIC_STRIDE + (size_t)L.N * RCG;
+  return (size_t)4 * L.nx + (size_t)20 * L.ng + L.nnz_jac + L.nnz_hess + (size_t)L.N * RUNC + (size_t)(L.N + 1) * RIC_STRIDE + (size_t)L.N * RCG + EXIT_REC;
 }
 
 // optional per-member phase timers (wall_clock64 ticks, 100 MHz) -- enabled when SolveArgs.prof != nullptr
@@ -1582,6 +1585,10 @@ __global__ void __launch_bounds__(SOLVER_THREADS, SOLVER_MIN_WAVES) landing_ipm_
   }
   __syncthreads();
   if (A.prof && lane == 0) { S.prof[PH_NITER] = (double)K.it; for (int i = 0; i < PH_COUNT; ++i) A.prof[(size_t)m * PH_COUNT + i] = S.prof[i]; }
+  if (lane == 0) {      // exit record (EXIT_REC): M still holds the instances as carve() laid them out, S.M the live ones
+    double* rec = M.y2 + ng;
+    rec[0] = K.mu; rec[1] = K.delta; rec[2] = K.alpha; rec[3] = K.a_du; rec[4] = (S.M.s == M.s) ? 0.0 : 1.0; rec[5] = (double)K.it; rec[6] = K.omt; rec[7] = K.s_corr;
+  }
 
   // -------------------------------------------------------------------- outputs
   // multipliers of the initial-state rows from stationarity of X(:,1): lam = -(grad f + J^T y)
