@@ -4,7 +4,10 @@ X [12, N+1] (q = x y z roll pitch yaw; qdot = omega_body, v_world), U [24, N] (c
 Rotation rpyToRotMat_xyz.m:2, Euler rates Binv.m:13-17, foot Jacobians get_foot_jacobians_mc.m, forward kinematics
 get_forward_kin_foot.m (through oracle/rbd_oracle.py).  Pinned by reference-held data: the two stored solutions of
 optimizations/landing/test_scripts (tests/golden/n1_kinodyn_solutions.npz, tests/test_n1_rows.py) satisfy every row group below
-to the feasibility tolerance of the solver that produced them (KNITRO feastol 1e-4 relative / 1e-3 absolute, :392-393).
+to the feasibility tolerance of the solver that produced them (KNITRO feastol 1e-4 relative / 1e-3 absolute, :392-393), and the
+reference's own KNITRO solution AND multipliers of the production problem (main_scripts/prevSoln.mat: lam_g_star [2844],
+tests/golden/n1_kinodyn_multipliers.npz) are a KKT point of nlp_g / grad_lagrangian_batch / kkt below to 1e-6, which pins order, sign and
+multiplier convention of 19 of the 27 row groups (tests/test_kd_multipliers_cpu.py; the other 8 by feasibility only).
 Only tests/ may import this module."""
 import numpy as np
 

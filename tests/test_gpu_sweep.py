@@ -102,8 +102,10 @@ def test_casadi_dropin_on_gpu_matches_reference_golden():
 def test_knitro_dropin_on_gpu_matches_oracle():
     """landingCtrller_KNITRO_mi355x.so (round 6): the CasADi-external face of the kinodynamic refinement NLP (generate_landingCtrller_KNITRO.m:360-377 generates and loads
     ./landingCtrller_KNITRO.so; a missing blob of the reference) called exactly as CasADi's external() would -- metadata CasADi asserts on (external.cpp:325-363),
-    arg / res pointer arrays, NULL outputs skipped -- at the script's size (21 knots: x 972, p 373, g 2844) against the oracle (KD oracle: parity unpinned beyond row
-    feasibility of the reference's two stored solutions; derivatives of the oracle are complex-step / Richardson derivatives of itself)."""
+    arg / res pointer arrays, NULL outputs skipped -- at the script's size (21 knots: x 972, p 373, g 2844) against the oracle (KD oracle: pinned by the reference's own
+    KNITRO multipliers for 19 of its 27 row groups, the other 8 -- c_init, the four terminal boxes, leg torques, joint limits lower / upper -- by feasibility only:
+    tests/test_kd_multipliers_cpu.py; the drop-in AT the reference's solution: tests/test_gpu_kd_multipliers.py; derivatives of the oracle are complex-step /
+    Richardson derivatives of itself)."""
     from oracle import kinodyn_oracle as ko
     kd = lc("kinodyn")
     N, nx, ng, npar = 20, 972, 2844, 373
