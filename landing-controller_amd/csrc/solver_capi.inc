@@ -225,8 +225,10 @@ int build_tables(const Layout& L, std::vector<int>& data, std::vector<int>& stag
   {
     using landing::Lds;
     const int NTH = landing::SOLVER_THREADS;
-    const int oG = (int)offsetof(Lds, G), oGam = (int)offsetof(Lds, gam), oAh = (int)offsetof(Lds, Ah), oCx = (int)offsetof(Lds, jhl), oCarry = (int)offsetof(Lds, carry), oDump = (int)offsetof(Lds, dump);
+    const int oG = (int)offsetof(Lds, G), oAh = (int)offsetof(Lds, Ah), oCx = (int)offsetof(Lds, jhl), oCarry = (int)offsetof(Lds, carry), oDump = (int)offsetof(Lds, dump);
     auto cx = [&](int pos) { return oCx + 8 * pos; };
+    // G in elimination order, the same for every stage type: (sigma, f, c+) -> rows / columns (f, c+, sigma); gamma is its spare column
+    auto gpos = [](int a) { return a < 24 ? a + 24 : a - 24; };
     int ch = 0;
     for (size_t u = 0; u < uniq.size(); ++u) ch = std::max(ch, ((int)uniq[u].cloc.size() + NTH - 1) / NTH);
     struct Piece { std::vector<std::array<int, 3>> ops; int d; bool ah; };
@@ -254,8 +256,8 @@ int build_tables(const Layout& L, std::vector<int>& data, std::vector<int>& stag
           if (dst >= (int)T.tg_ab.size()) return -12;
           const int a0 = T.tg_ab[dst] & 255, b0 = T.tg_ab[dst] >> 8;
           if (a0 >= 48 || b0 >= 48) return -12;
-          d = oG + 8 * (std::min(a0, b0) * landing::GS + std::max(a0, b0));      // upper triangle (block_eliminate's tile fetch)
-        } else if (dst < landing::COND_AH) d = oGam + 8 * (dst - landing::COND_GAM);
+          d = oG + 8 * (std::min(gpos(a0), gpos(b0)) * landing::GS + std::max(gpos(a0), gpos(b0)));      // upper triangle (block_eliminate's tile fetch)
+        } else if (dst < landing::COND_AH) d = oG + 8 * (gpos(dst - landing::COND_GAM) * landing::GS + landing::G_GAMMA);
         else {
           const int q = dst - landing::COND_AH;
           if (3 * q + 2 >= (int)T.a_term.size()) return -12;

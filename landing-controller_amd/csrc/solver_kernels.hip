@@ -174,7 +174,7 @@ struct Lds {
   double A1[2 * XCH];          // Y = P(:,0:12)*A^ (24 x YS = 888) while T^T P T is formed, then the elimination side block
                               // Ex (24 x ES): col 0 = gamma_u -> z, cols 1.. = I -> unit-lower inverse
   double Ah[2 * 12 * YS];      // A^ of the stage being eliminated and of the one being assembled (copy k & 1 belongs to stage k)
-  double gam[48], pv[24], q[24], bv[2 * 12], sig[24], w[48], dinv[24];
+  double gam[48], q[24], sig[24], w[48], dinv[24];      // (gam: the foot block of stage 0 only -- gamma of a stage is column 48 of G, p column 24 of P, b column 36 of A^)
   double red[(SOLVER_THREADS / 64) * 9];      // (the fused first-trial pass reduces 3 line-search sums + 6 quantities of the new point at once)
   double filt_th[FILT_CAP], filt_ph[FILT_CAP];
   double prof[32];
@@ -403,7 +403,7 @@ __device__ __forceinline__ void asm_terms(int k, int nb, const AsmRegs& R) {
       acc = (dd & 1u) ? acc : 0.0;
     }
   }
-  if (tid < 12) { const int i = tid; S.bv[nb * 12 + (i < 6 ? i : (i < 9 ? i + 3 : i - 3))] = -R.g; }
+  if (tid < 12) { const int i = tid; S.Ah[nb * (12 * YS) + (i < 6 ? i : (i < 9 ? i + 3 : i - 3)) * YS + (YS - 1)] = -R.g; }
   if (tid < RCG) S.rcl[tid] = R.rc;      // gradient of the running cost (w order X, c, f): added to gamma when its tile is fetched
 }
 // (4) behind the next barrier: the destinations whose terms more than one thread summed
@@ -427,6 +427,17 @@ typedef double __attribute__((address_space(1)))* landing_gptr_w;
 #else
 typedef double* landing_gptr_w;
 #endif
+// A stage record's base as a global pointer in scalar registers (a __noinline__ phase receives its arguments in vector registers; the
+// pointer is the same in every lane): stores through it are global_store with a scalar base and a 32-bit lane offset
+__device__ __forceinline__ landing_gptr_w uniform_record(double* rec) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const unsigned long long a = (unsigned long long)rec;
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(a >> 32));
+  return (landing_gptr_w)((unsigned long long)lo | ((unsigned long long)hi << 32));
+#else
+  return rec;
+#endif
+}
 
 // Elimination of the controls of one stage on the matrix cores (waves 0..2): blocked Gauss-Jordan with
 // 4 x 4 pivot blocks on the (NU + 24) x (NU + 25) array  [G_uu G_us gamma_u ; G_su G_ss gamma_s]  (rows/columns: controls
@@ -511,46 +522,67 @@ __device__ __forceinline__ bool pivot_block_step(f64x4 (&T)[3], int ct, int lj, 
   return ok;                                             // identical in every lane of the workgroup (tested after the update so
 }                                                        // that the operand fetches are not held behind it)
 
-// (`k` = stage, its copy of A^ / b is k & 1; the assembly of stage k - 1 rides along)
+// (`k` = stage, its copy of A^ | b is k & 1; the assembly of stage k - 1 rides along)
+//
+// Where the operands sit (the host's assembly tables, solver_capi.inc, and the epilogue below write them there):
+//  * G holds the condensed stage array in ELIMINATION order -- rows / columns (f, c+, sigma), upper triangle --
+//    with gamma in the spare column GS - 1 = 48.  Element (rho, c) of the symmetric array [G | gamma] is therefore
+//    G[min(rho, c) * GS + max(rho, c)] = G[48 min(rho, c) + rho + c] for the columns of G AND for the gamma lane (c = 48).  The last
+//    stage (no c+) uses the same positions, its rows / columns skip the c+ range: the patterns of the stages still nest along the sweep.
+//  * P carries p in its spare column PS - 1 = 24, A^ carries b in its spare column YS - 1 = 36: the gamma lane reads its operands
+//    with the formula of the other lanes, at a column of its own.
+// Every fetch below is then ONE per-lane base, formed here once from (lj, lk, ct), plus a compile-time offset; a lane without an operand
+// (dead column, structural zero) loads from a clamped column and drops the value under a lane mask.  Until round 8 every fetch chose
+// its index through nested conditions on the lane, which the compiler turned into about 30 instructions of exec-mask branches per load.
+constexpr int G_GAMMA = GS - 1, P_PV = PS - 1, AH_B = YS - 1;
+static_assert(G_GAMMA == 48 && P_PV == 24 && AH_B == 36, "spare columns of G / P / A^ hold gamma / p / b");
 template <int NU>
-__device__ __noinline__ bool block_eliminate(double* __restrict__ rec, double delta, int k) {
+__device__ __noinline__ bool block_eliminate(double* __restrict__ rec_, double delta, int k) {
   Lds& S = SH;
   constexpr int NR = NU + 24;                         // rows; column NR is gamma
   const int tid = threadIdx.x, ct = tid >> 6, l = tid & 63, lj = l & 15, lk = l >> 4;
   const int c = 16 * ct + lj;
   const bool isg = (c == NR), live = (c <= NR);
-  const int bcol = c < NU ? 24 + c : (c < NR ? c - NU : 0);        // position of the own column in the (sigma, f, c+) order of G
   const int cb = k & 1;
-  const double* Ah = S.Ah + cb * (12 * YS);
-  const double* bv = S.bv + cb * 12;
   f64x4 T[3];
-  // Every operand of the prologue is ONE unconditional LDS load: where a lane has no operand (dead column, row outside the array, structural zero)
-  // the index points at a slot that holds 0.0 (cx's constant).  Written as `cond ? S.Ah[i] : 0.0` the compiler turned each of the ~40 operand fetches
-  // into a branch around a load with a wait behind it -- a chain of LDS round trips, 1.4 us of the 7 us a stage takes (round 5).
   const double* const lds0 = reinterpret_cast<const double*>(&S);
-  const int oG = (int)(offsetof(Lds, G) / sizeof(double)), oGam = (int)(offsetof(Lds, gam) / sizeof(double)), oP = (int)(offsetof(Lds, P) / sizeof(double)),
-            oPv = (int)(offsetof(Lds, pv) / sizeof(double)), oAh = (int)(offsetof(Lds, Ah) / sizeof(double)) + cb * (12 * YS), oBv = (int)(offsetof(Lds, bv) / sizeof(double)) + cb * 12,
-            oZ = (int)(offsetof(Lds, jhl) / sizeof(double)) + CX_ZERO;
-  {   // tile fetch: every lane walks its own column of the condensed G (the assembly fills the upper triangle only) / of gamma; delta_w on the diagonal
+  constexpr int oG = (int)(offsetof(Lds, G) / sizeof(double)), oP = (int)(offsetof(Lds, P) / sizeof(double));
+  const int oAh = (int)(offsetof(Lds, Ah) / sizeof(double)) + cb * (12 * YS);
+  // per-lane columns and masks, once: position of the own column in G; its column of A^ | b (state and force columns, b for gamma); its
+  // column of P | p (columns of c+, p for gamma)
+  const int cl = c < NR ? c : NR;
+  const int cp = NU == 24 ? cl : (cl < NU ? cl : cl + (24 - NU));
+  const bool ym = live && (c < 12 || c >= NU);
+  int ycol = c < NU ? c + 24 : c - NU;
+  ycol = ym ? (isg ? AH_B : ycol) : 0;
+  const bool pm = live && c >= 12 && (c < NU || isg);
+  const int pcol = pm ? (isg ? P_PV : c) : 0;
+  {   // tile fetch: every lane walks its own column of [G | gamma]; delta_w on the diagonal
+    const int gb = oG + cp + lk * GS, cd = cp - lk, cm = c - lk;
 #pragma unroll
     for (int rt = 0; rt < 3; ++rt)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int rho = 16 * rt + lk + 4 * r;
-        const int a = rho < NU ? 24 + rho : (rho < NR ? rho - NU : 0);
-        const bool in = live && rho < NR;
-        const double v = lds0[in ? (isg ? oGam + a : oG + (a < bcol ? a * GS + bcol : bcol * GS + a)) : oZ] + (rho == c ? delta : 0.0);
-        T[rt][r] = in ? v : 0.0;
+        const int rb = 16 * rt + 4 * r;                                  // (compile-time after unrolling) row rho = rb + lk
+        if (rb < NR) {
+          const int rp = NU == 24 ? rb : (rb < NU ? rb : rb + (24 - NU));      // its position in G, less lk
+          const int m = rp < cd ? rp : cd;
+          const double v = lds0[gb + rp + (GS - 1) * m] + (cm == rb ? delta : 0.0);
+          T[rt][r] = live ? v : 0.0;
+        } else T[rt][r] = 0.0;
       }
     if (S.rc_on) {      // (uniform) + gradient of the running cost of the stage's variables (X, c, f) in the column of gamma
 #pragma unroll
       for (int rt = 0; rt < 3; ++rt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int rho = 16 * rt + lk + 4 * r;
-          const int a = rho < NU ? 24 + rho : (rho < NR ? rho - NU : 0);
-          const double g = S.rcl[a < RCG ? a : 0];
-          T[rt][r] += (isg && rho < NR && a < RCG) ? g : 0.0;
+          const int rb = 16 * rt + 4 * r;
+          if (rb < NR) {
+            const int ab = rb < NU ? 24 + rb : rb - NU;                  // index of row rb in the (sigma, f, c+) order of the gradient
+            static_assert(RCG % 4 == 0 && NU % 4 == 0, "a group of four rows lies on one side of every border");
+            const double g = ab < RCG ? S.rcl[ab + lk] : 0.0;
+            T[rt][r] += isg ? g : 0.0;
+          }
         }
     }
   }
@@ -558,29 +590,36 @@ __device__ __noinline__ bool block_eliminate(double* __restrict__ rec, double de
       // A_ext = [A^ | b] (12 rows) the own column of Y = P(:,0:12) A_ext comes out of the matrix cores in accumulator
       // layout, which IS the B-operand layout of the next product (row 4kt+k of k-step kt sits in lane group k):
       // Y never touches LDS.  Columns of c+ and the p-part of gamma enter P T directly.
-    const bool cplus = live && !isg && bcol >= 36;
     double be[3];
+    {
+      const int yb = oAh + lk * YS + ycol;
 #pragma unroll
-    for (int kt = 0; kt < 3; ++kt) be[kt] = lds0[isg ? oBv + 4 * kt + lk : ((live && bcol < 36) ? oAh + (4 * kt + lk) * YS + bcol : oZ)];
+      for (int kt = 0; kt < 3; ++kt) { const double v = lds0[yb + 4 * kt * YS]; be[kt] = ym ? v : 0.0; }
+    }
     double pa1[3], add1[3];
 #pragma unroll
     for (int kt = 0; kt < 3; ++kt) pa1[kt] = lds0[oP + lj * PS + 4 * kt + lk];
+    const int pb = oP + lk * PS + pcol;
 #pragma unroll
-    for (int r = 0; r < 3; ++r) { const int row = lk + 4 * r; add1[r] = lds0[cplus ? oP + row * PS + 12 + bcol - 36 : (isg ? oPv + row : oZ)]; }
+    for (int r = 0; r < 3; ++r) { const double v = lds0[pb + 4 * r * PS]; add1[r] = pm ? v : 0.0; }
     double av[3][3];
 #pragma unroll
     for (int rt = 0; rt < 3; ++rt) {
       const int rho = 16 * rt + lj;
-      const int a = rho < NU ? 24 + rho : (rho < NR ? rho - NU : 99);
+      const int a = rho < NU ? 24 + rho : (rho < NR ? rho - NU : 36);      // column of A^ that belongs to row rho (none for the rows of c+ and the dead rows)
+      const bool am = a < 36;
+      const int ab = oAh + lk * YS + (am ? a : 0);
 #pragma unroll
-      for (int kt = 0; kt < 3; ++kt) av[rt][kt] = lds0[a < 36 ? oAh + (4 * kt + lk) * YS + a : oZ];
+      for (int kt = 0; kt < 3; ++kt) { const double v = lds0[ab + 4 * kt * YS]; av[rt][kt] = am ? v : 0.0; }
     }
     double pa2[3], add2[3];
     if (NU == 24) {
+      // (A-operand rows 12..15 feed rows 12..15 of Y2, which nothing reads: those lanes re-read row 11 instead of a zero)
+      const int p2 = oP + (12 + (lj < 12 ? lj : 11)) * PS + lk;
 #pragma unroll
-      for (int kt = 0; kt < 3; ++kt) pa2[kt] = lds0[lj < 12 ? oP + (12 + lj) * PS + 4 * kt + lk : oZ];
+      for (int kt = 0; kt < 3; ++kt) pa2[kt] = lds0[p2 + 4 * kt];
 #pragma unroll
-      for (int r = 0; r < 3; ++r) { const int row = 12 + lk + 4 * r; add2[r] = lds0[cplus ? oP + row * PS + 12 + bcol - 36 : (isg ? oPv + row : oZ)]; }
+      for (int r = 0; r < 3; ++r) { const double v = lds0[pb + (12 + 4 * r) * PS]; add2[r] = pm ? v : 0.0; }
     }
     f64x4 Y1 = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -625,39 +664,38 @@ __device__ __noinline__ bool block_eliminate(double* __restrict__ rec, double de
   }
 #undef ASM_HOOK
   if (!ok) return false;                                 // (identical in every lane)
-  {   // closed-loop state map for the forward sweep: X+ = A^_sigma sigma + A^_f f + b with f = -(K_f sigma + kappa_f), i.e.
-      // Mt = A^_sigma - A^_f K_f, mv = b - A^_f kappa_f.  K_f / kappa_f are rows 0..11 of the first row tile, already in
-      // B-operand layout (k-step kt = accumulator kt).
-    f64x4 Mq = {0.0, 0.0, 0.0, 0.0};
+  // closed-loop state map for the forward sweep: X+ = A^_sigma sigma + A^_f f + b with f = -(K_f sigma + kappa_f), i.e.
+  // Mt = A^_sigma - A^_f K_f, mv = b - A^_f kappa_f.  K_f / kappa_f are rows 0..11 of the first row tile, already in
+  // B-operand layout (k-step kt = accumulator kt).  (Rows 12..15 of the product are not read: their lanes re-read row 11 of A^.)
+  f64x4 Mq = {0.0, 0.0, 0.0, 0.0};
+  {
+    const int fb = oAh + (lj < 12 ? lj : 11) * YS + 24 + lk;
 #pragma unroll
-    for (int kt = 0; kt < 3; ++kt) {
-      const double af = lds0[lj < 12 ? oAh + lj * YS + 24 + 4 * kt + lk : oZ];
-      Mq = __builtin_amdgcn_mfma_f64_16x16x4f64(af, T[0][kt], Mq, 0, 0, 0);
-    }
-    if (c >= NU && c <= NR) {
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        const int i = lk + 4 * r;
-        if (c < NR) rec[RIC_MT + i * 24 + (c - NU)] = Ah[i * YS + (c - NU)] - Mq[r];
-        else rec[RIC_MV + i] = bv[i] - Mq[r];
-      }
-    }
+    for (int kt = 0; kt < 3; ++kt) Mq = __builtin_amdgcn_mfma_f64_16x16x4f64(lds0[fb + 4 * kt], T[0][kt], Mq, 0, 0, 0);
   }
-  // gains to the stage record, cost-to-go to LDS (+ its state rows to the record)
+  // Mt | mv and the gains to the stage record, cost-to-go to LDS (+ its state rows to the record).  Which field a row goes to is known
+  // per accumulator; a lane differs only in "state column or gamma", which is a base and a row stride of its own (K + sj, stride 24,
+  // against kappa, stride 1; alike Mt / mv and P_x / p): one store per accumulator under ONE lane mask.  Wave 0 (columns < NU) skips it.
   if (c >= NU && c <= NR) {
-    const int sj = c - NU;
+    const unsigned sj = (unsigned)(c - NU), ulk = (unsigned)lk;
+    const unsigned rs = isg ? 1u : 24u;                                    // row stride in the record
+    const unsigned iK = (isg ? (unsigned)RIC_KAP : (unsigned)RIC_K + sj) + ulk * rs, iM = (isg ? (unsigned)RIC_MV : (unsigned)RIC_MT + sj) + ulk * rs,
+                   iP = (isg ? (unsigned)RIC_PV : (unsigned)RIC_PX + sj) + ulk * rs;
+    const int scol = isg ? AH_B : (int)sj, pcw = isg ? P_PV : (int)sj;      // the own column of A^ | b and of P | p
+    landing_gptr_w rec = uniform_record(rec_);
+    double* const Pw = S.P + lk * PS + pcw;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) rec[iM + (unsigned)(4 * r) * rs] = lds0[oAh + (lk + 4 * r) * YS + scol] - Mq[r];
 #pragma unroll
     for (int rt = 0; rt < 3; ++rt)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int rho = 16 * rt + lk + 4 * r;
+        const int rb = 16 * rt + 4 * r;                                    // (compile-time) row rho = rb + lk
         const double v = T[rt][r];
-        if (rho < NU) {
-          if (c < NR) rec[RIC_K + rho * 24 + sj] = v; else rec[RIC_KAP + rho] = v;
-        } else if (rho < NR) {
-          const int i = rho - NU;
-          if (c < NR) { S.P[i * PS + sj] = v; if (i < 12) rec[RIC_PX + i * 24 + sj] = v; }
-          else { S.pv[i] = v; if (i < 12) rec[RIC_PV + i] = v; }
+        if (rb < NU) rec[iK + (unsigned)rb * rs] = v;
+        else if (rb < NR) {
+          Pw[(rb - NU) * PS] = v;
+          if (rb - NU < 12) rec[iP + (unsigned)(rb - NU) * rs] = v;
         }
       }
   }
@@ -692,16 +730,15 @@ __device__ __noinline__ bool riccati_backward(double delta) {
     const int ra = i < 6 ? 12 + i : 24 + (i - 6), rb = i < 6 ? 18 + i : 30 + (i - 6);
     const double qn2 = S.ks.feas ? 0.0 : 2.0 * p[L.o_QN + i];      // (the feasibility phase has no objective)
     S.P[i * PS + i] = qn2 + M.sig[ra] + M.sig[rb] + delta;
-    S.pv[i] = qn2 * (M.x[12 * N + i] - p[12 * N + i]) + M.rho[ra] + M.rho[rb];
+    S.P[i * PS + P_PV] = qn2 * (M.x[12 * N + i] - p[12 * N + i]) + M.rho[ra] + M.rho[rb];      // p_N in the spare column of P (rows 12..23 stay 0)
     double* rec = M.ric + (size_t)N * RIC_STRIDE;      // record N: P_N (diag), p_N
     for (int j = 0; j < 24; ++j) rec[RIC_PX + i * 24 + j] = (j == i) ? S.P[i * PS + i] : 0.0;
-    rec[RIC_PV + i] = S.pv[i];
+    rec[RIC_PV + i] = S.P[i * PS + P_PV];
   }
   // background of the condensed stage data: the scatter below writes the structural nonzeros only (the patterns
   // of the stages nest along the sweep unless the tables say otherwise), nothing else writes G / A^ any more
   for (int e = lane; e < 48 * GS; e += NT) S.G[e] = 0.0;
   for (int e = lane; e < 2 * 12 * YS; e += NT) S.Ah[e] = 0.0;
-  if (lane < 24) S.pv[lane] = (lane < 12) ? S.pv[lane] : 0.0;
   __syncthreads();
   {   // the only exposed assembly of the sweep
     AsmRegs first;
@@ -732,7 +769,7 @@ __device__ __noinline__ bool riccati_backward(double delta) {
     for (int e = lane; e < 144; e += NT) { const int i = e / 12, j = e % 12; S.G[(24 + i) * GS + 24 + j] = S.P[(12 + i) * PS + 12 + j]; }
     __syncthreads();
     if (lane < 12) {
-      double v = S.pv[12 + lane];
+      double v = S.P[(12 + lane) * PS + P_PV];
       for (int t = 0; t < 12; ++t) v += S.P[(12 + lane) * PS + t] * S.sig[t];
       S.gam[24 + lane] = v;
     }

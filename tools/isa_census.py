@@ -1,0 +1,146 @@
+#!/usr/bin/env python3
+"""Instruction census of the gfx950 code the product library is built from (needs hipcc, no GPU).
+
+Compiles landing-controller_amd/csrc/capi.hip to assembly with the flags of csrc/Makefile (device side only) and prints, for every
+function whose demangled name contains one of --match (default: the solver kernel and the phases of its backward sweep), what the
+function is made of: instructions, instructions up to the first matrix-core instruction (operand fetch), instructions behind the last
+barrier (write-out), MFMA / LDS / flat / global / branch counts, vector registers and the private segment.  For kernels the LDS block
+and the private segment of the kernel descriptor are added.
+
+    python tools/isa_census.py [--label NAME] [--match SUBSTR ...] [--asm FILE.s] [--json OUT.json]
+
+--asm reads an assembly file made earlier instead of compiling.  --json merges the result under --label into OUT.json (so that the
+census of two source states can sit side by side in one file, profiles/r08_isa_census.json).
+"""
+import argparse
+import json
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "landing-controller_amd", "csrc")
+DEFAULT_MATCH = ["block_eliminate", "riccati_backward", "landing_ipm_kernel", "forward_pass"]
+
+
+def makefile_flags():
+    """ARCH, CXXFLAGS and HIPFLAGS as csrc/Makefile sets them"""
+    var = {}
+    for line in open(os.path.join(CSRC, "Makefile")):
+        m = re.match(r"^(\w+)\s*[:?]?=\s*(.*)$", line.rstrip("\n"))
+        if m:
+            var[m.group(1)] = m.group(2).strip()
+    return var.get("HIPCC", "/opt/rocm/bin/hipcc"), var.get("ARCH", "gfx950"), var["CXXFLAGS"].split(), var["HIPFLAGS"].split()
+
+
+def compile_asm(out):
+    hipcc, arch, cxx, hip = makefile_flags()
+    hipcc = os.environ.get("HIPCC", hipcc)
+    cmd = [hipcc, "--offload-arch=" + arch] + cxx + hip + ["--cuda-device-only", "-S", "-o", out, os.path.join(CSRC, "capi.hip")]
+    subprocess.run(cmd, check=True, cwd=CSRC, stderr=subprocess.DEVNULL)
+    return " ".join(cmd[:-3] + ["capi.hip"]).replace(hipcc, "hipcc")
+
+
+def demangle(names):
+    try:
+        out = subprocess.run(["c++filt"] + names, check=True, capture_output=True, text=True).stdout.split("\n")
+        return dict(zip(names, out))
+    except (OSError, subprocess.CalledProcessError):
+        return {n: n for n in names}
+
+
+INSTR = re.compile(r"^\t([a-z][a-z0-9_]+)(\s|$)")
+KD = re.compile(r"^\t\t\.amdhsa_(group_segment_fixed_size|private_segment_fixed_size|next_free_vgpr|accum_offset)\s+(\d+)")
+
+
+def census(path, match):
+    lines = open(path, errors="replace").read().split("\n")
+    funcs, kd = {}, {}
+    i, n = 0, len(lines)
+    while i < n:
+        m = re.match(r"^\t\.type\t(\S+),@function", lines[i])
+        if m:
+            name = m.group(1)
+            body, j = [], i + 1
+            while j < n and not lines[j].startswith(".Lfunc_end"):
+                mm = KD.match(lines[j])      # (a kernel's descriptor sits between its s_endpgm and the end label)
+                if mm:
+                    kd.setdefault(name, {})[mm.group(1)] = int(mm.group(2))
+                body.append(lines[j]); j += 1
+            info = {}
+            while j < n and not lines[j].startswith("; MemoryBound") and not re.match(r"^\t\.type\t\S+,@function", lines[j]):
+                mm = re.match(r"^; (NumVgprs|NumAgprs|ScratchSize|codeLenInByte)\s*[:=]\s*(\d+)", lines[j])
+                if mm:
+                    info[mm.group(1)] = int(mm.group(2))
+                j += 1
+            funcs[name] = (body, info)
+            i = j
+            continue
+        i += 1
+    pretty = demangle(list(funcs))
+    out = {}
+    for name, (body, info) in funcs.items():
+        if not any(s in pretty[name] for s in match):
+            continue
+        ops = [m.group(1) for m in (INSTR.match(b) for b in body) if m]
+        first_mfma = next((k for k, o in enumerate(ops) if o.startswith("v_mfma")), None)
+        last_bar = max((k for k, o in enumerate(ops) if o == "s_barrier"), default=None)
+        cnt = lambda f: sum(1 for o in ops if f(o))
+        fp64 = {k: cnt(lambda o, k=k: o.startswith("v_" + k + "_f64")) for k in ("fma", "mul", "add", "rcp")}
+        row = {
+            "instructions": len(ops),
+            "to_first_mfma": first_mfma,
+            "behind_last_barrier": None if last_bar is None else len(ops) - 1 - last_bar,
+            "mfma": cnt(lambda o: o.startswith("v_mfma")),
+            "fp64_valu": fp64,
+            "lds_read": cnt(lambda o: o.startswith("ds_read") or o.startswith("ds_load")),
+            "lds_write": cnt(lambda o: o.startswith("ds_write") or o.startswith("ds_store")),
+            "flat_load": cnt(lambda o: o.startswith("flat_load")), "flat_store": cnt(lambda o: o.startswith("flat_store")),
+            "global_load": cnt(lambda o: o.startswith("global_load")), "global_store": cnt(lambda o: o.startswith("global_store")),
+            "scratch": cnt(lambda o: o.startswith("scratch_") or o.startswith("buffer_")),
+            "branch": cnt(lambda o: o.startswith("s_cbranch") or o == "s_branch"),
+            "v_cmp": cnt(lambda o: o.startswith("v_cmp")), "v_cndmask": cnt(lambda o: o.startswith("v_cndmask")),
+            "exec_mask_salu": cnt(lambda o: re.match(r"s_(and|or|xor|andn2|orn2)(_saveexec)?_b64", o) is not None),
+            "int_address_valu": cnt(lambda o: re.match(r"v_(add_u32|sub_u32|subrev_u32|add_co_u32|mad_u32_u24|mul_u32_u24|mad_u64_u32|lshl|lshr|ashr|or_b32|and_b32|and_or|add3|add_lshl|lshl_add|lshl_or|min_[iu]32|max_[iu]32)", o) is not None),
+            "barrier": cnt(lambda o: o == "s_barrier"),
+            "vgprs": info.get("NumVgprs"), "private_segment": info.get("ScratchSize"), "code_bytes": info.get("codeLenInByte"),
+        }
+        if name in kd:
+            row["kernel_descriptor"] = kd[name]
+        out[pretty[name]] = row
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--label", default="worktree")
+    ap.add_argument("--match", nargs="*", default=DEFAULT_MATCH)
+    ap.add_argument("--asm", default="")
+    ap.add_argument("--json", default="")
+    a = ap.parse_args()
+    if a.asm:
+        res, how = census(a.asm, a.match), "read from " + os.path.basename(a.asm)
+    else:
+        with tempfile.TemporaryDirectory() as d:
+            s = os.path.join(d, "capi.s")
+            how = compile_asm(s)
+            res = census(s, a.match)
+    keys = ["instructions", "to_first_mfma", "behind_last_barrier", "mfma", "lds_read", "lds_write", "flat_load", "flat_store", "global_load", "global_store",
+            "branch", "vgprs", "private_segment"]
+    print("%-58s" % "function" + "".join(" %9s" % k[:9] for k in keys))
+    for f, row in sorted(res.items()):
+        print("%-58s" % f[:58] + "".join(" %9s" % ("-" if row[k] is None else row[k]) for k in keys))
+        if "kernel_descriptor" in row:
+            print("    kernel descriptor: " + ", ".join("%s %d" % kv for kv in sorted(row["kernel_descriptor"].items())))
+    if a.json:
+        doc = json.load(open(a.json)) if os.path.exists(a.json) else {}
+        doc[a.label] = {"how": how, "functions": res}
+        json.dump(doc, open(a.json, "w"), indent=1, sort_keys=True)
+        open(a.json, "a").write("\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
