@@ -522,6 +522,26 @@ int landing_riccati_gains_batch(landing_ctx* ctx, int B, int n, const double* d_
                                 const double* Ib3x3, double mass, const double* Q, const double* r_diag, const double* F,
                                 double dt, int rk4, double* d_P, double* d_K, double* d_A, double* d_B, void* stream);
 
+/* The same straight from a solved batch, on the device (quadruped_SRBM_NLP.m:487-499 puts the solution onto the controller's grid).
+ *   d_x [B][nx]: solutions in the solver's layout; d_p [B][np]: their parameters -- the time grid is the member's own dt inside p, in the parameter
+ *   layout of the context; dt_r > 0, n >= 2: step and number of points of the uniform Riccati grid; N <= 96.
+ * landing_sample_reference_batch: d_xref [B][n][24] = the interpolation of [X*(1:12); U*(1:12)] between knots, d_fref [B][n][12] = the forces
+ *   U*(13:24) held over their interval (either may be NULL).  As in the reference, the knot search never enters the LAST interval: grid points
+ *   beyond the second-to-last knot extrapolate the second-to-last interval and hold its forces.
+ * landing_tracking_gains_batch: the resampling and then landing_riccati_gains_batch (step dt_r) on one stream, no host read in between.  Outputs as
+ *   there (any may be NULL); d_xref / d_fref NULL: the reference stays in a block of the context.  d_status [B] (may be NULL): members whose status
+ *   is not LANDING_CONVERGED get zeros in every requested output, so a whole solved batch can be handed over; the others are unaffected.
+ * landing_tracking_gains_host: the same with host arrays (blocking).
+ * n < 2, dt_r <= 0, NULL x / p or no output requested: LANDING_E_ARG before anything is launched. */
+int landing_sample_reference_batch(landing_ctx* ctx, int B, const double* d_x, const double* d_p, double dt_r, int n,
+                                   double* d_xref, double* d_fref, void* stream);
+int landing_tracking_gains_batch(landing_ctx* ctx, int B, const double* d_x, const double* d_p, const int* d_status /* may be NULL */,
+                                 double dt_r, int n, const double* Ib3x3, double mass, const double* Q, const double* r_diag, const double* F, int rk4,
+                                 double* d_P, double* d_K, double* d_A, double* d_B, double* d_xref, double* d_fref, void* stream);
+int landing_tracking_gains_host(landing_ctx* ctx, int B, const double* x, const double* p, const int* status /* may be NULL */,
+                                double dt_r, int n, const double* Ib3x3, double mass, const double* Q, const double* r_diag, const double* F, int rk4,
+                                double* P, double* K, double* A, double* Bm, double* xref, double* fref);
+
 /* Receding-horizon loop (BASELINE configs[4]: 100 Hz warm-started re-solves).  One control tick =
  *   landing_mpc_shift(previous solution, measured states) -> x0, p;  landing_solve_batch(p, x0, warm-start options).
  * landing_mpc_shift: x0 = previous solution advanced by one stage (last column held) with d_state [B][12] = measured

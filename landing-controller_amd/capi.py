@@ -76,7 +76,8 @@ EXPORTS = ["landing_last_error", "landing_form_default", "landing_solver_opts_de
            "landing_np_ccc", "landing_ctx_np", "landing_pack_args25", "landing_solve_args25", "landing_riccati_gains_batch", "landing_mpc_shift", "landing_solver_opts_warm", "landing_rbd_set_model", "landing_fb_dynamics_batch",
            "landing_kinodyn_rows_batch", "landing_kinodyn_nlp_dims", "landing_kinodyn_nlp_eval", "landing_kinodyn_nlp_hess", "landing_leg_ik_batch", "landing_nnz_hess_rc", "landing_pattern_hess_rc",
            "landing_eval_hess_rc_batch", "landing_eval_hess_rc_batch_host",
-           "landing_stream_create", "landing_stream_destroy", "landing_stream_lanes", "landing_stream_submit", "landing_stream_wait", "landing_stream_sync", "landing_solve_stream_host"]
+           "landing_stream_create", "landing_stream_destroy", "landing_stream_lanes", "landing_stream_submit", "landing_stream_wait", "landing_stream_sync", "landing_solve_stream_host",
+           "landing_sample_reference_batch", "landing_tracking_gains_batch", "landing_tracking_gains_host"]
 
 
 # Sizes the solver kernel's workspace layout is built from (csrc/solver_kernels.hip: RUNC, RIC_STRIDE, RCG, EXIT_REC)
@@ -148,6 +149,11 @@ def load(path=None):
     lib.landing_pack_args21.argtypes = [C.c_int, C.c_int, C.POINTER(Args21), _dp]
     lib.landing_solve_args21.argtypes = [vp, C.c_int, C.POINTER(Args21), C.POINTER(SolverOpts), _dp, _dp, _ip, _ip, _dp]
     lib.landing_riccati_gains_batch.argtypes = [vp, C.c_int, C.c_int, vp, vp, _dp, C.c_double, _dp, _dp, _dp, C.c_double, C.c_int, vp, vp, vp, vp, vp]
+    if hasattr(lib, "landing_tracking_gains_batch"):      # gains straight from a solved batch
+        lib.landing_sample_reference_batch.argtypes = [vp, C.c_int, vp, vp, C.c_double, C.c_int, vp, vp, vp]
+        gains = [C.c_double, C.c_int, _dp, C.c_double, _dp, _dp, _dp, C.c_int]      # dt_r n Ib3x3 mass Q r_diag F rk4
+        lib.landing_tracking_gains_batch.argtypes = [vp, C.c_int, vp, vp, vp] + gains + [vp] * 6 + [vp]
+        lib.landing_tracking_gains_host.argtypes = [vp, C.c_int, _dp, _dp, _ip] + gains + [_dp] * 6
     if hasattr(lib, "landing_mpc_shift"):
         lib.landing_mpc_shift.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     if hasattr(lib, "landing_solve_args25"):
@@ -457,6 +463,33 @@ class LandingLib:
         rc = self.lib.landing_riccati_gains_batch(self.ctx, B, n, d_xref, d_fref, _p(Ib3x3), float(mass), _p(Q), _p(r), _p(F), float(dt), int(bool(rk4)),
                                                   d_P or None, d_K or None, d_A or None, d_B or None, stream or None)
         self._check(rc, "landing_riccati_gains_batch")
+
+    def sample_reference_device(self, B, d_x, d_p, dt_r, n, d_xref=0, d_fref=0, stream=0):
+        """landing_sample_reference_batch: B solutions (solver layout) onto the uniform Riccati grid of n points, step dt_r, each member along the
+        time grid its own p carries (device pointers).  The last interval is never entered: points past the second-to-last knot extrapolate."""
+        rc = self.lib.landing_sample_reference_batch(self.ctx, B, d_x or None, d_p or None, float(dt_r), int(n), d_xref or None, d_fref or None, stream or None)
+        self._check(rc, "landing_sample_reference_batch")
+
+    def tracking_gains_device(self, B, d_x, d_p, dt_r, n, Ib3x3, mass, Q, r_diag, F, rk4=False, d_status=0, d_P=0, d_K=0, d_A=0, d_B=0, d_xref=0, d_fref=0, stream=0):
+        """landing_tracking_gains_batch: resampling + Riccati tracking gains of a solved batch on one stream (device pointers).  With d_status,
+        members that did not converge get zeros; d_xref / d_fref = 0 keeps the sampled reference in the context."""
+        Ib3x3 = np.ascontiguousarray(Ib3x3, float); Q = np.ascontiguousarray(Q, float); F = np.ascontiguousarray(F, float); r = np.ascontiguousarray(r_diag, float)
+        rc = self.lib.landing_tracking_gains_batch(self.ctx, B, d_x or None, d_p or None, d_status or None, float(dt_r), int(n), _p(Ib3x3), float(mass), _p(Q), _p(r), _p(F),
+                                                   int(bool(rk4)), d_P or None, d_K or None, d_A or None, d_B or None, d_xref or None, d_fref or None, stream or None)
+        self._check(rc, "landing_tracking_gains_batch")
+
+    def tracking_gains_host(self, x, p, dt_r, n, Ib3x3, mass, Q, r_diag, F, rk4=False, status=None, want=("K",)):
+        """landing_tracking_gains_host: numpy in / numpy out; want: any of P, K, A, B, xref, fref"""
+        x = np.ascontiguousarray(np.atleast_2d(x), float); p = np.ascontiguousarray(np.atleast_2d(p), float)
+        B = x.shape[0]
+        status = None if status is None else np.ascontiguousarray(status, np.int32)
+        Ib3x3 = np.ascontiguousarray(Ib3x3, float); Q = np.ascontiguousarray(Q, float); F = np.ascontiguousarray(F, float); r = np.ascontiguousarray(r_diag, float)
+        shapes = dict(P=(B, n, 24, 24), K=(B, n, 12, 24), A=(B, n, 24, 24), B=(B, n, 24, 12), xref=(B, n, 24), fref=(B, n, 12))
+        out = {k: (np.full(shapes[k], np.nan) if k in want else None) for k in shapes}
+        rc = self.lib.landing_tracking_gains_host(self.ctx, B, _p(x), _p(p), None if status is None else status.ctypes.data_as(_ip), float(dt_r), int(n), _p(Ib3x3),
+                                                  float(mass), _p(Q), _p(r), _p(F), int(bool(rk4)), *[_p(out[k]) for k in ("P", "K", "A", "B", "xref", "fref")])
+        self._check(rc, "landing_tracking_gains_host")
+        return {k: v for k, v in out.items() if v is not None}
 
     # ---- device-pointer entry points (integers = device addresses, e.g. torch tensor.data_ptr()) --
     def eval_device(self, B, d_x, d_p, d_lam_f=0, d_lam_g=0, d_f=0, d_g=0, d_grad_f=0, d_jac=0, d_hess=0, d_ggx=0, d_ggp=0, stream=0):

@@ -86,6 +86,7 @@ struct landing_ctx {
   double* d_prof = nullptr;     // the caller's (landing_set_profile_buffer)
   DevBuf<double> d_vbl;
   double* h_vbl = nullptr; hipEvent_t vbl_copied = nullptr;      // pinned staging block of landing_riccati_gains_batch and the event behind its copy
+  DevBuf<double> d_gref;      // landing_tracking_gains_batch (gains_capi.inc): [xref B x n x 24 | fref B x n x 12] when the caller keeps neither, grown on demand
   DevBuf<landing::RbdModel> d_rbd;     // uploaded by landing_rbd_set_model
   DevBuf<int2> d_rc_map;               // landing_eval_hess_rc_batch: source nonzero + running-cost code of every entry of the extended pattern
   DevBuf<double> d_fb_scratch;         // qdd and H^-1 per knot of the exact floating-base linearisation
@@ -494,3 +495,4 @@ int landing_bounds_batch(landing_ctx* ctx, int B, const double* d_p, double* d_l
 #include "kd_capi.inc"
 #include "kd_casadi_capi.inc"
 #include "pipeline_capi.inc"
+#include "gains_capi.inc"

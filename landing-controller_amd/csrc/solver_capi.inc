@@ -568,25 +568,23 @@ int landing_solve_21(landing_ctx* ctx, int B, const double* Xref, const double* 
 }
 
 // ---- SRBM variational linearisation + Riccati tracking gains (vbl_kernels.hip) ----------------------------------------
-int landing_riccati_gains_batch(landing_ctx* ctx, int B, int n, const double* d_xref, const double* d_fref,
-                                const double* Ib3x3, double mass, const double* Q, const double* r_diag, const double* F,
-                                double dt, int rk4, double* d_P, double* d_K, double* d_A, double* d_B, void* stream) {
-  if (ctx && B == 0) return 0;
-  if (!ctx || B < 0 || n < 1 || !d_xref || !d_fref || !Ib3x3 || !(mass > 0.0) || !Q || !r_diag) return fail(LANDING_E_ARG, "landing_riccati_gains_batch: bad argument");
-  HIP_TRY(hipSetDevice(ctx->device));
-  landing::RdeArgs a;
-  a.B = B; a.n = n; a.rk4 = rk4 ? 1 : 0; a.dt = dt; a.xref = d_xref; a.fref = d_fref; a.P = d_P; a.K = d_K; a.Aout = d_A; a.Bout = d_B;
-  {  // inverse of the 3 x 3 inertia (adjugate)
-    const double* I = Ib3x3; double* J = a.C.Ibi;
-    const double det = I[0] * (I[4] * I[8] - I[5] * I[7]) - I[1] * (I[3] * I[8] - I[5] * I[6]) + I[2] * (I[3] * I[7] - I[4] * I[6]);
-    if (!(fabs(det) > 0.0)) return fail(LANDING_E_ARG, "landing_riccati_gains_batch: singular inertia");
-    J[0] = (I[4] * I[8] - I[5] * I[7]) / det; J[1] = (I[2] * I[7] - I[1] * I[8]) / det; J[2] = (I[1] * I[5] - I[2] * I[4]) / det;
-    J[3] = (I[5] * I[6] - I[3] * I[8]) / det; J[4] = (I[0] * I[8] - I[2] * I[6]) / det; J[5] = (I[2] * I[3] - I[0] * I[5]) / det;
-    J[6] = (I[3] * I[7] - I[4] * I[6]) / det; J[7] = (I[1] * I[6] - I[0] * I[7]) / det; J[8] = (I[0] * I[4] - I[1] * I[3]) / det;
-    for (int i = 0; i < 9; ++i) a.C.Ib[i] = I[i];
-    a.C.inv_m = 1.0 / mass;
-  }
-  std::lock_guard<std::mutex> lock(ctx->mu);
+// the model and weight arguments the Riccati entry points share: checked, and the inertia, its inverse (adjugate) and 1/mass put into a.C
+static int vbl_model(const char* who, const double* Ib3x3, double mass, const double* Q, const double* r_diag, landing::RdeArgs& a) {
+  if (!Ib3x3 || !(mass > 0.0) || !Q || !r_diag) return fail(LANDING_E_ARG, std::string(who) + ": bad argument");
+  const double* I = Ib3x3; double* J = a.C.Ibi;
+  const double det = I[0] * (I[4] * I[8] - I[5] * I[7]) - I[1] * (I[3] * I[8] - I[5] * I[6]) + I[2] * (I[3] * I[7] - I[4] * I[6]);
+  if (!(fabs(det) > 0.0)) return fail(LANDING_E_ARG, std::string(who) + ": singular inertia");
+  J[0] = (I[4] * I[8] - I[5] * I[7]) / det; J[1] = (I[2] * I[7] - I[1] * I[8]) / det; J[2] = (I[1] * I[5] - I[2] * I[4]) / det;
+  J[3] = (I[5] * I[6] - I[3] * I[8]) / det; J[4] = (I[0] * I[8] - I[2] * I[6]) / det; J[5] = (I[2] * I[3] - I[0] * I[5]) / det;
+  J[6] = (I[3] * I[7] - I[4] * I[6]) / det; J[7] = (I[1] * I[6] - I[0] * I[7]) / det; J[8] = (I[0] * I[4] - I[1] * I[3]) / det;
+  for (int i = 0; i < 9; ++i) a.C.Ib[i] = I[i];
+  a.C.inv_m = 1.0 / mass;
+  for (int i = 0; i < 12; ++i) if (!(r_diag[i] > 0.0)) return fail(LANDING_E_ARG, std::string(who) + ": R must be positive");
+  return 0;
+}
+
+// uploads the weights and launches landing_rde_kernel on `stream`.  Call with ctx->mu held and the device selected; `a` is complete but for Q / F / rinv.
+static int vbl_launch(landing_ctx* ctx, landing::RdeArgs& a, const double* Q, const double* r_diag, const double* F, hipStream_t stream) {
   constexpr size_t VBL_N = 576 + 576 + 12;
   if (!ctx->d_vbl) HIP_TRY(ctx->d_vbl.alloc(VBL_N));
   // The weights travel through a PINNED staging block owned by the context, so the upload is a true asynchronous copy and the call returns
@@ -597,18 +595,30 @@ int landing_riccati_gains_batch(landing_ctx* ctx, int B, int n, const double* d_
     if (!ctx->vbl_copied) HIP_TRY(hipEventCreateWithFlags(&ctx->vbl_copied, hipEventDisableTiming));
     HIP_TRY(hipHostMalloc((void**)&ctx->h_vbl, VBL_N * sizeof(double), hipHostMallocDefault));
   } else HIP_TRY(hipEventSynchronize(ctx->vbl_copied));
-  for (int i = 0; i < 12; ++i) if (!(r_diag[i] > 0.0)) return fail(LANDING_E_ARG, "landing_riccati_gains_batch: R must be positive");
   double* host = ctx->h_vbl;
   for (int i = 0; i < 576; ++i) { host[i] = Q[i]; host[576 + i] = F ? F[i] : 0.0; }
   for (int i = 0; i < 12; ++i) host[1152 + i] = 1.0 / r_diag[i];
-  HIP_TRY(scratch_acquire(ctx, (hipStream_t)stream));      // the previous call's kernel (any stream) still reads Q / F / 1/R from the device block
-  HIP_TRY(hipMemcpyAsync(ctx->d_vbl.get(), host, VBL_N * sizeof(double), hipMemcpyHostToDevice, (hipStream_t)stream));
-  HIP_TRY(hipEventRecord(ctx->vbl_copied, (hipStream_t)stream));
+  HIP_TRY(scratch_acquire(ctx, stream));      // the previous call's kernel (any stream) still reads Q / F / 1/R from the device block
+  HIP_TRY(hipMemcpyAsync(ctx->d_vbl.get(), host, VBL_N * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipEventRecord(ctx->vbl_copied, stream));
   a.Q = ctx->d_vbl.get(); a.F = a.Q + 576; a.rinv = a.Q + 1152;
-  hipLaunchKernelGGL(landing::landing_rde_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(landing::landing_rde_kernel, dim3(a.B), dim3(256), 0, stream, a);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(scratch_release(ctx, (hipStream_t)stream));
+  HIP_TRY(scratch_release(ctx, stream));
   return 0;
+}
+
+int landing_riccati_gains_batch(landing_ctx* ctx, int B, int n, const double* d_xref, const double* d_fref,
+                                const double* Ib3x3, double mass, const double* Q, const double* r_diag, const double* F,
+                                double dt, int rk4, double* d_P, double* d_K, double* d_A, double* d_B, void* stream) {
+  if (ctx && B == 0) return 0;
+  if (!ctx || B < 0 || n < 1 || !d_xref || !d_fref) return fail(LANDING_E_ARG, "landing_riccati_gains_batch: bad argument");
+  landing::RdeArgs a;
+  a.B = B; a.n = n; a.rk4 = rk4 ? 1 : 0; a.dt = dt; a.xref = d_xref; a.fref = d_fref; a.P = d_P; a.K = d_K; a.Aout = d_A; a.Bout = d_B;
+  if (const int rc = vbl_model("landing_riccati_gains_batch", Ib3x3, mass, Q, r_diag, a)) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  return vbl_launch(ctx, a, Q, r_diag, F, (hipStream_t)stream);
 }
 
 // ---- receding-horizon shift of a solved batch (landing_mpc_shift_kernel) ---------------------------------------------------

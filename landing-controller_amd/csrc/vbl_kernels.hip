@@ -11,6 +11,8 @@
 // written out by hand (the reference differentiates the error dynamics symbolically -- they are linear in the error).
 //
 // State order [dp(3) deta(3) domega(3) dv(3) dpf(12)], control = the twelve ground-reaction force components.
+// landing_sample_reference_kernel (end of this file) puts a solved batch onto the Riccati grid (quadruped_SRBM_NLP.m:487-499), so that the
+// chain solve -> reference -> gains stays on the device.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -123,6 +125,7 @@ struct RdeArgs {
   double* P; double* K;                         // [B][n][576] row-major, [B][n][12*24] (may be null)
   double* Aout; double* Bout;                   // optional [B][n][576], [B][n][288]
   VblConst C;
+  const int* status = nullptr;                  // optional [B]: a member whose status is not 0 (LANDING_CONVERGED) gets zeros in every output
 };
 
 // One workgroup (256 threads) per trajectory.  Backward sweep j = n-1 .. 1:  P[j-1] = P[j] + dt * f(P[j]; ref_j)
@@ -134,6 +137,12 @@ __global__ void __launch_bounds__(256) landing_rde_kernel(RdeArgs a) {
   if (m >= a.B) return;
   const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, ti = w >> 1, tj = w & 1;
   double* Pm = a.P ? a.P + (size_t)m * a.n * VN * VN : nullptr;
+  if (a.status && a.status[m] != 0) {      // (the whole workgroup takes this branch: no barrier is skipped by a part of it)
+    const size_t o = (size_t)m * a.n;
+    for (size_t e = tid; e < (size_t)a.n * VN * VN; e += 256) { if (Pm) Pm[e] = 0.0; if (a.Aout) a.Aout[o * VN * VN + e] = 0.0; }
+    for (size_t e = tid; e < (size_t)a.n * VM * VN; e += 256) { if (a.K) a.K[o * VM * VN + e] = 0.0; if (a.Bout) a.Bout[o * VN * VM + e] = 0.0; }
+    return;
+  }
   for (int e = tid; e < VP * VLD; e += 256) { const int i = e / VLD, j = e % VLD; S.P[e] = (a.F && i < VN && j < VN) ? a.F[i * VN + j] : 0.0; }
   __syncthreads();
   for (int j = a.n - 1; j >= 0; --j) {
@@ -178,6 +187,72 @@ __global__ void __launch_bounds__(256) landing_rde_kernel(RdeArgs a) {
       for (int r = 0; r < 4; ++r) { const int e = (16 * ti + (l >> 4) + 4 * r) * VLD + 16 * tj + (l & 15); S.P[e] += a.dt * (acc[r] + k[r]) / 6.0; }
     }
     __syncthreads();
+  }
+}
+
+// ---- the Riccati reference straight from a solved batch ----------------------------------------------------------------------------------
+// quadruped_SRBM_NLP.m:487-499: grid point k (1-based) sits at t = (k-1) dt_r; k_opt is the first interval whose right knot is not before t,
+//   xd = ki [X*(:,k_opt); U*(1:12,k_opt)] + (1-ki) [X*(:,k_opt+1); U*(1:12,k_opt)],  ki = (t*(k_opt+1) - t) / (t*(k_opt+1) - t*(k_opt)),  ud = U*(13:24,k_opt),
+// with t* the running sum of the member's own dt (p at Layout::o_dt), summed left to right, one add per knot.
+// The search stops at k_opt < N-1, as the reference's does: it NEVER enters the last interval.  A sample beyond t*(N-1) extrapolates the
+// second-to-last interval (ki < 0) and holds the second-to-last force column.  That is the reference's behaviour, reproduced on purpose.
+// x [B][36N+12] is the solver's layout (X columns, then U columns).  One thread per output sample (member, grid point), SR_THREADS consecutive
+// samples per workgroup: the cumulative times of the members they belong to (at most SR_MEMB, since n >= 2) are staged in LDS once, every
+// thread searches its interval there, then the workgroup writes the 24 / 12 values of its samples as one contiguous run.
+constexpr int SR_NMAX = 96, SR_THREADS = 64, SR_MEMB = SR_THREADS / 2 + 1;
+
+struct SampleArgs {
+  int B, N, n, nx, np, o_dt; double dt_r;
+  const double* x; const double* p;             // [B][nx], [B][np]
+  const int* status;                            // optional [B]: members whose status is not 0 get zeros
+  double* xref; double* fref;                   // [B][n][24], [B][n][12] (either may be null)
+};
+
+__global__ void __launch_bounds__(SR_THREADS) landing_sample_reference_kernel(SampleArgs a) {
+  __shared__ double ts[SR_MEMB * (SR_NMAX + 1)];      // [member of the workgroup][knot], row stride N + 1
+  __shared__ double s_ki[SR_THREADS];
+  __shared__ int s_ko[SR_THREADS];                    // k_opt (1-based) of a sample; 0: masked member
+  const int tid = threadIdx.x, N = a.N, ld = N + 1;
+  const size_t total = (size_t)a.B * a.n, s0 = (size_t)blockIdx.x * SR_THREADS;
+  if (s0 >= total) return;
+  const int cnt = total - s0 < (size_t)SR_THREADS ? (int)(total - s0) : SR_THREADS;
+  const int m0 = (int)(s0 / a.n), nm = (int)((s0 + cnt - 1) / a.n) - m0 + 1;
+  for (int e = tid; e < nm * N; e += SR_THREADS) { const int i = e / N, k = e % N; ts[i * ld + 1 + k] = a.p[(size_t)(m0 + i) * a.np + a.o_dt + k]; }
+  __syncthreads();
+  if (tid < nm) {
+    double* t = ts + tid * ld;
+    double acc = 0.0;
+    t[0] = 0.0;
+    for (int k = 1; k <= N; ++k) { acc += t[k]; t[k] = acc; }
+  }
+  __syncthreads();
+  if (tid < cnt) {
+    const size_t s = s0 + tid;
+    const int m = (int)(s / a.n), j = (int)(s % a.n);
+    const double* t = ts + (m - m0) * ld;
+    const double tj = (double)j * a.dt_r;
+    int ko = 1;
+    while (tj > t[ko] && ko < N - 1) ++ko;
+    s_ki[tid] = (t[ko] - tj) / (t[ko] - t[ko - 1]);
+    s_ko[tid] = (a.status && a.status[m] != 0) ? 0 : ko;
+  }
+  __syncthreads();
+  const int oU = 12 * (N + 1);
+  if (a.xref) for (int e = tid; e < cnt * VN; e += SR_THREADS) {
+    const int i = e / VN, c = e % VN, ko = s_ko[i];
+    double v = 0.0;
+    if (ko) {
+      const double* xm = a.x + (size_t)((s0 + i) / a.n) * a.nx;
+      const double ki = s_ki[i];
+      const double lo = c < 12 ? xm[12 * (ko - 1) + c] : xm[oU + 24 * (ko - 1) + c - 12];      // the feet are U*(1:12, k_opt) on both sides
+      const double hi = c < 12 ? xm[12 * ko + c] : lo;
+      v = ki * lo + (1.0 - ki) * hi;
+    }
+    a.xref[s0 * VN + e] = v;
+  }
+  if (a.fref) for (int e = tid; e < cnt * VM; e += SR_THREADS) {
+    const int i = e / VM, c = e % VM, ko = s_ko[i];
+    a.fref[s0 * VM + e] = ko ? a.x[(size_t)((s0 + i) / a.n) * a.nx + oU + 24 * (ko - 1) + 12 + c] : 0.0;
   }
 }
 

@@ -11,6 +11,7 @@ the host enqueues one shift kernel and one solver launch per batch.
         u0 = ctl.first_controls()              # [B, 24] feet and forces applied during the tick
         x_meas = plant(ctl.predicted_next_state(), ...)   # the caller's plant / state estimator, [B, 12] on the device
         info = ctl.tick(x_meas)                # shift + warm-started solve; info: iterations, status, kkt
+        K = ctl.tracking_gains(0.02, 26, weights=(Q, r_diag, F))   # [B, 26, 12, 24] tracking gains along the current plan
 """
 import torch
 
@@ -49,3 +50,20 @@ class RecedingHorizon:
         self.lib.mpc_shift_device(self.B, self.x.data_ptr(), state.data_ptr(), self.p.data_ptr(), self.x0.data_ptr(), self.stream)
         self._solve(self.opts_warm)
         return dict(status=self.status, iters=self.iters, kkt=self.kkt, f=self.f)
+
+    def tracking_gains(self, dt_r, n, weights, Ib=None, mass=None, rk4=False, want_P=False):
+        """Tracking gains K [B, n, 12, 24] (and P [B, n, 24, 24] with want_P) along the current plan, on the uniform grid of n points with step
+        dt_r: the plan is resampled along each member's own dt and the Riccati sweep runs behind it on the loop's stream (device tensors;
+        nothing is copied to the host).  weights = (Q [24, 24], r_diag [12], F [24, 24]); Ib [3, 3] and mass default to the robot's.  Members
+        whose last solve did not converge get zeros."""
+        Q, r_diag, F = weights
+        if Ib is None or mass is None:
+            from .constants import composite_body_inertia, robot_constants
+            Ib = composite_body_inertia()[0:3, 0:3] if Ib is None else Ib
+            mass = robot_constants()[0] if mass is None else mass
+        f64 = dict(device=self.x.device, dtype=torch.float64)
+        K = torch.empty(self.B, n, 12, 24, **f64)
+        P = torch.empty(self.B, n, 24, 24, **f64) if want_P else None
+        self.lib.tracking_gains_device(self.B, self.x.data_ptr(), self.p.data_ptr(), dt_r, n, Ib, mass, Q, r_diag, F, rk4, d_status=self.status.data_ptr(),
+                                       d_P=P.data_ptr() if want_P else 0, d_K=K.data_ptr(), stream=self.stream)
+        return (K, P) if want_P else K
