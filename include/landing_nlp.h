@@ -827,6 +827,10 @@ int landing_set_profile_buffer(landing_ctx* ctx, double* d_prof);
  *   [5] it       iterations counted (= iters)   [6] omt   > 0: the clip_k rule was in force in the last step   [7] s_corr
  * tests/test_solver_step_cpu.py and tests/test_gpu_solver_step.py use it to check the step against an independent KKT solve. */
 int landing_debug_workspace(landing_ctx* ctx, double** d_ws, unsigned long long* stride);
+/* diagnostic: one of the tables the solver kernel reads, as the context holds it on the device (built here when no solve has run yet).
+ * which = 0 ctab, 1 ccomb, 2 ctype, 3 rterm, 4 the three ints {c_ml, c_mid, rlen}.  *n_bytes receives the table's size; host_out, when
+ * not NULL, receives that many bytes.  tests/test_solver_tables_cpu.py holds them against a recorded fixture. */
+int landing_debug_solver_tables(landing_ctx* ctx, int which, void* host_out, unsigned long long* n_bytes);
 
 /* name of the dominant kernels (for profilers) and per-launch algorithmic bytes of the sweep */
 const char* landing_kernel_name_sweep(void);

@@ -69,7 +69,7 @@ EXPORTS = ["landing_last_error", "landing_form_default", "landing_solver_opts_de
            "landing_np", "landing_nnz_jac", "landing_nnz_hess", "landing_pattern_jac", "landing_pattern_hess",
            "landing_create", "landing_destroy", "landing_device_count", "landing_eval_batch", "landing_eval_batch_host",
            "landing_bounds_batch", "landing_solve_batch", "landing_solve_batch_host", "landing_kernel_name_sweep",
-           "landing_sweep_bytes_per_member", "landing_set_profile_buffer", "landing_debug_workspace",
+           "landing_sweep_bytes_per_member", "landing_set_profile_buffer", "landing_debug_workspace", "landing_debug_solver_tables",
            "landing_pack_args21", "landing_solve_args21", "landing_solve_21",
            "landing_multi_create", "landing_multi_destroy", "landing_multi_count", "landing_shard_range", "landing_multi_solve_args21",
            "landing_solve_21_multi", "landing_multi_release_cached",
@@ -145,6 +145,7 @@ def load(path=None):
         lib.landing_eval_hess_rc_batch_host.argtypes = [vp, C.c_int, _dp, _dp, _dp, _dp, _dp]
     lib.landing_solve_batch.argtypes = [vp, C.c_int, vp, vp, C.POINTER(SolverOpts), vp, vp, vp, vp, vp, vp, vp]
     lib.landing_set_profile_buffer.argtypes = [vp, vp]
+    lib.landing_debug_solver_tables.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_ulonglong)]
     lib.landing_solve_batch_host.argtypes = [vp, C.c_int, _dp, _dp, C.POINTER(SolverOpts), _dp, _dp, _dp, _ip, _ip, _dp]
     lib.landing_pack_args21.argtypes = [C.c_int, C.c_int, C.POINTER(Args21), _dp]
     lib.landing_solve_args21.argtypes = [vp, C.c_int, C.POINTER(Args21), C.POINTER(SolverOpts), _dp, _dp, _ip, _ip, _dp]
@@ -358,6 +359,18 @@ class LandingLib:
             rc = hip.hipMemcpy(out.ctypes.data, ptr.value, out.nbytes, 2)      # hipMemcpyDeviceToHost
             if rc != 0:
                 raise RuntimeError("hipMemcpy of the solver workspace failed (%d)" % rc)
+        return out
+
+    def solver_tables(self):
+        """landing_debug_solver_tables: the tables the solver kernel reads, as the context holds them -- dict of ctab, ccomb, rterm (uint64),
+        ctype (int32) and the ints c_ml, c_mid, rlen.  Builds them when no solve has run in this context."""
+        out = {}
+        for which, (name, dt) in enumerate((("ctab", np.uint64), ("ccomb", np.uint64), ("ctype", np.int32), ("rterm", np.uint64), ("scalars", np.int32))):
+            n = C.c_ulonglong()
+            self._check(self.lib.landing_debug_solver_tables(self.ctx, which, None, C.byref(n)), "landing_debug_solver_tables")
+            out[name] = np.empty(n.value // np.dtype(dt).itemsize, dt)
+            self._check(self.lib.landing_debug_solver_tables(self.ctx, which, out[name].ctypes.data, C.byref(n)), "landing_debug_solver_tables")
+        out["c_ml"], out["c_mid"], out["rlen"] = (int(v) for v in out.pop("scalars"))
         return out
 
     # ---- host-pointer entry points (numpy in / numpy out) --------------------------------------

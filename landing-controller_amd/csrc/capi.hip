@@ -69,9 +69,10 @@ struct SolverWorkspace {
   DevBuf<double> buf;
   DevBuf<int> d_order;
   hipEvent_t done = nullptr;     // recorded behind every solve launch: the next launch (any stream) and any re-allocation wait for it
-  DevBuf<int> d_tab, d_stage_tab, d_rterm, d_ctype;      // d_tab is moved in last: d_tab set <=> all tables are resident
   DevBuf<unsigned long long> d_ctab, d_ccomb;      // packed per-stage-type assembly tables (aterm_pack): [type][c_ml][256]; destinations summed from partial slots
-  int n_tab = 0, rlen = 0, c_ml = 0, c_mid = 0;    // ... c_mid: the most frequent stage type
+  DevBuf<int> d_ctype;                             // ... type of every stage; c_mid: the most frequent one
+  DevBuf<unsigned long long> d_rterm;              // row-product records [rlen][256]
+  int rlen = 0, c_ml = 0, c_mid = 0;               // (d_ctab is moved in last: d_ctab set <=> all tables are resident)
   int ensure(const Layout& L, int B, hipStream_t stream);
   void release();
 };
@@ -101,8 +102,8 @@ struct landing_ctx {
   hipEvent_t scratch_done = nullptr;
   DevBuf<double> d_kd_ws; DevBuf<int> d_kd_active, d_kd_done;      // workspace of landing_kinodyn_solve_batch (kd_capi.inc), count of members still iterating
   int kd_jpat_nnz[2] = {0, 0}; size_t kd_cpat_off = 0;
-  DevBuf<unsigned char> d_kd_jpat;      // [landing::KdJPat | landing::KdCPat at kd_cpat_off]: structural non-zeros of the kinodynamic NLP's Jacobian blocks (kd_ensure_jpat, solver_capi.inc)
-  DevBuf<unsigned char> d_kd_pairs; int kd_npair = 0; int rbd_std_base = 0;      // structurally non-zero pairs of a Hessian block of the kinodynamic NLP ([2][kd_npair]: i | j; solver_capi.inc, kd_ensure_pairs)
+  DevBuf<unsigned char> d_kd_jpat;      // [landing::KdJPat | landing::KdCPat at kd_cpat_off]: structural non-zeros of the kinodynamic NLP's Jacobian blocks (kd_ensure_jpat, kd_capi.inc)
+  DevBuf<unsigned char> d_kd_pairs; int kd_npair = 0; int rbd_std_base = 0;      // structurally non-zero pairs of a Hessian block of the kinodynamic NLP ([2][kd_npair]: i | j; kd_capi.inc, kd_ensure_pairs)
   std::mutex kdc_mu; std::map<int, std::unique_ptr<KdCasadi, KdCasadiFree>> kdc;      // CasADi face of the kinodynamic NLP per N (kd_casadi_capi.inc)
   // drop-state chain (pipeline_capi.inc): the hand-off arrays between its passes, grown to the largest batch seen; pl_done is recorded behind every
   // chain call (the next call, on any stream, and a re-allocation wait for it); pl_mu serialises the chain calls on one context

@@ -4,6 +4,233 @@
 
 extern "C" {
 
+// The two derivative kernels of the kinodynamic NLP exist in two forms (rbd_kernels.hip kd_stage_rows): with the base transform of the tree taken from R and pos (the
+// floating base Px Py Pz Rx Ry Rz of the reference's model -- landing_rbd_set_model checks it) or composed joint by joint
+static void kd_launch_jac(landing_ctx* ctx, const landing::KdNlpArgs& a, long long B, int N, hipStream_t st) {
+  const dim3 grid((unsigned)landing::kd_jac_blocks(B, N)), block(landing::KD_JAC_THREADS);
+  if (ctx->rbd_std_base) hipLaunchKernelGGL(landing::landing_kinodyn_nlp_jac_kernel<1>, grid, block, 0, st, a);
+  else hipLaunchKernelGGL(landing::landing_kinodyn_nlp_jac_kernel<0>, grid, block, 0, st, a);
+}
+static void kd_launch_hess(landing_ctx* ctx, const landing::KdNlpArgs& a, long long B, int N, const unsigned char* pi, const unsigned char* pj, int npair, hipStream_t st) {
+  const dim3 grid((unsigned)landing::kd_hess_blocks(B, N, npair)), block(64);
+  if (ctx->rbd_std_base) hipLaunchKernelGGL(landing::landing_kinodyn_nlp_hess_kernel<1>, grid, block, 0, st, a, pi, pj, npair);
+  else hipLaunchKernelGGL(landing::landing_kinodyn_nlp_hess_kernel<0>, grid, block, 0, st, a, pi, pj, npair);
+}
+
+int landing_kinodyn_nlp_dims(int N, long long* nx, long long* ng) {
+  if (N < 2 || N > 64) return fail(LANDING_E_ARG, "landing_kinodyn_nlp_dims: 2 <= N <= 64");
+  if (nx) *nx = landing::kd_nx(N);
+  if (ng) *ng = landing::kd_ng(N);
+  return 0;
+}
+
+int landing_kinodyn_nlp_eval(landing_ctx* ctx, int B, int N, const double* d_x, const landing_kinodyn_params* prm, double* d_g, double* d_jac, void* stream) {
+  if (ctx && B == 0) return 0;
+  if (!ctx || B < 0 || N < 2 || N > 64 || !d_x || !prm || (!d_g && !d_jac)) return fail(LANDING_E_ARG, "landing_kinodyn_nlp_eval: bad argument");
+  if (!ctx->d_rbd) return fail(LANDING_E_ARG, "landing_kinodyn_nlp_eval: no model (landing_rbd_set_model)");
+  HIP_TRY(hipSetDevice(ctx->device));
+  landing::KdNlpArgs a;
+  a.sx = a.sg = a.sj = a.sh = 0; a.skip = nullptr;
+  a.model = ctx->d_rbd.get(); a.B = B; a.N = N; a.x = d_x; a.g = d_g; a.jac = d_jac; a.lam = nullptr; a.hess = nullptr;
+  for (int k = 0; k < 64; ++k) a.P.dt[k] = k < N ? prm->dt[k] : 0.0;
+  a.P.mass = prm->mass; a.P.mu = prm->mu; a.P.std_base = ctx->rbd_std_base;
+  for (int i = 0; i < 3; ++i) { a.P.Ib[i] = prm->Ib[i]; a.P.Ibi[i] = prm->Ib_inv[i]; }
+  if (d_g) {
+    const long long n = (long long)B * N;
+    hipLaunchKernelGGL(landing::landing_kinodyn_nlp_g_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
+  }
+  if (d_jac) {
+    const long long n = (long long)B * N * landing::KD_NW;
+    kd_launch_jac(ctx, a, B, N, (hipStream_t)stream);
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// The pairs (i <= j) of a Hessian block of the kinodynamic NLP that are evaluated: kd_pair_list's 561 candidates (one leg's variables couple with
+// themselves and the base only, ...) thinned out to those whose entry is not structurally zero.  Which those are is asked of the derivative kernel
+// itself, once per context (round 5): the candidates are evaluated on a few members with random variables and multipliers (three intervals: two
+// middle ones and a last one) and a pair is kept when its entry is non-zero anywhere -- a mixed second derivative through hyper-dual numbers is
+// exactly 0.0 when no row couples the two variables (friction and contact rows are linear in the forces, the FK band is linear in the feet and the
+// body position, omega x I omega has no squares, ...).  286 of the 561 remain; tests/test_n1_rows.py checks EVERY column of the blocks against
+// central differences of the exact Jacobian, which also proves this list.  Caller holds ctx->mu.
+static int kd_ensure_pairs(landing_ctx* ctx, const landing::KdNlpParams& P) {
+  if (ctx->d_kd_pairs) return 0;
+  const int NP = landing::KD_NPAIR;
+  unsigned char host[2 * landing::KD_NPAIR];
+  if (landing::kd_pair_list(host, host + NP) != NP) return fail(LANDING_E_ARG, "kinodynamic NLP: internal pair table");
+  const int B = 6, N = 3, NW = landing::KD_NW;
+  const size_t nx = (size_t)landing::kd_nx(N), ng = (size_t)landing::kd_ng(N), nh = (size_t)B * N * NW * NW;
+  std::vector<double> hx(B * nx), hl(B * ng), hh(nh);
+  unsigned long long sdd = 0x9E3779B97F4A7C15ull;
+  auto rnd = [&]() { sdd = sdd * 6364136223846793005ull + 1442695040888963407ull; return (double)((sdd >> 11) & 0xFFFFFFFFFFFFFull) / 4503599627370496.0; };      // [0, 1)
+  for (auto& v : hx) v = rnd() - 0.5;
+  for (auto& v : hl) v = (0.5 + rnd()) * (rnd() < 0.5 ? -1.0 : 1.0);
+  DevBuf<unsigned char> d_full; DevBuf<double> d_x, d_l, d_h;
+  HIP_TRY(d_full.alloc(sizeof(host))); HIP_TRY(hipMemcpy(d_full.get(), host, sizeof(host), hipMemcpyHostToDevice));
+  HIP_TRY(d_x.alloc(hx.size())); HIP_TRY(hipMemcpy(d_x.get(), hx.data(), hx.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(d_l.alloc(hl.size())); HIP_TRY(hipMemcpy(d_l.get(), hl.data(), hl.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(d_h.alloc(nh)); HIP_TRY(hipMemset(d_h.get(), 0, nh * sizeof(double)));
+  landing::KdNlpArgs a;
+  a.sx = a.sg = a.sj = a.sh = 0; a.skip = nullptr;
+  a.model = ctx->d_rbd.get(); a.B = B; a.N = N; a.x = d_x.get(); a.g = nullptr; a.jac = nullptr; a.lam = d_l.get(); a.hess = d_h.get(); a.P = P;
+  // The structure must not depend on the caller's parameter VALUES (ADVICE r5: with Ib = (0.03, 0.03, 0.03) the omega-omega entries of omega x I omega vanish and a later
+  // call with the real inertia got 36 wrong zeros): the probe runs with fixed generic constants -- distinct inertias, mu > 0, unit mass, a uniform grid -- so that only the model
+  // (landing_rbd_set_model invalidates the table) and the formulation decide which pairs are kept.
+  for (int k = 0; k < 64; ++k) a.P.dt[k] = k < N ? 0.03 : 0.0;
+  a.P.mass = 1.0; a.P.mu = 0.7; a.P.Ib[0] = 0.05; a.P.Ib[1] = 0.2; a.P.Ib[2] = 0.3; a.P.Ibi[0] = 17.0; a.P.Ibi[1] = 4.3; a.P.Ibi[2] = 3.6;
+  const long long n = (long long)B * N * NP;
+  kd_launch_hess(ctx, a, B, N, d_full.get(), d_full.get() + NP, NP, (hipStream_t)nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(hh.data(), d_h.get(), nh * sizeof(double), hipMemcpyDeviceToHost));
+  unsigned char keep[2 * landing::KD_NPAIR]; int nk = 0;
+  for (int q = 0; q < NP; ++q) {
+    const int i = host[q], j = host[NP + q];
+    bool nz = false;
+    for (int b = 0; b < B && !nz; ++b) for (int k = 0; k < N && !nz; ++k) { const double v = hh[(((size_t)b * N + k) * NW + i) * NW + j]; nz = v != 0.0 || v != v; }
+    if (nz) { keep[nk] = (unsigned char)i; keep[NP + nk] = (unsigned char)j; ++nk; }
+  }
+  if (nk < 1) return fail(LANDING_E_ARG, "kinodynamic NLP: empty pair table");
+  // Wavefront-pure order: a lane's pair decides which legs' kinematic rows it evaluates (kd_stage_rows' legmask: all four for a pair inside the base, one for a pair
+  // that involves a leg), and a wavefront runs the rows of every leg any of its lanes needs.  The pairs of the base fill their own wavefront(s), then leg by leg,
+  // each class padded to a multiple of 64 with empty entries (255: the lane leaves at once).
+  unsigned char packed[2 * 1024]; int np_ = 0;
+  {
+    unsigned char oi[1024], oj[1024];
+    for (int cls = -1; cls < 4; ++cls) {
+      for (int q = 0; q < nk; ++q) if (landing::kd_pair_leg(keep[q], keep[NP + q]) == cls) { oi[np_] = keep[q]; oj[np_] = keep[NP + q]; ++np_; }
+      while (np_ % 64) { oi[np_] = 255; oj[np_] = 255; ++np_; }
+    }
+    for (int q = 0; q < np_; ++q) { packed[q] = oi[q]; packed[np_ + q] = oj[q]; }
+  }
+  nk = np_;
+  DevBuf<unsigned char> d_pairs;
+  HIP_TRY(d_pairs.alloc((size_t)2 * nk));
+  HIP_TRY(hipMemcpy(d_pairs.get(), packed, (size_t)2 * nk, hipMemcpyHostToDevice));
+  ctx->d_kd_pairs = std::move(d_pairs); ctx->kd_npair = nk;
+  return 0;
+}
+
+// Structural non-zeros of the inequality rows of the kinodynamic NLP's Jacobian blocks (landing::KdJPat, read by the solver's forward sweep: ds = J_I dx over the non-zeros
+// only).  Asked of the Jacobian kernel itself, once per context, like the pair table above: random variables on six members of a four-interval problem with fixed generic
+// constants; an entry is kept when it is non-zero on any member (a forward-mode derivative is exactly 0.0 where the row does not depend on the variable).  The three
+// intervals that are not the last must agree (they do: the rows depend on the interval through dt only).  tests/test_n1_rows.py checks every column of the blocks against
+// central differences; tests/test_kd_solver_cpu.py pins the counts (529 / 457).  Caller holds ctx->mu.
+static int kd_ensure_jpat(landing_ctx* ctx) {
+  if (ctx->d_kd_jpat) return 0;
+  const int B = 6, N = 4, NW = landing::KD_NW, NR = landing::KD_ROWS;
+  const size_t nx = (size_t)landing::kd_nx(N), nj = (size_t)B * N * NR * NW;
+  std::vector<double> hx(B * nx), hj(nj);
+  unsigned long long sdd = 0x2545F4914F6CDD1Dull;
+  auto rnd = [&]() { sdd = sdd * 6364136223846793005ull + 1442695040888963407ull; return (double)((sdd >> 11) & 0xFFFFFFFFFFFFFull) / 4503599627370496.0; };      // [0, 1)
+  for (auto& v : hx) v = rnd() - 0.4;
+  DevBuf<double> d_x, d_j;
+  HIP_TRY(d_x.alloc(hx.size())); HIP_TRY(hipMemcpy(d_x.get(), hx.data(), hx.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(d_j.alloc(nj)); HIP_TRY(hipMemset(d_j.get(), 0, nj * sizeof(double)));
+  landing::KdNlpArgs a;
+  a.sx = a.sg = a.sj = a.sh = 0; a.skip = nullptr;
+  a.model = ctx->d_rbd.get(); a.B = B; a.N = N; a.x = d_x.get(); a.g = nullptr; a.jac = d_j.get(); a.lam = nullptr; a.hess = nullptr;
+  for (int k = 0; k < 64; ++k) a.P.dt[k] = k < N ? 0.03 : 0.0;
+  a.P.mass = 1.0; a.P.mu = 0.7; a.P.Ib[0] = 0.05; a.P.Ib[1] = 0.2; a.P.Ib[2] = 0.3; a.P.Ibi[0] = 17.0; a.P.Ibi[1] = 4.3; a.P.Ibi[2] = 3.6; a.P.std_base = ctx->rbd_std_base;
+  kd_launch_jac(ctx, a, B, N, (hipStream_t)nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(hj.data(), d_j.get(), nj * sizeof(double), hipMemcpyDeviceToHost));
+  auto nz = [&](int k, int r, int c) { for (int b = 0; b < B; ++b) { const double v = hj[(((size_t)b * N + k) * NR + r) * NW + c]; if (v != 0.0 || v != v) return true; } return false; };
+  for (int r = 12; r < NR; ++r) for (int c = 0; c < NW; ++c)
+    if (nz(0, r, c) != nz(1, r, c) || nz(1, r, c) != nz(2, r, c)) return fail(LANDING_E_ARG, "kinodynamic NLP: the Jacobian blocks of two middle intervals differ in structure");
+  std::vector<landing::KdJPat> T(1);
+  memset(T.data(), 0, sizeof(landing::KdJPat));
+  std::vector<landing::KdCPat> Cp(1);
+  memset(Cp.data(), 0, sizeof(landing::KdCPat));
+  for (int lp = 0; lp < 2; ++lp) {
+    const int k = lp ? N - 1 : 1, nrow = (lp ? landing::KD_ROWS_LAST : NR) - 12;
+    std::vector<std::vector<int>> cols(nrow);
+    for (int j = 0; j < nrow; ++j) for (int c = 0; c < NW; ++c) if (nz(k, 12 + j, c)) cols[j].push_back(c);
+    std::vector<int> order(nrow);
+    for (int j = 0; j < nrow; ++j) order[j] = j;
+    std::stable_sort(order.begin(), order.end(), [&](int p, int q) { return cols[p].size() > cols[q].size(); });
+    int n = 0;
+    for (int j = 0; j < nrow; ++j) {
+      const std::vector<int>& cj = cols[order[j]];
+      if ((int)cj.size() > landing::KD_JP_MAX || n + (int)cj.size() > landing::KD_JP_NNZ - landing::KD_JP_MAX) return fail(LANDING_E_ARG, "kinodynamic NLP: Jacobian block denser than the table of its non-zeros");
+      T[0].perm[lp][j] = (unsigned char)(12 + order[j]); T[0].rp[lp][j] = (unsigned short)n;
+      for (int c : cj) T[0].cl[lp][n++] = (unsigned char)c;
+    }
+    T[0].rp[lp][nrow] = (unsigned short)n;
+    ctx->kd_jpat_nnz[lp] = n;
+    // place table of the compact block (KdNlpArgs::jpos): defect rows dense, inequality entries in table order
+    {
+      std::vector<std::vector<unsigned>> colv(NW);
+      for (int c = 0; c < NW; ++c) for (int r = 0; r < 12; ++r) colv[c].push_back(((unsigned)r << 16) | (unsigned)(r * NW + c));
+      for (int j = 0; j < nrow; ++j) for (int t = T[0].rp[lp][j]; t < T[0].rp[lp][j + 1]; ++t) colv[T[0].cl[lp][t]].push_back(((unsigned)T[0].perm[lp][j] << 16) | (unsigned)(landing::KD_JC_DEF + t));
+      for (int c = 0; c < NW; ++c) {
+        std::sort(colv[c].begin(), colv[c].end());      // (by row: the kernel emits the rows of a column in rising order)
+        if ((int)colv[c].size() >= landing::KD_JCOL) return fail(LANDING_E_ARG, "kinodynamic NLP: a column of the Jacobian block has more entries than its list holds");
+        for (size_t i = 0; i < colv[c].size(); ++i) Cp[0].jcol[lp][c][i] = colv[c][i];
+        for (int i = (int)colv[c].size(); i < landing::KD_JCOL; ++i) Cp[0].jcol[lp][c][i] = 0xffff0000u;
+      }
+    }
+    // the condensation over these entries (landing::KdCPat): stage variable v of block column w (the inequality rows do not see X_k+1, columns 48..59)
+    const int nv = lp ? 48 : landing::KD_NV;
+    auto vof = [&](int w) { return w < 48 ? w : (w >= 60 ? w - 12 : -1); };
+    std::map<std::pair<int, int>, std::vector<unsigned>> dest;
+    std::vector<std::vector<unsigned>> rhs(landing::KD_NV);
+    for (int j = 0; j < nrow; ++j)
+      for (int ta = T[0].rp[lp][j]; ta < T[0].rp[lp][j + 1]; ++ta) {
+        Cp[0].erow[lp][ta] = (unsigned char)j;
+        const int va = vof(T[0].cl[lp][ta]);
+        if (va < 0 || va >= nv) return fail(LANDING_E_ARG, "kinodynamic NLP: an inequality row depends on a variable outside its stage");
+        rhs[va].push_back((unsigned)ta | ((unsigned)j << 10));
+        for (int tb = T[0].rp[lp][j]; tb < T[0].rp[lp][j + 1]; ++tb) {
+          const int vb = vof(T[0].cl[lp][tb]);
+          if (vb >= va) dest[{va, vb}].push_back((unsigned)ta | ((unsigned)tb << 10) | ((unsigned)j << 20));
+        }
+      }
+    std::vector<std::pair<std::pair<int, int>, std::vector<unsigned>>> dl(dest.begin(), dest.end());
+    std::stable_sort(dl.begin(), dl.end(), [](const auto& p, const auto& q) { return p.second.size() > q.second.size(); });      // lanes of a wavefront: destinations of similar length
+    int nd = 0, nt = 0;
+    for (const auto& e : dl) {
+      if (nd >= landing::KD_CP_ND || nt + (int)e.second.size() > landing::KD_CP_NT) return fail(LANDING_E_ARG, "kinodynamic NLP: condensation table too small");
+      Cp[0].drp[lp][nd] = (unsigned short)nt; Cp[0].dab[lp][nd] = (unsigned short)(e.first.first | (e.first.second << 8));
+      for (unsigned w : e.second) Cp[0].dterm[lp][nt++] = w;
+      ++nd;
+    }
+    Cp[0].drp[lp][nd] = (unsigned short)nt; Cp[0].nd[lp] = nd; Cp[0].nt[lp] = nt;
+    int nr = 0;
+    for (int v = 0; v < landing::KD_NV; ++v) { Cp[0].rrp[lp][v] = (unsigned short)nr; for (unsigned w : rhs[v]) Cp[0].rterm[lp][nr++] = w; }
+    Cp[0].rrp[lp][landing::KD_NV] = (unsigned short)nr;
+  }
+  DevBuf<unsigned char> d_t;      // [KdJPat | KdCPat]
+  constexpr size_t JP8 = (sizeof(landing::KdJPat) + 15) / 16 * 16;
+  HIP_TRY(d_t.alloc(JP8 + sizeof(landing::KdCPat)));
+  HIP_TRY(hipMemcpy(d_t.get(), T.data(), sizeof(landing::KdJPat), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_t.get() + JP8, Cp.data(), sizeof(landing::KdCPat), hipMemcpyHostToDevice));
+  ctx->kd_cpat_off = JP8;
+  ctx->d_kd_jpat = std::move(d_t);
+  return 0;
+}
+
+int landing_kinodyn_nlp_hess(landing_ctx* ctx, int B, int N, const double* d_x, const landing_kinodyn_params* prm, const double* d_lam_g, double* d_hess, void* stream) {
+  if (ctx && B == 0) return 0;
+  if (!ctx || B < 0 || N < 2 || N > 64 || !d_x || !prm || !d_lam_g || !d_hess) return fail(LANDING_E_ARG, "landing_kinodyn_nlp_hess: bad argument");
+  if (!ctx->d_rbd) return fail(LANDING_E_ARG, "landing_kinodyn_nlp_hess: no model (landing_rbd_set_model)");
+  HIP_TRY(hipSetDevice(ctx->device));
+  landing::KdNlpArgs a;
+  a.sx = a.sg = a.sj = a.sh = 0; a.skip = nullptr;
+  a.model = ctx->d_rbd.get(); a.B = B; a.N = N; a.x = d_x; a.g = nullptr; a.jac = nullptr; a.lam = d_lam_g; a.hess = d_hess;
+  for (int k = 0; k < 64; ++k) a.P.dt[k] = k < N ? prm->dt[k] : 0.0;
+  a.P.mass = prm->mass; a.P.mu = prm->mu; a.P.std_base = ctx->rbd_std_base;
+  for (int i = 0; i < 3; ++i) { a.P.Ib[i] = prm->Ib[i]; a.P.Ibi[i] = prm->Ib_inv[i]; }
+  std::lock_guard<std::mutex> lock(ctx->mu);      // (the lazily built table below, like every other lazily created resource of the context)
+  { const int rc = kd_ensure_pairs(ctx, a.P); if (rc) return rc; }      // the list of structurally non-zero pairs of a block, built once per context
+  const long long n = (long long)B * N * ctx->kd_npair;
+  if (n > 0x7fffffffLL * 64) return fail(LANDING_E_ARG, "landing_kinodyn_nlp_hess: batch too large for one launch");
+  HIP_TRY(hipMemsetAsync(d_hess, 0, (size_t)B * N * landing::KD_NW * landing::KD_NW * sizeof(double), (hipStream_t)stream));
+  kd_launch_hess(ctx, a, B, N, ctx->d_kd_pairs.get(), ctx->d_kd_pairs.get() + ctx->kd_npair, ctx->kd_npair, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // Warm-start preset of the refinement (round 6): every production caller solves this NLP twice, the second time from the first solution (`prevSoln`:
 // main_scripts/landing_optimization.m:395-435; generate_solver/generate_landingCtrller_KNITRO_warmstart.m builds the `_ws` function for it).  From a solution the
 // slacks of the active rows sit AT their bounds: pushed 1e-6 inside with mu_init = 1e-6 the iteration starts in the last barrier problem instead of walking back
@@ -90,8 +317,8 @@ int landing_kinodyn_solve_batch(landing_ctx* ctx, int B, int N, const landing_ki
   for (int k = 0; k < 64; ++k) A.P.dt[k] = k < N ? prm->dt[k] : 0.0;
   A.P.mass = prm->mass; A.P.mu = prm->mu; A.P.std_base = ctx->rbd_std_base;
   for (int i = 0; i < 3; ++i) { A.P.Ib[i] = prm->Ib[i]; A.P.Ibi[i] = prm->Ib_inv[i]; }
-  { const int rc = kd_ensure_pairs(ctx, A.P); if (rc) return rc; }      // structurally non-zero pairs of a Hessian block (solver_capi.inc)
-  { const int rc = kd_ensure_jpat(ctx); if (rc) return rc; }            // structurally non-zero entries of a Jacobian block (solver_capi.inc)
+  { const int rc = kd_ensure_pairs(ctx, A.P); if (rc) return rc; }      // structurally non-zero pairs of a Hessian block
+  { const int rc = kd_ensure_jpat(ctx); if (rc) return rc; }            // structurally non-zero entries of a Jacobian block
   A.jpat = (const landing::KdJPat*)ctx->d_kd_jpat.get(); A.cpat = (const landing::KdCPat*)(ctx->d_kd_jpat.get() + ctx->kd_cpat_off);
   A.x0 = d_x0; A.lb = d_lbg; A.ub = d_ubg; A.cost = d_cost; A.ws = ctx->d_kd_ws.get(); A.ws_stride = stride;
   int* const cnt = ctx->d_kd_active.get();

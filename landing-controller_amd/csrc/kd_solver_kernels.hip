@@ -88,7 +88,7 @@ __device__ __forceinline__ KdMem kd_carve(int N, double* w) {
 
 // Structural non-zeros of the inequality rows (12 ..) of an interval's Jacobian block, [0] = every interval but the last, [1] = the last one: the rows in the order of
 // falling counts (perm: the lanes of a wavefront then run rows of the same length), their entries as ranges rp[j] .. rp[j + 1] of the column list cl.  Built once per
-// context by asking the Jacobian kernel itself (kd_ensure_jpat, solver_capi.inc: an entry of a forward-mode derivative is exactly 0.0 where the row does not depend on the
+// context by asking the Jacobian kernel itself (kd_ensure_jpat, kd_capi.inc: an entry of a forward-mode derivative is exactly 0.0 where the row does not depend on the
 // variable): 529 of the 129 x 72 entries of a middle interval, at most 9 in a row.
 constexpr int KD_JP_ROWS = 132, KD_JP_NNZ = 640, KD_JP_MAX = 12;
 struct KdJPat { unsigned short rp[2][KD_JP_ROWS]; unsigned char perm[2][KD_JP_ROWS]; unsigned char cl[2][KD_JP_NNZ]; };

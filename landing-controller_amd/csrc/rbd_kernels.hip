@@ -925,7 +925,7 @@ __host__ __device__ inline int kd_pair_list(unsigned char* pi, unsigned char* pj
   return n;
 }
 constexpr int KD_NPAIR = 561;
-// (npair pairs per block: the KD_NPAIR candidates of kd_pair_list, or the subset of them whose entry is not structurally zero -- solver_capi.inc, kd_ensure_pairs)
+// (npair pairs per block: the KD_NPAIR candidates of kd_pair_list, or the subset of them whose entry is not structurally zero -- kd_capi.inc, kd_ensure_pairs)
 // One block (one wave) = 64 pairs of ONE (member, interval): the 72 stage variables are common to the block and live in LDS (read on access, one broadcast
 // ds_read each) instead of 144 VGPRs per lane -- the kernel ran at 256 VGPRs + 256 AGPRs + 1.6 KB of scratch per lane with them.  Grid = B * N * ceil(npair / 64).
 // (The pairs of KD_HESS_G = 2 consecutive intervals are numbered through: 2 x 286 = 572 pairs fill 9 wavefronts but for 4 lanes; interval by interval the fifth
@@ -953,7 +953,7 @@ __global__ void __launch_bounds__(64, 1) landing_kinodyn_nlp_hess_kernel(KdNlpAr
   if (ks >= KD_HESS_G || k >= N) return;
   const double* xv = xs[ks];
   const int i = pair_i[pr], j = pair_j[pr];
-  if (i == 255) return;      // padding of the wavefront-pure order (solver_capi.inc kd_ensure_pairs)
+  if (i == 255) return;      // padding of the wavefront-pure order (kd_capi.inc kd_ensure_pairs)
   double* Hk = a.hess + a.oh(b) + ((size_t)k * KD_NW) * KD_NW;
   const bool last = k == N - 1;
   if (last && j >= 60) return;

@@ -5,23 +5,29 @@
 // (casadi_s5 / casadi_s4 order).  For every stage k the host precomputes, from the patterns, how the
 // stage's nonzeros combine into the condensed stage block
 //     G_k = H_k + J_d^T Sigma J_d   (48x48 over w = [X_k(12) c_k(12) f_k(12) c_{k+1}(12)])
-// the barrier gradient gamma_k = J_d^T rho, the dynamics block A^ = -dg_dyn/d(X_k,c_k,f_k) (12x36, rows in
-// state order) and the row-major products J_d w.  Identical tables are de-duplicated (first / middle /
-// penultimate / last stage), so the table data stays L1/L2 resident.
+// the barrier gradient gamma_k = J_d^T rho and the dynamics block A^ = -dg_dyn/d(X_k,c_k,f_k) (12x36, rows in
+// state order), and, for the whole horizon, the records of the row products J_d dx.  Stages with identical tables
+// share one (first / middle / penultimate / last stage), so the table data stays L1/L2 resident.
 
 namespace {
 
-struct StageTab {
-  std::vector<int> tg_ab, tg_start, tg_term, gm_start, gm_term, a_term, r_start, r_term;
-  int nu;
-  // not part of the de-duplicated table: member-global flat term lists (see build_tables)
-  std::vector<std::array<int, 4>> cterm;   // {row (global; -1: Hessian entry; -2: negated Jacobian entry), i1, i2 (-1: rho term), dst}
-  std::vector<std::array<int, 4>> rterm;   // {jac index, x index, dst row (-1: more terms follow), 0}
-  std::vector<unsigned long long> cloc;    // condensation terms in stage-local packed form (landing::cterm_pack); identical for stages of one type
-  bool operator==(const StageTab& o) const {
-    return nu == o.nu && tg_ab == o.tg_ab && tg_start == o.tg_start && tg_term == o.tg_term && gm_start == o.gm_start &&
-           gm_term == o.gm_term && a_term == o.a_term && r_start == o.r_start && r_term == o.r_term && cloc == o.cloc;
-  }
+constexpr int NTH = landing::SOLVER_THREADS;
+
+// What the solver kernel reads (SolveArgs): everything in lists interleaved over the 256 threads, entry j of thread t at [j * 256 + t]
+struct SolverTables {
+  std::vector<unsigned long long> ctab, ccomb;      // per stage type: terms [c_ml][256] (landing::aterm_pack), destinations summed from partial slots [256] (landing::acomb_pack)
+  std::vector<int> ctype;                           // type of every stage, numbered as first seen
+  int c_ml = 0, c_mid = 0;                          // terms per thread; the most frequent type
+  std::vector<unsigned long long> rterm;            // row products [rlen][256]: jac index | x index << 16 | row << 32 | closes the row << 48 | valid << 49
+  int rlen = 0;
+};
+
+// One entry of G (upper triangle, elimination order), of gamma or of A^: its byte offset inside the kernel's LDS block (`ah`: inside Lds::Ah,
+// whose two copies alternate between stages) and the terms summed into it, each a product of three entries of the LDS array cx
+struct AsmDest {
+  int d; bool ah;
+  std::vector<std::array<int, 3>> terms;      // positions in cx
+  bool operator==(const AsmDest& o) const { return d == o.d && ah == o.ah && terms == o.terms; }
 };
 
 // w-index of global variable c relative to stage k, or -1 (X_{k+1} / unrelated)
@@ -32,314 +38,198 @@ int w_index(const Layout& L, int k, long long c) {
   if (k < N - 1 && c >= L.x_U(k + 1) && c < L.x_U(k + 1) + 12) return 36 + (int)(c - L.x_U(k + 1));
   return -1;
 }
-// position of Jacobian nonzero idx (column c) in the stage-k staging buffer, or -1
+// position in cx of entry `off` of segment `seg` of the stage's nonzeros (asm_copy: J X_k | J U_k | J U_{k+1} | H X_k | H U_k | H U_{k+1} | running-cost
+// constants, one load per thread and segment), or -1 when the segment does not hold it
+int seg_pos(int seg, long long off) { return off >= 0 && off < landing::ASM_SEG_LEN[seg] ? landing::ASM_SEG_POS[seg] + (int)off : -1; }
+// ... of Jacobian nonzero idx (column c) of stage k, or -1
 int jpos(const Layout& L, int k, long long c, long long idx) {
-  if (c >= L.x_X(k) && c < L.x_X(k) + 12) return landing::NZ_JX + (int)(idx - L.jx(k));
-  if (c >= L.x_U(k) && c < L.x_U(k) + 24) return landing::NZ_JU + (int)(idx - L.ju(k));
-  if (k < L.N - 1 && c >= L.x_U(k + 1) && c < L.x_U(k + 1) + 12) return landing::NZ_JUN + (int)(idx - L.ju(k + 1));
+  if (c >= L.x_X(k) && c < L.x_X(k) + 12) return seg_pos(0, idx - L.jx(k));
+  if (c >= L.x_U(k) && c < L.x_U(k) + 24) return seg_pos(1, idx - L.ju(k));
+  if (k < L.N - 1 && c >= L.x_U(k + 1) && c < L.x_U(k + 1) + 12) return seg_pos(2, idx - L.ju(k + 1));
   return -1;
 }
 
-// stage-local encoding of an index into the member's [J | H | Hc] array: segment (landing::SEG_*) and offset inside it
-bool encode_jh(const Layout& L, int k, int idx, int& seg, int& off) {
-  const int nj = L.nnz_jac, nh = L.nnz_hess, N = L.N;
-  struct R { int base, len; };
-  const R r[7] = {{L.jx(k), 157}, {L.ju(k), L.ju_len(k)}, {k < N - 1 ? L.ju(k + 1) : -1, k < N - 1 ? L.ju_len(k + 1) : 0},
-                  {nj + L.hx(k), 29}, {nj + L.hu(k), k == 0 ? 148 : 160}, {k < N - 1 ? nj + L.hu(k + 1) : -1, k < N - 1 ? 160 : 0},
-                  {nj + nh + k * landing::RUNC, landing::RUNC}};
-  for (int q = 0; q < 7; ++q) if (r[q].base >= 0 && idx >= r[q].base && idx < r[q].base + r[q].len) { seg = q; off = idx - r[q].base; return off < 256; }
-  return false;
+struct Patterns {
+  std::vector<std::vector<std::pair<long long, long long>>> rows;      // row-major view of J: (col, idx)
+  std::vector<long long> hci, hr;                                      // CCS of the Hessian
+};
+
+// Destinations of stage k in table order -- the entries of G by (a, b), a <= b indices into w; gamma 0..47, a structural zero included; A^ in the
+// order of the dynamics rows -- with their terms in the order they are summed in.  Appends the stage's row-product records to `rrec`.
+int stage_dests(const Layout& L, int k, const Patterns& pat, std::vector<AsmDest>& dests, std::vector<unsigned long long>& rrec) {
+  using namespace landing;
+  const int oG = (int)offsetof(Lds, G), oAh = (int)offsetof(Lds, Ah);
+  // G in elimination order, the same for every stage type: (sigma, f, c+) -> rows / columns (f, c+, sigma); gamma is its spare column
+  auto gpos = [](int a) { return a < 24 ? a + 24 : a - 24; };
+  const bool last = (k == L.N - 1);
+  const int nr = L.rows(k), g0 = L.g_stage(k);
+  if (nr > 104) return -9;      // sigma and rho of a stage's rows: 104 entries each in cx
+  std::map<std::pair<int, int>, std::vector<std::array<int, 3>>> tg;
+  std::vector<std::vector<std::array<int, 3>>> gm(48);
+  std::vector<AsmDest> ah;
+  // --- Jacobian rows ---
+  for (int q = 0; q < nr; ++q) {
+    std::vector<std::array<int, 2>> ent;   // (w index, position)
+    const size_t r0 = rrec.size();
+    for (auto& ci : pat.rows[g0 + q]) {
+      const int a = w_index(L, k, ci.first);
+      if (a < 0) continue;                 // X_{k+1} identity
+      const int pos = jpos(L, k, ci.first, ci.second);
+      if (pos < 0) return -2;
+      ent.push_back({a, pos});
+      if (q < 12) continue;
+      if (ci.second > 0xffff || ci.first > 0xffff || g0 + q > 0xffff) return -18;      // the 16-bit fields of a record
+      rrec.push_back((unsigned long long)ci.second | ((unsigned long long)ci.first << 16) | (1ull << 49));
+    }
+    if (rrec.size() > r0) rrec.back() |= ((unsigned long long)(g0 + q) << 32) | (1ull << 48);
+    if (q < 12) {                          // dynamics rows -> A^ (state order)
+      const int sr = q < 6 ? q : (q < 9 ? q + 3 : q - 3);
+      for (auto& e : ent) { if (e[0] >= 36) return -3; ah.push_back({oAh + 8 * (sr * YS + e[0]), true, {{e[1], CX_ONE, CX_MONE}}}); }
+    } else {                               // inequality rows: sigma_q J_qa J_qb into G, rho_q J_qa into gamma
+      for (size_t i = 0; i < ent.size(); ++i) {
+        gm[ent[i][0]].push_back({ent[i][1], CX_ONE, CX_SR + 104 + q});
+        for (size_t j = i; j < ent.size(); ++j) {
+          int a = ent[i][0], b = ent[j][0], pa = ent[i][1], pb = ent[j][1];
+          if (a > b) { std::swap(a, b); std::swap(pa, pb); }
+          tg[{a, b}].push_back({pa, pb, CX_SR + q});
+        }
+      }
+    }
+  }
+  // --- Hessian nonzeros owned by stage k ---
+  auto add_h = [&](long long r, long long c, int pos) {
+    int a = w_index(L, k, r), b = w_index(L, k, c);
+    if (a < 0 || b < 0 || pos < 0) return false;
+    if (a > b) std::swap(a, b);
+    tg[{a, b}].push_back({pos, CX_ONE, CX_ONE});
+    return true;
+  };
+  const auto& hci = pat.hci; const auto& hr = pat.hr;
+  for (long long c = L.x_X(k); c < L.x_X(k) + 12; ++c)
+    for (long long i = hci[c]; i < hci[c + 1]; ++i) if (!add_h(hr[i], c, seg_pos(3, i - L.hx(k)))) return -4;
+  for (long long c = L.x_U(k); c < L.x_U(k) + 24; ++c)
+    for (long long i = hci[c]; i < hci[c + 1]; ++i) {
+      if (k > 0 && hr[i] >= L.x_U(k - 1) && hr[i] < L.x_U(k - 1) + 24) continue;   // (f_z of stage k-1, c_k): owned by stage k-1
+      if (!add_h(hr[i], c, seg_pos(4, i - L.hu(k)))) return -5;
+    }
+  if (!last)
+    for (long long c = L.x_U(k + 1); c < L.x_U(k + 1) + 12; ++c)
+      for (long long i = hci[c]; i < hci[c + 1]; ++i)
+        if (hr[i] >= L.x_U(k) && hr[i] < L.x_U(k) + 24) { if (!add_h(hr[i], c, seg_pos(5, i - L.hu(k + 1)))) return -6; }
+  // --- constant Hessian entries of the running cost (segment 6 of cx, layout: RUNC) ---
+  if (L.run_cost) {
+    auto add_c = [&](int a, int b, int j) { tg[{a, b}].push_back({seg_pos(6, j), CX_ONE, CX_ONE}); };
+    for (int i = 0; i < 12; ++i) add_c(i, i, i);                                  // (X_i, X_i)
+    for (int l = 0; l < 4; ++l) for (int a = 0; a < 3; ++a) add_c(a, 12 + 3 * l + a, 12 + 3 * l + a);   // (pos_a, c_leg,a)
+    for (int j = 0; j < 12; ++j) add_c(12 + j, 12 + j, 24 + j);                  // (c, c)
+    for (int j = 0; j < 12; ++j) add_c(24 + j, 24 + j, 36 + j);                  // (f, f)
+  }
+  for (auto& kv : tg) {      // upper triangle (block_eliminate's tile fetch)
+    const int ga = gpos(kv.first.first), gb = gpos(kv.first.second);
+    dests.push_back({oG + 8 * (std::min(ga, gb) * GS + std::max(ga, gb)), false, kv.second});
+  }
+  for (int a = 0; a < 48; ++a) {
+    if (gm[a].empty()) gm[a].push_back({0, CX_ONE, CX_ZERO});      // structural zero
+    dests.push_back({oG + 8 * (gpos(a) * GS + G_GAMMA), false, gm[a]});
+  }
+  dests.insert(dests.end(), ah.begin(), ah.end());
+  return 0;
 }
 
-int build_tables(const Layout& L, std::vector<int>& data, std::vector<int>& stage_tab,
-                 std::vector<int>& rterms, std::vector<int>& rstart,
-                 std::vector<unsigned long long>& ctab, std::vector<unsigned long long>& ccomb, std::vector<int>& ctype, int& c_ml, int& c_mid) {
+// The tables of a horizon.  Assembly (ctab, read by asm_terms of the backward sweep): the terms of a stage type, destination behind destination, are cut into
+// PIECES at every ch-th term (ch = ceil(n / 256) terms, the same for every type: where the 256 equal chunks of rounds 1-4 cut them).  A destination of one
+// piece is summed and stored by one thread; the pieces of a longer one go to consecutive partial-sum slots and thread j adds up the slots of the j-th
+// such destination (ccomb, asm_combine) -- every sum keeps the association it had, results stay bit-identical to the earlier kernels.  Pieces are
+// spread over the 256 threads by longest-processing-time assignment, the lists padded with terms that add 0 to a closed sum to a multiple of ATAB_TB.
+// Row products (rterm, read by row_products): the records of all inequality rows in row order, in 256 chunks of equal length moved to the next row border.
+int build_tables(const Layout& L, SolverTables& T) {
+  using namespace landing;
   const int N = L.N;
-  std::vector<long long> jci(L.nx + 1), jr(L.nnz_jac), hci(L.nx + 1), hr(L.nnz_hess);
-  if (landing_pattern_jac(N, jci.data(), jr.data()) || landing_pattern_hess(N, hci.data(), hr.data())) return -1;
-  // row-major view of J
-  std::vector<std::vector<std::pair<long long, long long>>> rows(L.ng);  // (col, idx)
-  for (long long c = 0; c < L.nx; ++c) for (long long i = jci[c]; i < jci[c + 1]; ++i) rows[jr[i]].push_back({c, i});
-  std::vector<StageTab> uniq;
-  stage_tab.assign(N, 0);
-  std::vector<int> which(N);
-  std::vector<std::set<int>> pat_g(N), pat_a(N);   // structural nonzeros of the condensed G / of A^ per stage
+  Patterns pat;
+  std::vector<long long> jci(L.nx + 1), jr(L.nnz_jac);
+  pat.hci.resize(L.nx + 1); pat.hr.resize(L.nnz_hess); pat.rows.resize(L.ng);
+  if (landing_pattern_jac(N, jci.data(), jr.data()) || landing_pattern_hess(N, pat.hci.data(), pat.hr.data())) return -1;
+  for (long long c = 0; c < L.nx; ++c) for (long long i = jci[c]; i < jci[c + 1]; ++i) pat.rows[jr[i]].push_back({c, i});
+  std::vector<std::vector<AsmDest>> types;
+  std::vector<std::set<int>> where(N);      // structural nonzeros of G and A^ per stage, by their place
+  std::vector<unsigned long long> rrec;
+  T.ctype.assign(N, 0);
   for (int k = 0; k < N; ++k) {
-    StageTab T;
-    const bool last = (k == N - 1);
-    T.nu = last ? 12 : 24;
-    const int nr = L.rows(k), g0 = L.g_stage(k);
-    std::map<std::pair<int, int>, std::vector<std::array<int, 3>>> tg;   // (a,b) -> terms
-    std::map<int, int> pos2idx;            // staging position -> index into the member's [J | H] nonzeros
-    std::vector<std::vector<std::array<int, 2>>> gm(48);
-    T.r_start.assign(105, 0);
-    // --- Jacobian rows ---
-    for (int q = 0; q < nr; ++q) {
-      std::vector<std::array<int, 2>> ent;   // (w index, pos)
-      std::vector<std::array<int, 2>> entg;  // (global jac index, global x index), same order
-      for (auto& ci : rows[g0 + q]) {
-        const int a = w_index(L, k, ci.first), pos = jpos(L, k, ci.first, ci.second);
-        if (a < 0) continue;                 // X_{k+1} identity
-        if (pos < 0) return -2;
-        ent.push_back({a, pos});
-        entg.push_back({(int)ci.second, (int)ci.first});
-        pos2idx[pos] = (int)ci.second;
-      }
-      if (q >= 12) for (size_t i = 0; i < entg.size(); ++i)
-        T.rterm.push_back({entg[i][0], entg[i][1], i + 1 == entg.size() ? g0 + q : -1, 0});
-      if (q < 12) {                          // dynamics rows -> A^ (state order)
-        const int sr = q < 6 ? q : (q < 9 ? q + 3 : q - 3);
-        for (auto& e : ent) { if (e[0] >= 36) return -3; T.a_term.push_back(e[1]); T.a_term.push_back(sr); T.a_term.push_back(e[0]); }
-      } else {                               // inequality rows
-        for (size_t i = 0; i < ent.size(); ++i) {
-          gm[ent[i][0]].push_back({q, ent[i][1]});
-          T.r_term.push_back(ent[i][1]); T.r_term.push_back(ent[i][0]);
-          for (size_t j = i; j < ent.size(); ++j) {
-            int a = ent[i][0], b = ent[j][0], pa = ent[i][1], pb = ent[j][1];
-            if (a > b) { std::swap(a, b); std::swap(pa, pb); }
-            tg[{a, b}].push_back({q, pa, pb});
-          }
-        }
-      }
-      T.r_start[q + 1] = (int)T.r_term.size() / 2;
-    }
-    for (int q = nr; q < 104; ++q) T.r_start[q + 1] = T.r_start[nr];
-    // --- Hessian nonzeros owned by stage k ---
-    auto add_h = [&](long long r, long long c, long long idx, int pos) {
-      int a = w_index(L, k, r), b = w_index(L, k, c);
-      if (a < 0 || b < 0) return false;
-      if (a > b) std::swap(a, b);
-      tg[{a, b}].push_back({-1, pos, 0});
-      pos2idx[pos] = L.nnz_jac + (int)idx;
-      return true;
-    };
-    for (long long c = L.x_X(k); c < L.x_X(k) + 12; ++c)
-      for (long long i = hci[c]; i < hci[c + 1]; ++i) if (!add_h(hr[i], c, i, landing::NZ_HX + (int)(i - L.hx(k)))) return -4;
-    for (long long c = L.x_U(k); c < L.x_U(k) + 24; ++c)
-      for (long long i = hci[c]; i < hci[c + 1]; ++i) {
-        if (k > 0 && hr[i] >= L.x_U(k - 1) && hr[i] < L.x_U(k - 1) + 24) continue;   // (f_z of stage k-1, c_k): owned by stage k-1
-        if (!add_h(hr[i], c, i, landing::NZ_HU + (int)(i - L.hu(k)))) return -5;
-      }
-    if (!last)
-      for (long long c = L.x_U(k + 1); c < L.x_U(k + 1) + 12; ++c)
-        for (long long i = hci[c]; i < hci[c + 1]; ++i)
-          if (hr[i] >= L.x_U(k) && hr[i] < L.x_U(k) + 24) { if (!add_h(hr[i], c, i, landing::NZ_HUN + (int)(i - L.hu(k + 1)))) return -6; }
-    // --- constant Hessian entries of the running cost (stored behind the Hessian nonzeros, RUNC per stage) ---
-    if (L.run_cost) {
-      auto add_c = [&](int a, int b, int j) {
-        const int pos = 100000 + j;
-        tg[{a, b}].push_back({-1, pos, 0});
-        pos2idx[pos] = L.nnz_jac + L.nnz_hess + k * landing::RUNC + j;
-      };
-      for (int i = 0; i < 12; ++i) add_c(i, i, i);                                  // (X_i, X_i)
-      for (int l = 0; l < 4; ++l) for (int a = 0; a < 3; ++a) add_c(a, 12 + 3 * l + a, 12 + 3 * l + a);   // (pos_a, c_leg,a)
-      for (int j = 0; j < 12; ++j) add_c(12 + j, 12 + j, 24 + j);                  // (c, c)
-      for (int j = 0; j < 12; ++j) add_c(24 + j, 24 + j, 36 + j);                  // (f, f)
-    }
-    // --- flatten ---
-    T.tg_start.push_back(0);
-    for (auto& kv : tg) {
-      T.tg_ab.push_back(kv.first.first | (kv.first.second << 8));
-      for (auto& t : kv.second) { T.tg_term.push_back(t[0]); T.tg_term.push_back(t[1]); T.tg_term.push_back(t[2]); }
-      T.tg_start.push_back((int)T.tg_term.size() / 3);
-    }
-    T.gm_start.push_back(0);
-    for (int a = 0; a < 48; ++a) {
-      for (auto& t : gm[a]) { T.gm_term.push_back(t[0]); T.gm_term.push_back(t[1]); }
-      T.gm_start.push_back((int)T.gm_term.size() / 2);
-    }
-    // member-global condensation terms of this stage: targets, gamma, A^ (destinations k*COND_STRIDE + slot)
-    {
-      const int base = k * landing::COND_STRIDE;
-      if ((int)T.tg_ab.size() > landing::COND_GAM || (int)T.a_term.size() / 3 > landing::COND_STRIDE - landing::COND_AH) return -7;
-      int slot = 0;
-      for (auto& kv : tg) {
-        for (size_t i = 0; i < kv.second.size(); ++i) {
-          const auto& t = kv.second[i];
-          const int dst = (i + 1 == kv.second.size()) ? base + slot : -1;
-          if (t[0] < 0) T.cterm.push_back({-1, pos2idx.at(t[1]), -1, dst});
-          else T.cterm.push_back({g0 + t[0], pos2idx.at(t[1]), pos2idx.at(t[2]), dst});
-        }
-        ++slot;
-      }
-      for (int a = 0; a < 48; ++a) {
-        if (gm[a].empty()) { T.cterm.push_back({-3, 0, -1, base + landing::COND_GAM + a}); continue; }   // structural zero
-        for (size_t i = 0; i < gm[a].size(); ++i)
-          T.cterm.push_back({g0 + gm[a][i][0], pos2idx.at(gm[a][i][1]), -1, (i + 1 == gm[a].size()) ? base + landing::COND_GAM + a : -1});
-      }
-      for (size_t i = 0; i < T.a_term.size() / 3; ++i) T.cterm.push_back({-2, pos2idx.at(T.a_term[3 * i]), -1, base + landing::COND_AH + (int)i});
-    }
-    for (auto& t : T.cterm) {   // stage-local packed form of the same terms
-      int sa = 0, oa = 0, sb = 0, ob = 0;
-      const bool has_b = t[2] >= 0;
-      if (t[0] != -3 && !encode_jh(L, k, t[1], sa, oa)) return -9;
-      if (has_b && !encode_jh(L, k, t[2], sb, ob)) return -9;
-      const int rtype = t[0] >= 0 ? 0 : (t[0] == -1 ? 1 : (t[0] == -2 ? 2 : 3));
-      const int rowq = t[0] >= 0 ? t[0] - g0 : 0;
-      if (rowq < 0 || rowq >= 128) return -9;
-      const int dstl = t[3] >= 0 ? t[3] - k * landing::COND_STRIDE : 0;
-      if (dstl < 0 || dstl >= 1024) return -9;
-      T.cloc.push_back(landing::cterm_pack(sa, oa, sb, ob, has_b, rowq, rtype, dstl, t[3] >= 0));
-    }
-    for (int ab : T.tg_ab) pat_g[k].insert(ab);
-    for (size_t i = 0; i < T.a_term.size() / 3; ++i) pat_a[k].insert(T.a_term[3 * i + 1] * 64 + T.a_term[3 * i + 2]);
-    for (auto& t : T.rterm) { rterms.push_back(t[0]); rterms.push_back(t[1]); rterms.push_back(t[2]); rterms.push_back(t[3]); }
-    T.cterm.clear(); T.rterm.clear();
-    int id = -1;
-    for (size_t u = 0; u < uniq.size(); ++u) if (uniq[u] == T) { id = (int)u; break; }
-    if (id < 0) { id = (int)uniq.size(); uniq.push_back(T); }
-    which[k] = id;
+    std::vector<AsmDest> dests;
+    if (const int rc = stage_dests(L, k, pat, dests, rrec)) return rc;
+    for (const AsmDest& D : dests) where[k].insert(D.d);
+    const size_t id = std::find(types.begin(), types.end(), dests) - types.begin();
+    if (id == types.size()) types.push_back(dests);
+    T.ctype[k] = (int)id;
   }
   // the backward sweep visits k = N-1 .. 0 and only overwrites structural nonzeros in LDS: that needs the pattern of
   // stage k to contain the one of stage k+1 (true for this NLP: the last stage lacks the c+ block, all others agree)
-  int zero_each = 0;
   for (int k = N - 2; k >= 0; --k)
-    if (!std::includes(pat_g[k].begin(), pat_g[k].end(), pat_g[k + 1].begin(), pat_g[k + 1].end()) ||
-        !std::includes(pat_a[k].begin(), pat_a[k].end(), pat_a[k + 1].begin(), pat_a[k + 1].end())) zero_each = 1;
-  if (zero_each) return -8;     // cannot happen for this NLP family; the kernel relies on the nesting
-  // --- serialise: header of 16 ints per table, then the arrays ---
-  data.clear();
-  std::vector<int> off(uniq.size());
-  for (size_t u = 0; u < uniq.size(); ++u) {
-    const StageTab& T = uniq[u];
-    off[u] = (int)data.size();
-    const int h = (int)data.size();
-    data.resize(data.size() + 16, 0);
-    auto put = [&](const std::vector<int>& v) { const int o = (int)data.size(); data.insert(data.end(), v.begin(), v.end()); return o; };
-    data[h + 0] = (int)T.tg_ab.size();
-    data[h + 1] = put(T.tg_ab); data[h + 2] = put(T.tg_start); data[h + 3] = put(T.tg_term);
-    data[h + 4] = put(T.gm_start); data[h + 5] = put(T.gm_term);
-    data[h + 6] = (int)T.a_term.size() / 3; data[h + 7] = put(T.a_term);
-    data[h + 8] = put(T.r_start); data[h + 9] = put(T.r_term);
-    data[h + 10] = T.nu;
-    data[h + 11] = zero_each;
+    if (!std::includes(where[k].begin(), where[k].end(), where[k + 1].begin(), where[k + 1].end())) return -8;
+  std::vector<int> cnt(types.size(), 0);
+  for (int id : T.ctype) cnt[id]++;
+  T.c_mid = (int)(std::max_element(cnt.begin(), cnt.end()) - cnt.begin());
+
+  const int oCx = (int)offsetof(Lds, jhl), oCarry = (int)offsetof(Lds, carry), oDump = (int)offsetof(Lds, dump);
+  auto cx = [&](int pos) { return oCx + 8 * pos; };
+  int ch = 0;
+  for (const auto& dests : types) {
+    size_t n = 0;
+    for (const AsmDest& D : dests) n += D.terms.size();
+    ch = std::max(ch, ((int)n + NTH - 1) / NTH);
   }
-  for (int k = 0; k < N; ++k) stage_tab[k] = off[which[k]];
-  // Assembly tables, one per stage type (landing::aterm_pack, read by asm_terms of the backward sweep), every place given as a byte
-  // offset inside the kernel's LDS block.  The terms of a destination are cut into PIECES where the 256 equal chunks of rounds 1-4
-  // cut them (chunk = ceil(n / 256) terms, the same for every type): a destination of one piece is summed and stored by one thread;
-  // the pieces of a longer one go to consecutive partial-sum slots and thread j adds up the slots of the j-th such destination
-  // (landing::acomb_pack, asm_combine) -- every sum keeps the association it had, results stay bit-identical to the earlier kernels.
-  // Pieces are spread over the 256 threads by longest-processing-time assignment; list [entry j][thread], padded with terms that add
-  // 0 to a closed sum; the length is a multiple of ATAB_TB.
-  {
-    using landing::Lds;
-    const int NTH = landing::SOLVER_THREADS;
-    const int oG = (int)offsetof(Lds, G), oAh = (int)offsetof(Lds, Ah), oCx = (int)offsetof(Lds, jhl), oCarry = (int)offsetof(Lds, carry), oDump = (int)offsetof(Lds, dump);
-    auto cx = [&](int pos) { return oCx + 8 * pos; };
-    // G in elimination order, the same for every stage type: (sigma, f, c+) -> rows / columns (f, c+, sigma); gamma is its spare column
-    auto gpos = [](int a) { return a < 24 ? a + 24 : a - 24; };
-    int ch = 0;
-    for (size_t u = 0; u < uniq.size(); ++u) ch = std::max(ch, ((int)uniq[u].cloc.size() + NTH - 1) / NTH);
-    struct Piece { std::vector<std::array<int, 3>> ops; int d; bool ah; };
-    std::vector<std::vector<std::vector<unsigned long long>>> lists(uniq.size(), std::vector<std::vector<unsigned long long>>(NTH));
-    ccomb.assign(uniq.size() * (size_t)NTH, 0ull);
-    c_ml = 0;
-    for (size_t u = 0; u < uniq.size(); ++u) {
-      const StageTab& T = uniq[u];
-      const auto& v = T.cloc; const int n = (int)v.size();
-      if (n == 0 || !landing::cterm_closes(v[n - 1])) return -11;
-      std::vector<Piece> pieces, cur;      // all pieces; pieces of the open destination
-      int nslot = 0, ncomb = 0;
-      Piece pc_; pc_.d = 0; pc_.ah = false;
-      for (int i = 0; i < n; ++i) {
-        const unsigned lo = (unsigned)v[i], hi = (unsigned)(v[i] >> 32);
-        const int pa = (int)(lo & 2047u), pb0 = (int)((lo >> 11) & 2047u), rowq = (int)((lo >> 23) & 127u), rtype = (int)(lo >> 30), dst = (int)(hi & 1023u);
-        const bool has_b = (lo >> 22) & 1u, closes = landing::cterm_closes(v[i]);
-        const int pb = has_b ? pb0 : landing::CX_ONE;
-        const int pc = rtype == 0 ? landing::CX_SR + rowq + (has_b ? 0 : 104) : (rtype == 1 ? landing::CX_ONE : (rtype == 2 ? landing::CX_MONE : landing::CX_ZERO));
-        if (i % ch == 0 && !pc_.ops.empty()) { cur.push_back(pc_); pc_.ops.clear(); }      // chunk border inside a destination
-        pc_.ops.push_back({cx(pa), cx(pb), cx(pc)});
-        if (!closes) continue;
-        int d; bool ah = false;
-        if (dst < landing::COND_GAM) {
-          if (dst >= (int)T.tg_ab.size()) return -12;
-          const int a0 = T.tg_ab[dst] & 255, b0 = T.tg_ab[dst] >> 8;
-          if (a0 >= 48 || b0 >= 48) return -12;
-          d = oG + 8 * (std::min(gpos(a0), gpos(b0)) * landing::GS + std::max(gpos(a0), gpos(b0)));      // upper triangle (block_eliminate's tile fetch)
-        } else if (dst < landing::COND_AH) d = oG + 8 * (gpos(dst - landing::COND_GAM) * landing::GS + landing::G_GAMMA);
-        else {
-          const int q = dst - landing::COND_AH;
-          if (3 * q + 2 >= (int)T.a_term.size()) return -12;
-          d = oAh + 8 * (T.a_term[3 * q + 1] * landing::YS + T.a_term[3 * q + 2]); ah = true;
-        }
-        cur.push_back(pc_); pc_.ops.clear();
-        if (cur.size() == 1) { cur[0].d = d; cur[0].ah = ah; pieces.push_back(cur[0]); }
-        else {
-          if (cur.size() > 7 || nslot + (int)cur.size() > landing::ASM_NSLOT || ncomb >= NTH) return -13;
-          ccomb[u * NTH + ncomb++] = landing::acomb_pack((int)cur.size(), oCarry + 8 * nslot, d, ah);
-          for (auto& q : cur) { q.d = oCarry + 8 * nslot; q.ah = false; ++nslot; pieces.push_back(q); }
-        }
-        cur.clear();
+  struct Piece { std::vector<std::array<int, 3>> ops; int d = 0; bool ah = false; };
+  std::vector<std::vector<std::vector<unsigned long long>>> lists(types.size(), std::vector<std::vector<unsigned long long>>(NTH));
+  T.ccomb.assign(types.size() * (size_t)NTH, 0ull);
+  for (size_t u = 0; u < types.size(); ++u) {
+    std::vector<Piece> pieces;
+    int nslot = 0, ncomb = 0, i = 0;
+    for (const AsmDest& D : types[u]) {
+      std::vector<Piece> cur(1);      // pieces of this destination
+      for (const auto& t : D.terms) {
+        if (i++ % ch == 0 && !cur.back().ops.empty()) cur.emplace_back();
+        cur.back().ops.push_back(t);
       }
-      std::vector<int> order(pieces.size());
-      for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
-      std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return pieces[x].ops.size() > pieces[y].ops.size(); });
-      std::vector<int> load(NTH, 0);
-      for (int di : order) {
-        const int l = (int)(std::min_element(load.begin(), load.end()) - load.begin());
-        const Piece& q = pieces[di];
-        for (size_t i = 0; i < q.ops.size(); ++i) {
-          const bool lastt = i + 1 == q.ops.size();
-          lists[u][l].push_back(landing::aterm_pack(q.ops[i][0], q.ops[i][1], q.ops[i][2], lastt ? q.d : oDump + 8 * (l & 63), !lastt, lastt && q.ah));
-        }
-        load[l] += (int)q.ops.size();
+      if (cur.size() == 1) { cur[0].d = D.d; cur[0].ah = D.ah; pieces.push_back(cur[0]); continue; }
+      if (cur.size() > 7 || nslot + (int)cur.size() > ASM_NSLOT || ncomb >= NTH) return -13;
+      T.ccomb[u * NTH + ncomb++] = acomb_pack((int)cur.size(), oCarry + 8 * nslot, D.d, D.ah);
+      for (auto& q : cur) { q.d = oCarry + 8 * nslot++; pieces.push_back(q); }
+    }
+    std::vector<int> order(pieces.size());
+    for (size_t j = 0; j < order.size(); ++j) order[j] = (int)j;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return pieces[x].ops.size() > pieces[y].ops.size(); });
+    std::vector<int> load(NTH, 0);
+    for (int di : order) {
+      const int l = (int)(std::min_element(load.begin(), load.end()) - load.begin());
+      const Piece& q = pieces[di];
+      for (size_t j = 0; j < q.ops.size(); ++j) {
+        const bool lastt = j + 1 == q.ops.size();
+        lists[u][l].push_back(aterm_pack(cx(q.ops[j][0]), cx(q.ops[j][1]), cx(q.ops[j][2]), lastt ? q.d : oDump + 8 * (l & 63), !lastt, lastt && q.ah));
       }
-      c_ml = std::max(c_ml, *std::max_element(load.begin(), load.end()));
+      load[l] += (int)q.ops.size();
     }
-    c_ml = (c_ml + landing::ATAB_TB - 1) / landing::ATAB_TB * landing::ATAB_TB;
-    if (c_ml > landing::ATAB_LTMAX) return -10;
-    ctab.assign(uniq.size() * (size_t)c_ml * NTH, 0ull);
-    for (size_t u = 0; u < uniq.size(); ++u)
-      for (int l = 0; l < NTH; ++l)
-        for (int j = 0; j < c_ml; ++j)
-          ctab[(u * c_ml + j) * NTH + l] = j < (int)lists[u][l].size() ? lists[u][l][j]
-                                           : landing::aterm_pack(cx(landing::CX_ZERO), cx(landing::CX_ONE), cx(landing::CX_ONE), oDump + 8 * (l & 63), true, false);
-    ctype.assign(N, 0);
-    std::vector<int> cnt(uniq.size(), 0);
-    for (int k = 0; k < N; ++k) { ctype[k] = which[k]; cnt[which[k]]++; }
-    c_mid = (int)(std::max_element(cnt.begin(), cnt.end()) - cnt.begin());
+    T.c_ml = std::max(T.c_ml, *std::max_element(load.begin(), load.end()));
   }
-  // contiguous per-thread chunks of the flat term lists, cut at destination boundaries
-  auto chunk_at = [](const std::vector<int>& terms, int dstcol, std::vector<int>& start) {
-    const int n = (int)terms.size() / 4, NTH = landing::SOLVER_THREADS;
-    start.assign(NTH + 1, n);
-    start[0] = 0;
-    for (int t = 1; t < NTH; ++t) {
-      int want = (int)((long long)n * t / NTH);
-      if (want < start[t - 1]) want = start[t - 1];
-      while (want < n && want > 0 && terms[4 * (want - 1) + dstcol] < 0) ++want;   // previous term must close its destination
-      start[t] = want;
-    }
-  };
-  chunk_at(rterms, 2, rstart);
-  // interleave: entry j of thread t at [j * NTH + t] (coalesced 16-byte loads), padded to the longest chunk
-  auto interleave = [](std::vector<int>& terms, std::vector<int>& start, const std::array<int, 4>& pad) {
-    const int NTH = landing::SOLVER_THREADS;
-    int maxlen = 0;
-    for (int t = 0; t < NTH; ++t) maxlen = std::max(maxlen, start[t + 1] - start[t]);
-    std::vector<int> out((size_t)maxlen * NTH * 4);
-    for (int j = 0; j < maxlen; ++j) for (int t = 0; t < NTH; ++t) {
-      const int e = start[t] + j;
-      for (int q = 0; q < 4; ++q) out[((size_t)j * NTH + t) * 4 + q] = (e < start[t + 1]) ? terms[4 * (size_t)e + q] : pad[q];
-    }
-    terms.swap(out);
-    start.assign(1, maxlen);
-  };
-  for (size_t i = 0; i < rterms.size() / 4; ++i) rterms[4 * i + 3] = 1;      // valid flag
-  interleave(rterms, rstart, {0, 0, -1, 0});
-  {   // pack the interleaved records into 8 bytes: jac index | x index << 16 | dst row << 32 | closes << 48 | valid << 49
-    const size_t n = rterms.size() / 4;
-    std::vector<int> packed(2 * n);
-    for (size_t i = 0; i < n; ++i) {
-      const int ij = rterms[4 * i], ix = rterms[4 * i + 1], ir = rterms[4 * i + 2], valid = rterms[4 * i + 3];
-      if (ij < 0 || ij > 0xffff || ix < 0 || ix > 0xffff || ir > 0xffff) return -18;
-      const unsigned long long rec = (unsigned long long)ij | ((unsigned long long)ix << 16) | ((unsigned long long)(ir >= 0 ? ir : 0) << 32) |
-                                     ((unsigned long long)(ir >= 0 ? 1 : 0) << 48) | ((unsigned long long)(valid ? 1 : 0) << 49);
-      memcpy(&packed[2 * i], &rec, 8);
-    }
-    rterms.swap(packed);
+  T.c_ml = (T.c_ml + ATAB_TB - 1) / ATAB_TB * ATAB_TB;
+  if (T.c_ml > ATAB_LTMAX) return -10;
+  T.ctab.assign(types.size() * (size_t)T.c_ml * NTH, 0ull);
+  for (size_t u = 0; u < types.size(); ++u)
+    for (int l = 0; l < NTH; ++l)
+      for (int j = 0; j < T.c_ml; ++j)
+        T.ctab[(u * T.c_ml + j) * NTH + l] = j < (int)lists[u][l].size() ? lists[u][l][j] : aterm_pack(cx(CX_ZERO), cx(CX_ONE), cx(CX_ONE), oDump + 8 * (l & 63), true, false);
+
+  // row products: thread t takes the records [start[t], start[t + 1]), cut where a row closes
+  const int n = (int)rrec.size();
+  std::vector<int> start(NTH + 1, n);
+  start[0] = 0;
+  for (int t = 1; t < NTH; ++t) {
+    int want = std::max((int)((long long)n * t / NTH), start[t - 1]);
+    while (want < n && want > 0 && !((rrec[want - 1] >> 48) & 1ull)) ++want;
+    start[t] = want;
   }
+  for (int t = 0; t < NTH; ++t) T.rlen = std::max(T.rlen, start[t + 1] - start[t]);
+  T.rterm.assign((size_t)T.rlen * NTH, 0ull);      // (0: not valid)
+  for (int t = 0; t < NTH; ++t) for (int e = start[t]; e < start[t + 1]; ++e) T.rterm[(size_t)(e - start[t]) * NTH + t] = rrec[e];
   return 0;
 }
 
@@ -352,29 +242,25 @@ namespace landing {
 // context per stream (tools/bench_pipeline.py).
 int SolverWorkspace::ensure(const Layout& L, int B, hipStream_t stream) {
   if (!done && hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess) return -100;
-  if (!d_tab) {
-    std::vector<int> data, st, rt, rs, cty;
-    std::vector<unsigned long long> ctb, ccb;
-    const int rc = build_tables(L, data, st, rt, rs, ctb, ccb, cty, c_ml, c_mid);
+  if (!d_ctab) {
+    SolverTables T;
+    const int rc = build_tables(L, T);
     if (rc) return rc;
-    n_tab = (int)data.size();
-    rlen = rs[0];
     auto up = [](auto& dst, const auto& v) {
       if (dst.alloc(v.size()) != hipSuccess) return -100;
       if (hipMemcpy(dst.get(), v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice) != hipSuccess) return -101;
       return 0;
     };
-    DevBuf<int> rterm, stage_tab, ctype, tab;      // all filled before any is moved in: a failure leaves the workspace as it was
-    DevBuf<unsigned long long> ctab, ccomb;
-    int e = up(rterm, rt);
-    if (!e) e = up(stage_tab, st);
-    if (!e) e = up(ctype, cty);
-    if (!e) e = up(ctab, ctb);
-    if (!e) e = up(ccomb, ccb);
-    if (!e) e = up(tab, data);
+    DevBuf<int> ctype;      // all filled before any is moved in: a failure leaves the workspace as it was
+    DevBuf<unsigned long long> rterm, ctab, ccomb;
+    int e = up(rterm, T.rterm);
+    if (!e) e = up(ctype, T.ctype);
+    if (!e) e = up(ctab, T.ctab);
+    if (!e) e = up(ccomb, T.ccomb);
     if (e) return e;
-    d_rterm = std::move(rterm); d_stage_tab = std::move(stage_tab); d_ctype = std::move(ctype); d_ctab = std::move(ctab); d_ccomb = std::move(ccomb);
-    d_tab = std::move(tab);   // set last: d_tab set <=> all tables are resident
+    rlen = T.rlen; c_ml = T.c_ml; c_mid = T.c_mid;
+    d_rterm = std::move(rterm); d_ctype = std::move(ctype); d_ccomb = std::move(ccomb);
+    d_ctab = std::move(ctab);   // set last: d_ctab set <=> all tables are resident
   }
   const size_t need = (size_t)B * member_stride(L);
   if (buf.size() < need) {
@@ -404,6 +290,24 @@ int landing_debug_workspace(landing_ctx* ctx, double** d_ws, unsigned long long*
   return 0;
 }
 
+// diagnostic: the tables the solver kernel reads, built (without a solve) when the context has none yet
+int landing_debug_solver_tables(landing_ctx* ctx, int which, void* host_out, unsigned long long* n_bytes) {
+  if (!ctx || which < 0 || which > 4 || !n_bytes) return fail(LANDING_E_ARG, "landing_debug_solver_tables: bad argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  landing::SolverWorkspace& ws = ctx->ws;
+  const int rc = ws.ensure(ctx->L, 0, nullptr);
+  if (rc) return fail(rc <= -100 ? LANDING_E_HIP : LANDING_E_ARG, "landing_debug_solver_tables: table setup failed (" + std::to_string(rc) + ")");
+  const int scal[3] = {ws.c_ml, ws.c_mid, ws.rlen};
+  const void* src[5] = {ws.d_ctab.get(), ws.d_ccomb.get(), ws.d_ctype.get(), ws.d_rterm.get(), scal};
+  const size_t len[5] = {ws.d_ctab.size() * sizeof(*ws.d_ctab.get()), ws.d_ccomb.size() * sizeof(*ws.d_ccomb.get()), ws.d_ctype.size() * sizeof(*ws.d_ctype.get()),
+                         ws.d_rterm.size() * sizeof(*ws.d_rterm.get()), sizeof(scal)};
+  *n_bytes = len[which];
+  if (host_out && which == 4) memcpy(host_out, scal, sizeof(scal));
+  else if (host_out) HIP_TRY(hipMemcpy(host_out, src[which], len[which], hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int landing_solve_batch(landing_ctx* ctx, int B, const double* d_p, const double* d_x0, const landing_solver_opts* opts,
                         double* d_x, double* d_f, double* d_lam_g, int* d_status, int* d_iters, double* d_kkt, void* stream) {
   if (ctx && B == 0) return 0;
@@ -427,7 +331,7 @@ int landing_solve_batch(landing_ctx* ctx, int B, const double* d_p, const double
   A.L = ctx->L; A.B = B; A.o = o; A.p = d_p; A.x0 = d_x0; A.x_out = d_x; A.f_out = d_f; A.lam_out = d_lam_g;
   A.status = d_status; A.iters = d_iters; A.kkt = d_kkt; A.ws = ctx->ws.buf.get(); A.ws_stride = landing::member_stride(ctx->L);
   A.ctab = ctx->ws.d_ctab.get(); A.ctype = ctx->ws.d_ctype.get(); A.c_ml = ctx->ws.c_ml; A.c_mid = ctx->ws.c_mid; A.ccomb = ctx->ws.d_ccomb.get();
-  A.rterm = (const unsigned long long*)ctx->ws.d_rterm.get(); A.rlen = ctx->ws.rlen;
+  A.rterm = ctx->ws.d_rterm.get(); A.rlen = ctx->ws.rlen;
   A.prof = ctx->d_prof;
   A.edge_map = ctx->d_edge_map.get();
   A.order = nullptr;
@@ -736,233 +640,6 @@ int landing_wb_backward(landing_ctx* ctx, int B, int N, double dt, double reg, c
   for (int i = 0; i < 12; ++i) a.R[i] = R12[i];
   a.K = d_K; a.kff = d_kff; a.dV = d_dV; a.ok = d_ok;
   hipLaunchKernelGGL(landing::landing_wb_backward_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, a);
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-// The two derivative kernels of the kinodynamic NLP exist in two forms (rbd_kernels.hip kd_stage_rows): with the base transform of the tree taken from R and pos (the
-// floating base Px Py Pz Rx Ry Rz of the reference's model -- landing_rbd_set_model checks it) or composed joint by joint
-static void kd_launch_jac(landing_ctx* ctx, const landing::KdNlpArgs& a, long long B, int N, hipStream_t st) {
-  const dim3 grid((unsigned)landing::kd_jac_blocks(B, N)), block(landing::KD_JAC_THREADS);
-  if (ctx->rbd_std_base) hipLaunchKernelGGL(landing::landing_kinodyn_nlp_jac_kernel<1>, grid, block, 0, st, a);
-  else hipLaunchKernelGGL(landing::landing_kinodyn_nlp_jac_kernel<0>, grid, block, 0, st, a);
-}
-static void kd_launch_hess(landing_ctx* ctx, const landing::KdNlpArgs& a, long long B, int N, const unsigned char* pi, const unsigned char* pj, int npair, hipStream_t st) {
-  const dim3 grid((unsigned)landing::kd_hess_blocks(B, N, npair)), block(64);
-  if (ctx->rbd_std_base) hipLaunchKernelGGL(landing::landing_kinodyn_nlp_hess_kernel<1>, grid, block, 0, st, a, pi, pj, npair);
-  else hipLaunchKernelGGL(landing::landing_kinodyn_nlp_hess_kernel<0>, grid, block, 0, st, a, pi, pj, npair);
-}
-
-int landing_kinodyn_nlp_dims(int N, long long* nx, long long* ng) {
-  if (N < 2 || N > 64) return fail(LANDING_E_ARG, "landing_kinodyn_nlp_dims: 2 <= N <= 64");
-  if (nx) *nx = landing::kd_nx(N);
-  if (ng) *ng = landing::kd_ng(N);
-  return 0;
-}
-
-int landing_kinodyn_nlp_eval(landing_ctx* ctx, int B, int N, const double* d_x, const landing_kinodyn_params* prm, double* d_g, double* d_jac, void* stream) {
-  if (ctx && B == 0) return 0;
-  if (!ctx || B < 0 || N < 2 || N > 64 || !d_x || !prm || (!d_g && !d_jac)) return fail(LANDING_E_ARG, "landing_kinodyn_nlp_eval: bad argument");
-  if (!ctx->d_rbd) return fail(LANDING_E_ARG, "landing_kinodyn_nlp_eval: no model (landing_rbd_set_model)");
-  HIP_TRY(hipSetDevice(ctx->device));
-  landing::KdNlpArgs a;
-  a.sx = a.sg = a.sj = a.sh = 0; a.skip = nullptr;
-  a.model = ctx->d_rbd.get(); a.B = B; a.N = N; a.x = d_x; a.g = d_g; a.jac = d_jac; a.lam = nullptr; a.hess = nullptr;
-  for (int k = 0; k < 64; ++k) a.P.dt[k] = k < N ? prm->dt[k] : 0.0;
-  a.P.mass = prm->mass; a.P.mu = prm->mu; a.P.std_base = ctx->rbd_std_base;
-  for (int i = 0; i < 3; ++i) { a.P.Ib[i] = prm->Ib[i]; a.P.Ibi[i] = prm->Ib_inv[i]; }
-  if (d_g) {
-    const long long n = (long long)B * N;
-    hipLaunchKernelGGL(landing::landing_kinodyn_nlp_g_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
-  }
-  if (d_jac) {
-    const long long n = (long long)B * N * landing::KD_NW;
-    kd_launch_jac(ctx, a, B, N, (hipStream_t)stream);
-  }
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-// The pairs (i <= j) of a Hessian block of the kinodynamic NLP that are evaluated: kd_pair_list's 561 candidates (one leg's variables couple with
-// themselves and the base only, ...) thinned out to those whose entry is not structurally zero.  Which those are is asked of the derivative kernel
-// itself, once per context (round 5): the candidates are evaluated on a few members with random variables and multipliers (three intervals: two
-// middle ones and a last one) and a pair is kept when its entry is non-zero anywhere -- a mixed second derivative through hyper-dual numbers is
-// exactly 0.0 when no row couples the two variables (friction and contact rows are linear in the forces, the FK band is linear in the feet and the
-// body position, omega x I omega has no squares, ...).  286 of the 561 remain; tests/test_n1_rows.py checks EVERY column of the blocks against
-// central differences of the exact Jacobian, which also proves this list.  Caller holds ctx->mu.
-static int kd_ensure_pairs(landing_ctx* ctx, const landing::KdNlpParams& P) {
-  if (ctx->d_kd_pairs) return 0;
-  const int NP = landing::KD_NPAIR;
-  unsigned char host[2 * landing::KD_NPAIR];
-  if (landing::kd_pair_list(host, host + NP) != NP) return fail(LANDING_E_ARG, "kinodynamic NLP: internal pair table");
-  const int B = 6, N = 3, NW = landing::KD_NW;
-  const size_t nx = (size_t)landing::kd_nx(N), ng = (size_t)landing::kd_ng(N), nh = (size_t)B * N * NW * NW;
-  std::vector<double> hx(B * nx), hl(B * ng), hh(nh);
-  unsigned long long sdd = 0x9E3779B97F4A7C15ull;
-  auto rnd = [&]() { sdd = sdd * 6364136223846793005ull + 1442695040888963407ull; return (double)((sdd >> 11) & 0xFFFFFFFFFFFFFull) / 4503599627370496.0; };      // [0, 1)
-  for (auto& v : hx) v = rnd() - 0.5;
-  for (auto& v : hl) v = (0.5 + rnd()) * (rnd() < 0.5 ? -1.0 : 1.0);
-  DevBuf<unsigned char> d_full; DevBuf<double> d_x, d_l, d_h;
-  HIP_TRY(d_full.alloc(sizeof(host))); HIP_TRY(hipMemcpy(d_full.get(), host, sizeof(host), hipMemcpyHostToDevice));
-  HIP_TRY(d_x.alloc(hx.size())); HIP_TRY(hipMemcpy(d_x.get(), hx.data(), hx.size() * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(d_l.alloc(hl.size())); HIP_TRY(hipMemcpy(d_l.get(), hl.data(), hl.size() * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(d_h.alloc(nh)); HIP_TRY(hipMemset(d_h.get(), 0, nh * sizeof(double)));
-  landing::KdNlpArgs a;
-  a.sx = a.sg = a.sj = a.sh = 0; a.skip = nullptr;
-  a.model = ctx->d_rbd.get(); a.B = B; a.N = N; a.x = d_x.get(); a.g = nullptr; a.jac = nullptr; a.lam = d_l.get(); a.hess = d_h.get(); a.P = P;
-  // The structure must not depend on the caller's parameter VALUES (ADVICE r5: with Ib = (0.03, 0.03, 0.03) the omega-omega entries of omega x I omega vanish and a later
-  // call with the real inertia got 36 wrong zeros): the probe runs with fixed generic constants -- distinct inertias, mu > 0, unit mass, a uniform grid -- so that only the model
-  // (landing_rbd_set_model invalidates the table) and the formulation decide which pairs are kept.
-  for (int k = 0; k < 64; ++k) a.P.dt[k] = k < N ? 0.03 : 0.0;
-  a.P.mass = 1.0; a.P.mu = 0.7; a.P.Ib[0] = 0.05; a.P.Ib[1] = 0.2; a.P.Ib[2] = 0.3; a.P.Ibi[0] = 17.0; a.P.Ibi[1] = 4.3; a.P.Ibi[2] = 3.6;
-  const long long n = (long long)B * N * NP;
-  kd_launch_hess(ctx, a, B, N, d_full.get(), d_full.get() + NP, NP, (hipStream_t)nullptr);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(hh.data(), d_h.get(), nh * sizeof(double), hipMemcpyDeviceToHost));
-  unsigned char keep[2 * landing::KD_NPAIR]; int nk = 0;
-  for (int q = 0; q < NP; ++q) {
-    const int i = host[q], j = host[NP + q];
-    bool nz = false;
-    for (int b = 0; b < B && !nz; ++b) for (int k = 0; k < N && !nz; ++k) { const double v = hh[(((size_t)b * N + k) * NW + i) * NW + j]; nz = v != 0.0 || v != v; }
-    if (nz) { keep[nk] = (unsigned char)i; keep[NP + nk] = (unsigned char)j; ++nk; }
-  }
-  if (nk < 1) return fail(LANDING_E_ARG, "kinodynamic NLP: empty pair table");
-  // Wavefront-pure order: a lane's pair decides which legs' kinematic rows it evaluates (kd_stage_rows' legmask: all four for a pair inside the base, one for a pair
-  // that involves a leg), and a wavefront runs the rows of every leg any of its lanes needs.  The pairs of the base fill their own wavefront(s), then leg by leg,
-  // each class padded to a multiple of 64 with empty entries (255: the lane leaves at once).
-  unsigned char packed[2 * 1024]; int np_ = 0;
-  {
-    unsigned char oi[1024], oj[1024];
-    for (int cls = -1; cls < 4; ++cls) {
-      for (int q = 0; q < nk; ++q) if (landing::kd_pair_leg(keep[q], keep[NP + q]) == cls) { oi[np_] = keep[q]; oj[np_] = keep[NP + q]; ++np_; }
-      while (np_ % 64) { oi[np_] = 255; oj[np_] = 255; ++np_; }
-    }
-    for (int q = 0; q < np_; ++q) { packed[q] = oi[q]; packed[np_ + q] = oj[q]; }
-  }
-  nk = np_;
-  DevBuf<unsigned char> d_pairs;
-  HIP_TRY(d_pairs.alloc((size_t)2 * nk));
-  HIP_TRY(hipMemcpy(d_pairs.get(), packed, (size_t)2 * nk, hipMemcpyHostToDevice));
-  ctx->d_kd_pairs = std::move(d_pairs); ctx->kd_npair = nk;
-  return 0;
-}
-
-// Structural non-zeros of the inequality rows of the kinodynamic NLP's Jacobian blocks (landing::KdJPat, read by the solver's forward sweep: ds = J_I dx over the non-zeros
-// only).  Asked of the Jacobian kernel itself, once per context, like the pair table above: random variables on six members of a four-interval problem with fixed generic
-// constants; an entry is kept when it is non-zero on any member (a forward-mode derivative is exactly 0.0 where the row does not depend on the variable).  The three
-// intervals that are not the last must agree (they do: the rows depend on the interval through dt only).  tests/test_n1_rows.py checks every column of the blocks against
-// central differences; tests/test_kd_solver_cpu.py pins the counts (529 / 457).  Caller holds ctx->mu.
-static int kd_ensure_jpat(landing_ctx* ctx) {
-  if (ctx->d_kd_jpat) return 0;
-  const int B = 6, N = 4, NW = landing::KD_NW, NR = landing::KD_ROWS;
-  const size_t nx = (size_t)landing::kd_nx(N), nj = (size_t)B * N * NR * NW;
-  std::vector<double> hx(B * nx), hj(nj);
-  unsigned long long sdd = 0x2545F4914F6CDD1Dull;
-  auto rnd = [&]() { sdd = sdd * 6364136223846793005ull + 1442695040888963407ull; return (double)((sdd >> 11) & 0xFFFFFFFFFFFFFull) / 4503599627370496.0; };      // [0, 1)
-  for (auto& v : hx) v = rnd() - 0.4;
-  DevBuf<double> d_x, d_j;
-  HIP_TRY(d_x.alloc(hx.size())); HIP_TRY(hipMemcpy(d_x.get(), hx.data(), hx.size() * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(d_j.alloc(nj)); HIP_TRY(hipMemset(d_j.get(), 0, nj * sizeof(double)));
-  landing::KdNlpArgs a;
-  a.sx = a.sg = a.sj = a.sh = 0; a.skip = nullptr;
-  a.model = ctx->d_rbd.get(); a.B = B; a.N = N; a.x = d_x.get(); a.g = nullptr; a.jac = d_j.get(); a.lam = nullptr; a.hess = nullptr;
-  for (int k = 0; k < 64; ++k) a.P.dt[k] = k < N ? 0.03 : 0.0;
-  a.P.mass = 1.0; a.P.mu = 0.7; a.P.Ib[0] = 0.05; a.P.Ib[1] = 0.2; a.P.Ib[2] = 0.3; a.P.Ibi[0] = 17.0; a.P.Ibi[1] = 4.3; a.P.Ibi[2] = 3.6; a.P.std_base = ctx->rbd_std_base;
-  kd_launch_jac(ctx, a, B, N, (hipStream_t)nullptr);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(hj.data(), d_j.get(), nj * sizeof(double), hipMemcpyDeviceToHost));
-  auto nz = [&](int k, int r, int c) { for (int b = 0; b < B; ++b) { const double v = hj[(((size_t)b * N + k) * NR + r) * NW + c]; if (v != 0.0 || v != v) return true; } return false; };
-  for (int r = 12; r < NR; ++r) for (int c = 0; c < NW; ++c)
-    if (nz(0, r, c) != nz(1, r, c) || nz(1, r, c) != nz(2, r, c)) return fail(LANDING_E_ARG, "kinodynamic NLP: the Jacobian blocks of two middle intervals differ in structure");
-  std::vector<landing::KdJPat> T(1);
-  memset(T.data(), 0, sizeof(landing::KdJPat));
-  std::vector<landing::KdCPat> Cp(1);
-  memset(Cp.data(), 0, sizeof(landing::KdCPat));
-  for (int lp = 0; lp < 2; ++lp) {
-    const int k = lp ? N - 1 : 1, nrow = (lp ? landing::KD_ROWS_LAST : NR) - 12;
-    std::vector<std::vector<int>> cols(nrow);
-    for (int j = 0; j < nrow; ++j) for (int c = 0; c < NW; ++c) if (nz(k, 12 + j, c)) cols[j].push_back(c);
-    std::vector<int> order(nrow);
-    for (int j = 0; j < nrow; ++j) order[j] = j;
-    std::stable_sort(order.begin(), order.end(), [&](int p, int q) { return cols[p].size() > cols[q].size(); });
-    int n = 0;
-    for (int j = 0; j < nrow; ++j) {
-      const std::vector<int>& cj = cols[order[j]];
-      if ((int)cj.size() > landing::KD_JP_MAX || n + (int)cj.size() > landing::KD_JP_NNZ - landing::KD_JP_MAX) return fail(LANDING_E_ARG, "kinodynamic NLP: Jacobian block denser than the table of its non-zeros");
-      T[0].perm[lp][j] = (unsigned char)(12 + order[j]); T[0].rp[lp][j] = (unsigned short)n;
-      for (int c : cj) T[0].cl[lp][n++] = (unsigned char)c;
-    }
-    T[0].rp[lp][nrow] = (unsigned short)n;
-    ctx->kd_jpat_nnz[lp] = n;
-    // place table of the compact block (KdNlpArgs::jpos): defect rows dense, inequality entries in table order
-    {
-      std::vector<std::vector<unsigned>> colv(NW);
-      for (int c = 0; c < NW; ++c) for (int r = 0; r < 12; ++r) colv[c].push_back(((unsigned)r << 16) | (unsigned)(r * NW + c));
-      for (int j = 0; j < nrow; ++j) for (int t = T[0].rp[lp][j]; t < T[0].rp[lp][j + 1]; ++t) colv[T[0].cl[lp][t]].push_back(((unsigned)T[0].perm[lp][j] << 16) | (unsigned)(landing::KD_JC_DEF + t));
-      for (int c = 0; c < NW; ++c) {
-        std::sort(colv[c].begin(), colv[c].end());      // (by row: the kernel emits the rows of a column in rising order)
-        if ((int)colv[c].size() >= landing::KD_JCOL) return fail(LANDING_E_ARG, "kinodynamic NLP: a column of the Jacobian block has more entries than its list holds");
-        for (size_t i = 0; i < colv[c].size(); ++i) Cp[0].jcol[lp][c][i] = colv[c][i];
-        for (int i = (int)colv[c].size(); i < landing::KD_JCOL; ++i) Cp[0].jcol[lp][c][i] = 0xffff0000u;
-      }
-    }
-    // the condensation over these entries (landing::KdCPat): stage variable v of block column w (the inequality rows do not see X_k+1, columns 48..59)
-    const int nv = lp ? 48 : landing::KD_NV;
-    auto vof = [&](int w) { return w < 48 ? w : (w >= 60 ? w - 12 : -1); };
-    std::map<std::pair<int, int>, std::vector<unsigned>> dest;
-    std::vector<std::vector<unsigned>> rhs(landing::KD_NV);
-    for (int j = 0; j < nrow; ++j)
-      for (int ta = T[0].rp[lp][j]; ta < T[0].rp[lp][j + 1]; ++ta) {
-        Cp[0].erow[lp][ta] = (unsigned char)j;
-        const int va = vof(T[0].cl[lp][ta]);
-        if (va < 0 || va >= nv) return fail(LANDING_E_ARG, "kinodynamic NLP: an inequality row depends on a variable outside its stage");
-        rhs[va].push_back((unsigned)ta | ((unsigned)j << 10));
-        for (int tb = T[0].rp[lp][j]; tb < T[0].rp[lp][j + 1]; ++tb) {
-          const int vb = vof(T[0].cl[lp][tb]);
-          if (vb >= va) dest[{va, vb}].push_back((unsigned)ta | ((unsigned)tb << 10) | ((unsigned)j << 20));
-        }
-      }
-    std::vector<std::pair<std::pair<int, int>, std::vector<unsigned>>> dl(dest.begin(), dest.end());
-    std::stable_sort(dl.begin(), dl.end(), [](const auto& p, const auto& q) { return p.second.size() > q.second.size(); });      // lanes of a wavefront: destinations of similar length
-    int nd = 0, nt = 0;
-    for (const auto& e : dl) {
-      if (nd >= landing::KD_CP_ND || nt + (int)e.second.size() > landing::KD_CP_NT) return fail(LANDING_E_ARG, "kinodynamic NLP: condensation table too small");
-      Cp[0].drp[lp][nd] = (unsigned short)nt; Cp[0].dab[lp][nd] = (unsigned short)(e.first.first | (e.first.second << 8));
-      for (unsigned w : e.second) Cp[0].dterm[lp][nt++] = w;
-      ++nd;
-    }
-    Cp[0].drp[lp][nd] = (unsigned short)nt; Cp[0].nd[lp] = nd; Cp[0].nt[lp] = nt;
-    int nr = 0;
-    for (int v = 0; v < landing::KD_NV; ++v) { Cp[0].rrp[lp][v] = (unsigned short)nr; for (unsigned w : rhs[v]) Cp[0].rterm[lp][nr++] = w; }
-    Cp[0].rrp[lp][landing::KD_NV] = (unsigned short)nr;
-  }
-  DevBuf<unsigned char> d_t;      // [KdJPat | KdCPat]
-  constexpr size_t JP8 = (sizeof(landing::KdJPat) + 15) / 16 * 16;
-  HIP_TRY(d_t.alloc(JP8 + sizeof(landing::KdCPat)));
-  HIP_TRY(hipMemcpy(d_t.get(), T.data(), sizeof(landing::KdJPat), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_t.get() + JP8, Cp.data(), sizeof(landing::KdCPat), hipMemcpyHostToDevice));
-  ctx->kd_cpat_off = JP8;
-  ctx->d_kd_jpat = std::move(d_t);
-  return 0;
-}
-
-int landing_kinodyn_nlp_hess(landing_ctx* ctx, int B, int N, const double* d_x, const landing_kinodyn_params* prm, const double* d_lam_g, double* d_hess, void* stream) {
-  if (ctx && B == 0) return 0;
-  if (!ctx || B < 0 || N < 2 || N > 64 || !d_x || !prm || !d_lam_g || !d_hess) return fail(LANDING_E_ARG, "landing_kinodyn_nlp_hess: bad argument");
-  if (!ctx->d_rbd) return fail(LANDING_E_ARG, "landing_kinodyn_nlp_hess: no model (landing_rbd_set_model)");
-  HIP_TRY(hipSetDevice(ctx->device));
-  landing::KdNlpArgs a;
-  a.sx = a.sg = a.sj = a.sh = 0; a.skip = nullptr;
-  a.model = ctx->d_rbd.get(); a.B = B; a.N = N; a.x = d_x; a.g = nullptr; a.jac = nullptr; a.lam = d_lam_g; a.hess = d_hess;
-  for (int k = 0; k < 64; ++k) a.P.dt[k] = k < N ? prm->dt[k] : 0.0;
-  a.P.mass = prm->mass; a.P.mu = prm->mu; a.P.std_base = ctx->rbd_std_base;
-  for (int i = 0; i < 3; ++i) { a.P.Ib[i] = prm->Ib[i]; a.P.Ibi[i] = prm->Ib_inv[i]; }
-  std::lock_guard<std::mutex> lock(ctx->mu);      // (the lazily built table below, like every other lazily created resource of the context)
-  { const int rc = kd_ensure_pairs(ctx, a.P); if (rc) return rc; }      // the list of structurally non-zero pairs of a block, built once per context
-  const long long n = (long long)B * N * ctx->kd_npair;
-  if (n > 0x7fffffffLL * 64) return fail(LANDING_E_ARG, "landing_kinodyn_nlp_hess: batch too large for one launch");
-  HIP_TRY(hipMemsetAsync(d_hess, 0, (size_t)B * N * landing::KD_NW * landing::KD_NW * sizeof(double), (hipStream_t)stream));
-  kd_launch_hess(ctx, a, B, N, ctx->d_kd_pairs.get(), ctx->d_kd_pairs.get() + ctx->kd_npair, ctx->kd_npair, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return 0;
 }

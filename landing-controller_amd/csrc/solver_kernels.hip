@@ -38,28 +38,12 @@ constexpr int RIC_K = 0, RIC_KAP = 576, RIC_MT = 600, RIC_MV = 888, RIC_PX = 900
 constexpr int RIC_FWD0 = 288, RIC_FWDN = 612;   // forward chain reads rec[288, 900): K rows of c+ | kappa | Mt | mv
 constexpr int FILT_CAP = 64;
 constexpr int SOLVER_NMAX = 96;   // longest horizon the solver kernel takes: sigma_0..sigma_N of the forward sweep live in the 48 x 49 LDS array, one table row per stage
-constexpr int ES = 26;    // LDS row stride of the elimination side block [gamma_u | I] (24 x 25)
 constexpr int SOLVER_THREADS = 256;
-// condensed stage data (LDS staging area of the backward sweep): [G targets (table order) | gamma 48 | A^ values] of one stage
-constexpr int COND_GAM = 480, COND_AH = 528, COND_STRIDE = 704;
 constexpr int RCG = 36;   // per stage in the member's workspace: gradient of the running cost w.r.t. (X_k, c_k, f_k) (forms with a running cost)
 // constant Hessian entries of the running cost per stage, stored right behind the Hessian nonzeros so that the
 // condensation tables address them like any other entry of [J | H]: X diagonal (12) | (pos_a, c_leg,a) (12) | c diagonal (12) | f diagonal (12)
 constexpr int RUNC = 48;
 
-// Packed condensation term (8 bytes), stage-local: value = JH[a] * (has_b ? JH[b] : 1) * coeff, coeff = sigma[row] (has_b) /
-// rho[row] (!has_b) for rtype 0, +1 / -1 / 0 for rtype 1 / 2 / 3; summed into the open destination, stored to
-// stg[dst] when `closes`.  a, b = positions in the stage's LDS copy of its nonzeros (segment sa at NZ_*[sa], offset oa inside):
-// segments 0..6 = J X_k | J U_k | J U_{k+1} | H X_k | H U_k | H U_{k+1} | running-cost constants of stage k.
-constexpr int CTAB_MLMAX = 6;
-__host__ __device__ inline unsigned long long cterm_pack(int sa, int oa, int sb, int ob, bool has_b, int rowq, int rtype, int dst, bool closes) {
-  const int nz[7] = {NZ_JX, NZ_JU, NZ_JUN, NZ_HX, NZ_HU, NZ_HUN, NZ_TOT};
-  const unsigned pa = (unsigned)(nz[sa] + oa), pb = (unsigned)(nz[sb] + ob);
-  const unsigned lo = pa | (pb << 11) | ((unsigned)(has_b ? 1 : 0) << 22) | ((unsigned)rowq << 23) | ((unsigned)rtype << 30);
-  const unsigned hi = (unsigned)dst | ((unsigned)(closes ? 1 : 0) << 10);
-  return (unsigned long long)lo | ((unsigned long long)hi << 32);
-}
-__host__ __device__ inline bool cterm_closes(unsigned long long t) { return ((t >> 42) & 1ull) != 0; }
 // Assembly of a stage inside the backward sweep (asm_terms): operands of the condensation terms are positions in the LDS array
 // cx = [nonzeros of the stage (NZ_TOT + RUNC) | sigma (104) | rho (104) | 1, -1, 0]
 constexpr int CX_SR = NZ_TOT + 48, CX_ONE = CX_SR + 208, CX_MONE = CX_ONE + 1, CX_ZERO = CX_ONE + 2, CX_LEN = CX_ONE + 3;
@@ -171,8 +155,7 @@ static_assert(2 * XCH >= 24 * YS, "A1 also holds Y (24 x YS)");
 struct Lds {
   double G[48 * GS];
   double P[24 * PS];
-  double A1[2 * XCH];          // Y = P(:,0:12)*A^ (24 x YS = 888) while T^T P T is formed, then the elimination side block
-                              // Ex (24 x ES): col 0 = gamma_u -> z, cols 1.. = I -> unit-lower inverse
+  double A1[2 * XCH];          // Y = P(:,0:12)*A^ (24 x YS = 888) while T^T P T is formed, then the exchange buffers of the blocked elimination
   double Ah[2 * 12 * YS];      // A^ of the stage being eliminated and of the one being assembled (copy k & 1 belongs to stage k)
   double gam[48], q[24], sig[24], w[48], dinv[24];      // (gam: the foot block of stage 0 only -- gamma of a stage is column 48 of G, p column 24 of P, b column 36 of A^)
   double red[(SOLVER_THREADS / 64) * 9];      // (the fused first-trial pass reduces 3 line-search sums + 6 quantities of the new point at once)
