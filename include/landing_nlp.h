@@ -691,6 +691,26 @@ int landing_kinodyn_pattern(landing_ctx* ctx, int N, int which, long long* colin
  * when `entries` is not NULL, the table itself as (row, column) byte pairs, the first *nnz_mid pairs for a middle interval, then *nnz_last for the last
  * (room for 2 x 1280 bytes).  Built once per context by asking the Jacobian kernel (device needed); it must agree with landing_kinodyn_pattern. */
 int landing_kinodyn_block_nonzeros(landing_ctx* ctx, int* nnz_mid, int* nnz_last, unsigned char* entries);
+/* Diagnostics: a read-only view of the workspace landing_kinodyn_solve_batch[_host] leaves behind (layout: csrc/kd_solver_kernels.hip, kd_carve).  None of them
+ * changes a solve.  tests/test_kd_step_cpu.py and tests/test_gpu_kd_step.py use them to check the Newton step of the refinement solver against an independent KKT solve.
+ * landing_debug_kd_workspace: device pointer and member stride (doubles) of the workspace of the LAST solve of this context, optionally its horizon and the number of
+ *   member blocks (the callers' B, then the portfolio's clone slots).  Member m's block starts at d_ws + m * stride.  LANDING_E_ARG when no such solve has run, or when the
+ *   last one failed before all its launches were queued (the view is valid only for a solve that returned 0).
+ * landing_debug_kd_layout: for a horizon N, offsets[LANDING_KD_LAYOUT_N] (doubles from the start of a member's block) of the arrays
+ *     x, dx, g, s, ds, zL, zU, y, yn, sig, rho, gc          (in this order; x, dx: nx doubles; g .. rho: ng doubles; gc: N x (60 x 60 + 60), see below)
+ *   and, when not NULL, the offset of the member's iteration state and the member stride.  Read off kd_carve itself.  After a solve the block holds x, g, s, zL, zU,
+ *   y, sig, rho of the LAST iterate and dx, ds, yn (the defect rows' multipliers; other rows of yn are not meaningful), gc of the last Newton step: per interval k the
+ *   inequality rows' J_I' Sigma J_I (60 x 60, row major, over v = (X_k, c_k, f_k, jpos_k, c_k+1)) and J_I' rho (60).  The outputs of the solve overwrite y[0:24].
+ * landing_debug_kd_state: member's iteration scalars as out[LANDING_KD_STATE_N] doubles:
+ *   [0] mu  barrier parameter of the last step   [1] delta  regularisation of the last factorisation tried   [2] delta_last   [3] alpha   [4] a_du
+ *   [5] it  iterations counted   [6] nfact  factorisations of the whole solve   [7] nreset   [8] last_reset_it   [9] feas  1 inside the feasibility phase
+ *   [10] status   [11] pending  1: the inertia correction waits for the next launch   [12] omt  > 0: clip_k rule in force in the last step   [13] s_corr
+ *   [14] done   [15] reg_it  iteration of the last regularised factorisation */
+#define LANDING_KD_LAYOUT_N 12
+#define LANDING_KD_STATE_N 16
+int landing_debug_kd_workspace(landing_ctx* ctx, double** d_ws, unsigned long long* stride, int* N, int* members);
+int landing_debug_kd_layout(int N, unsigned long long* offsets, unsigned long long* state_offset, unsigned long long* stride);
+int landing_debug_kd_state(landing_ctx* ctx, int member, double* out);
 
 /* ---- CasADi-external face of the kinodynamic refinement NLP (round 6) ------------------------------------------------------------------------
  * What landingCtrller_KNITRO_mi355x.so (csrc/casadi_abi.cpp with -DLANDING_KD=1) forwards to: the seven nlp_* functions of the library the reference generates

@@ -77,7 +77,8 @@ EXPORTS = ["landing_last_error", "landing_form_default", "landing_solver_opts_de
            "landing_kinodyn_rows_batch", "landing_kinodyn_nlp_dims", "landing_kinodyn_nlp_eval", "landing_kinodyn_nlp_hess", "landing_leg_ik_batch", "landing_nnz_hess_rc", "landing_pattern_hess_rc",
            "landing_eval_hess_rc_batch", "landing_eval_hess_rc_batch_host",
            "landing_stream_create", "landing_stream_destroy", "landing_stream_lanes", "landing_stream_submit", "landing_stream_wait", "landing_stream_sync", "landing_solve_stream_host",
-           "landing_sample_reference_batch", "landing_tracking_gains_batch", "landing_tracking_gains_host"]
+           "landing_sample_reference_batch", "landing_tracking_gains_batch", "landing_tracking_gains_host",
+           "landing_debug_kd_workspace", "landing_debug_kd_layout", "landing_debug_kd_state"]
 
 
 # Sizes the solver kernel's workspace layout is built from (csrc/solver_kernels.hip: RUNC, RIC_STRIDE, RCG, EXIT_REC)

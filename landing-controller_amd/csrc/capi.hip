@@ -101,6 +101,7 @@ struct landing_ctx {
   // fenced by this event (recorded behind them, waited for before the next writer / reader touches the block) -- ADVICE r2
   hipEvent_t scratch_done = nullptr;
   DevBuf<double> d_kd_ws; DevBuf<int> d_kd_active, d_kd_done;      // workspace of landing_kinodyn_solve_batch (kd_capi.inc), count of members still iterating
+  int kd_ws_N = 0, kd_ws_B = 0;      // horizon and member blocks (clone slots included) of the last landing_kinodyn_solve_batch: what landing_debug_kd_workspace describes
   int kd_jpat_nnz[2] = {0, 0}; size_t kd_cpat_off = 0;
   DevBuf<unsigned char> d_kd_jpat;      // [landing::KdJPat | landing::KdCPat at kd_cpat_off]: structural non-zeros of the kinodynamic NLP's Jacobian blocks (kd_ensure_jpat, kd_capi.inc)
   DevBuf<unsigned char> d_kd_pairs; int kd_npair = 0; int rbd_std_base = 0;      // structurally non-zero pairs of a Hessian block of the kinodynamic NLP ([2][kd_npair]: i | j; kd_capi.inc, kd_ensure_pairs)

@@ -297,6 +297,7 @@ int landing_kinodyn_solve_batch(landing_ctx* ctx, int B, int N, const landing_ki
     if (ctx->d_kd_ws) HIP_TRY(hipDeviceSynchronize());      // (a launch of an earlier call may still use the old block)
     HIP_TRY(ctx->d_kd_ws.grow(need));
   }
+  ctx->kd_ws_N = 0; ctx->kd_ws_B = 0;      // (the debug view describes a workspace only once every launch of this solve is queued: below)
   // counters: derivative list A | members still iterating | members the head kernel has prepared this round | derivative list B  (the two in the middle and the list of the NEXT round are cleared by one memset per round)
   if (!ctx->d_kd_active) HIP_TRY(ctx->d_kd_active.alloc(4));
   const size_t nflag = (size_t)BT + S + 3 * B + 3 * BT;      // done [BT] | src [S] | win [B] | cloned [B] | win_prev [B] | work list of the condensation [BT] | derivative lists A, B [BT] each
@@ -402,6 +403,7 @@ int landing_kinodyn_solve_batch(landing_ctx* ctx, int B, int N, const landing_ki
   if (active > 0) derivs(false);      // members stopped by the iteration limit: their J blocks belong to the previous iterate
   hipLaunchKernelGGL(landing::landing_kd_finish_kernel, dim3(B), dim3(landing::KD_THREADS), 0, st, A);
   HIP_TRY(hipGetLastError());
+  ctx->kd_ws_N = N; ctx->kd_ws_B = BT;
   return 0;      // (scratch_guard records the fence)
 }
 
@@ -661,6 +663,43 @@ int landing_kinodyn_block_nonzeros(landing_ctx* ctx, int* nnz_mid, int* nnz_last
       for (int j = 0; j < nrow; ++j) for (int t = T[0].rp[lp][j]; t < T[0].rp[lp][j + 1]; ++t) { entries[n++] = T[0].perm[lp][j]; entries[n++] = T[0].cl[lp][t]; }
     }
   }
+  return 0;
+}
+
+// ---- diagnostics: a read-only view of a member's block of the refinement solver's workspace (landing_nlp.h) ----------------------------
+int landing_debug_kd_workspace(landing_ctx* ctx, double** d_ws, unsigned long long* stride, int* N, int* members) {
+  if (!ctx || !d_ws || !stride) return fail(LANDING_E_ARG, "landing_debug_kd_workspace: bad argument");
+  if (!ctx->d_kd_ws || ctx->kd_ws_N < 2) return fail(LANDING_E_ARG, "landing_debug_kd_workspace: no kinodynamic solve has run in this context");
+  *d_ws = ctx->d_kd_ws.get(); *stride = (unsigned long long)landing::kd_ws_stride(ctx->kd_ws_N);
+  if (N) *N = ctx->kd_ws_N;
+  if (members) *members = ctx->kd_ws_B;
+  return 0;
+}
+
+int landing_debug_kd_layout(int N, unsigned long long* offsets, unsigned long long* state_offset, unsigned long long* stride) {
+  if (N < 2 || N > 64 || !offsets) return fail(LANDING_E_ARG, "landing_debug_kd_layout: bad argument");
+  // kd_carve itself over a host block of one member's size (never read or written): the one statement of the layout
+  std::vector<double> block(landing::kd_ws_stride(N));
+  double* const base = block.data();
+  const landing::KdMem M = landing::kd_carve(N, base);
+  const double* const arr[LANDING_KD_LAYOUT_N] = {M.x, M.dx, M.g, M.s, M.ds, M.zL, M.zU, M.y, M.yn, M.sig, M.rho, M.gc};
+  for (int i = 0; i < LANDING_KD_LAYOUT_N; ++i) offsets[i] = (unsigned long long)(arr[i] - base);
+  if (state_offset) *state_offset = (unsigned long long)(reinterpret_cast<const double*>(M.st) - base);
+  if (stride) *stride = (unsigned long long)landing::kd_ws_stride(N);
+  return 0;
+}
+
+int landing_debug_kd_state(landing_ctx* ctx, int member, double* out) {
+  if (!ctx || !out || member < 0) return fail(LANDING_E_ARG, "landing_debug_kd_state: bad argument");
+  if (!ctx->d_kd_ws || ctx->kd_ws_N < 2) return fail(LANDING_E_ARG, "landing_debug_kd_state: no kinodynamic solve has run in this context");
+  if (member >= ctx->kd_ws_B) return fail(LANDING_E_ARG, "landing_debug_kd_state: no such member in the last solve");
+  HIP_TRY(hipSetDevice(ctx->device));
+  const landing::KdMem M = landing::kd_carve(ctx->kd_ws_N, ctx->d_kd_ws.get() + (size_t)member * landing::kd_ws_stride(ctx->kd_ws_N));
+  landing::KdState K;
+  HIP_TRY(hipMemcpy(&K, M.st, sizeof(K), hipMemcpyDeviceToHost));      // (synchronises with the solve that wrote it)
+  const double v[LANDING_KD_STATE_N] = {K.mu, K.delta, K.delta_last, K.alpha, K.a_du, (double)K.it, (double)K.nfact, (double)K.nreset, (double)K.last_reset_it, (double)K.feas,
+                                        (double)K.status, (double)K.pending, K.omt, K.s_corr, (double)K.done, (double)K.reg_it};
+  for (int i = 0; i < LANDING_KD_STATE_N; ++i) out[i] = v[i];
   return 0;
 }
 

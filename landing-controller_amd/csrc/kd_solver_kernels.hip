@@ -71,7 +71,7 @@ __host__ __device__ inline size_t kd_ws_stride(int N) {
   const size_t nx = (size_t)kd_nx(N), ng = (size_t)kd_ng(N);
   return 4 * nx + 10 * ng + (size_t)N * KD_JCS + (size_t)N * KD_NW * KD_NW + (size_t)(N + 1) * KD_REC + 2 * (size_t)N * KD_NW + 4 * ng + (size_t)N * KD_GC + (sizeof(KdState) + 7) / 8 + 8;
 }
-__device__ __forceinline__ KdMem kd_carve(int N, double* w) {
+__host__ __device__ __forceinline__ KdMem kd_carve(int N, double* w) {      // (host: landing_debug_kd_layout reads the layout off it)
   const size_t nx = (size_t)kd_nx(N), ng = (size_t)kd_ng(N);
   KdMem M;
   M.x = w; w += nx; M.xt = w; w += nx; M.dx = w; w += nx; M.gx = w; w += nx;

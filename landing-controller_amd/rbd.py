@@ -308,6 +308,53 @@ class Rbd:
         e = buf[:2 * (n0.value + n1.value)].reshape(-1, 2).astype(int)
         return (e[:n0.value, 0], e[:n0.value, 1]), (e[n0.value:, 0], e[n0.value:, 1])
 
+    # ---- diagnostics: the workspace the refinement solve leaves behind (include/landing_nlp.h landing_debug_kd_*) ----
+    KD_LAYOUT = ("x", "dx", "g", "s", "ds", "zL", "zU", "y", "yn", "sig", "rho", "gc")
+    KD_STATE = ("mu", "delta", "delta_last", "alpha", "a_du", "it", "nfact", "nreset", "last_reset_it", "feas", "status", "pending", "omt", "s_corr", "done", "reg_it")
+    KD_GC = 60 * 60 + 60
+
+    def kinodyn_workspace_layout(self, N):
+        """landing_debug_kd_layout: dict name -> (offset, length) in doubles inside a member's block, plus "state" -> offset of the iteration state and
+        "total" -> the member stride"""
+        off = (C.c_ulonglong * len(self.KD_LAYOUT))(); so = C.c_ulonglong(); st = C.c_ulonglong()
+        fn = self.L.lib.landing_debug_kd_layout
+        fn.argtypes = [C.c_int, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
+        self.L._check(fn(N, off, C.byref(so), C.byref(st)), "landing_debug_kd_layout")
+        nx, ng = 48 * N + 12, 48 + 141 * (N - 1) + 117
+        size = dict(x=nx, dx=nx, gc=N * self.KD_GC)
+        out = {n: (int(o), size.get(n, ng)) for n, o in zip(self.KD_LAYOUT, off)}
+        out["state"] = int(so.value); out["total"] = int(st.value)
+        return out
+
+    def kinodyn_debug_workspace(self, B):
+        """landing_debug_kd_workspace: the blocks of the first B members of the last refinement solve as a host array [B, stride] (the caller has
+        synchronised with that solve -- the host entry point has).  Slice a row with kinodyn_workspace_layout()."""
+        ptr = C.c_void_p(); st = C.c_ulonglong(); n = C.c_int(); nb = C.c_int()
+        fn = self.L.lib.landing_debug_kd_workspace
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_ulonglong), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        self.L._check(fn(self.L.ctx, C.byref(ptr), C.byref(st), C.byref(n), C.byref(nb)), "landing_debug_kd_workspace")
+        if B > nb.value:
+            raise ValueError("the last refinement solve had %d member blocks" % nb.value)
+        out = np.empty((B, st.value))
+        if hasattr(self.L.lib, "landing_emu_set_fused"):      # host emulation: the workspace is host memory
+            C.memmove(out.ctypes.data, ptr.value, out.nbytes)
+        else:
+            from .capi import _hip_runtime
+            hip = _hip_runtime()
+            hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+            rc = hip.hipMemcpy(out.ctypes.data, ptr.value, out.nbytes, 2)      # hipMemcpyDeviceToHost
+            if rc != 0:
+                raise RuntimeError("hipMemcpy of the refinement solver's workspace failed (%d)" % rc)
+        return out, n.value
+
+    def kinodyn_debug_state(self, member):
+        """landing_debug_kd_state: the member's iteration scalars after the last refinement solve, dict by KD_STATE"""
+        out = (C.c_double * len(self.KD_STATE))()
+        fn = self.L.lib.landing_debug_kd_state
+        fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
+        self.L._check(fn(self.L.ctx, member, out), "landing_debug_kd_state")
+        return dict(zip(self.KD_STATE, out))
+
     def leg_ik(self, npts, d_q6, d_c, d_jpos, d_res=0, iters=12, jmin=None, jmax=None, stream=0):
         jmin = np.ascontiguousarray(JPOS_MIN[:3] if jmin is None else jmin, float); jmax = np.ascontiguousarray(JPOS_MAX[:3] if jmax is None else jmax, float)
         dp = C.POINTER(C.c_double)

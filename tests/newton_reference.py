@@ -61,18 +61,12 @@ def effective_opts(opts, run_cost):
     return mu, push, opts.bound_frac
 
 
-def initial_state(O, p, x0, opts):
-    """cold start of the solver (ipm_init_row restated): x0 with the initial state taken from p, slacks pushed into the interior by
-    bound_push / bound_frac, multipliers of finite bounds 1, y = zU - zL, equality multipliers 0.  Returns dict(x, s, zL, zU, y, mu)."""
-    po = O.param_offsets()
-    x = np.array(x0, float)
-    x[0:6] = p[po["q_init"]:po["q_init"] + 6]; x[6:12] = p[po["qd_init"]:po["qd_init"] + 6]
-    mu, push, frac = effective_opts(opts, O.form.run_cost != 0)
-    lb, ub = O.bounds(p)
-    g = O.g(x, p)
-    ng = O.ng
+def push_slacks(g, lb, ub, push, frac, first_row):
+    """slack initialisation of both solvers (ipm_core.hpp ipm_init_row restated) over the rows >= first_row: slacks of the inequality rows pushed
+    into the interior by bound_push / bound_frac, multipliers of finite bounds 1.  Returns (s, zL, zU), zero on every other row."""
+    ng = len(g)
     s = np.zeros(ng); zL = np.zeros(ng); zU = np.zeros(ng)
-    for r in range(12, ng):
+    for r in range(first_row, ng):
         if lb[r] == ub[r]:
             continue
         hL, hU = lb[r] > -np.inf, ub[r] < np.inf
@@ -86,6 +80,18 @@ def initial_state(O, p, x0, opts):
         if hU:
             v = min(v, ub[r] - pu)
         s[r] = v; zL[r] = 1.0 if hL else 0.0; zU[r] = 1.0 if hU else 0.0
+    return s, zL, zU
+
+
+def initial_state(O, p, x0, opts):
+    """cold start of the solver (ipm_init_row restated): x0 with the initial state taken from p, slacks pushed into the interior by
+    bound_push / bound_frac, multipliers of finite bounds 1, y = zU - zL, equality multipliers 0.  Returns dict(x, s, zL, zU, y, mu)."""
+    po = O.param_offsets()
+    x = np.array(x0, float)
+    x[0:6] = p[po["q_init"]:po["q_init"] + 6]; x[6:12] = p[po["qd_init"]:po["qd_init"] + 6]
+    mu, push, frac = effective_opts(opts, O.form.run_cost != 0)
+    lb, ub = O.bounds(p)
+    s, zL, zU = push_slacks(O.g(x, p), lb, ub, push, frac, 12)
     return dict(x=x, s=s, zL=zL, zU=zU, y=zU - zL, mu=mu)
 
 
@@ -102,6 +108,17 @@ def _res_ld(coo, z, b):
 
 def _scale(v):
     return max(1.0, float(np.max(np.abs(v)))) if len(v) else 1.0
+
+
+def sigma_bar(s, zL, zU, lb, ub, mu, ineq):
+    """sigma = zL / (s - lb) + zU / (ub - s) and bar = mu / (ub - s) - mu / (s - lb) of the inequality rows (finite sides only), zero elsewhere"""
+    ng = len(s)
+    sig = np.zeros(ng); bar = np.zeros(ng)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        hL = ineq & (lb > -np.inf); hU = ineq & (ub < np.inf)
+        sig[hL] += zL[hL] / (s[hL] - lb[hL]); bar[hL] -= mu / (s[hL] - lb[hL])
+        sig[hU] += zU[hU] / (ub[hU] - s[hU]); bar[hU] += mu / (ub[hU] - s[hU])
+    return sig, bar
 
 
 def assemble(O, p, st, mu, dreg):
@@ -121,11 +138,7 @@ def assemble(O, p, st, mu, dreg):
     H = (Hu + sp.triu(Hu, 1).T).tocsr()[12:, :][:, 12:]      # the oracle's Hessian is one triangle
     gf = O.grad_f(x, p)[1][12:]
     s, zL, zU = (np.asarray(st[k], float) for k in ("s", "zL", "zU"))
-    sig = np.zeros(ng); bar = np.zeros(ng)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        hL = ineq & (lb > -np.inf); hU = ineq & (ub < np.inf)
-        sig[hL] += zL[hL] / (s[hL] - lb[hL]); bar[hL] -= mu / (s[hL] - lb[hL])
-        sig[hU] += zU[hU] / (ub[hU] - s[hU]); bar[hU] += mu / (ub[hU] - s[hU])
+    sig, bar = sigma_bar(s, zL, zU, lb, ub, mu, ineq)
     res = np.where(ineq, g - s, g - lb)      # g - s / g - b
     return dict(J=J, H=H, gf=gf, sig=sig[12:], bar=bar[12:], res=res[12:], ineq=ineq[12:], eq=eq[12:], D=np.asarray(dreg, float)[12:], n=nx - 12, m=ng - 12)
 
@@ -158,12 +171,10 @@ def _quantities(a, dx, y_new):
     return np.asarray(dx, float), ds.astype(float), np.asarray(y_new, float)[a["eq"]]
 
 
-def solve_step(O, p, st, mu, dreg, refine=3):
-    """Refined Newton step at st.  Returns dict:
-      dx [nx] (dx[0:12] = 0), ds [ng] (inequality rows, 0 elsewhere), y_new [ng] (all rows >= 12), ineq / eq (row masks over ng),
-      e_aug / e_cond: dict(dx, ds, y) of the two yardsticks, res: relative residual of the refined solution,
-      and what backward_error() needs (K, b, a)."""
-    a = assemble(O, p, st, mu, dreg)
+def solve_assembled(a, refine=3):
+    """The refined step of an assembled system a = dict(J, H, gf, sig, bar, res, ineq, eq, D, n, m) over its free variables and rows (whichever NLP
+    it came from).  Returns dict: q = (dx [n], ds of the inequality rows, y_new of the equality rows), z (dx | y_new of all rows), e_aug / e_cond:
+    dict(dx, ds, y) of the two yardsticks, res: relative residual of the refined solution, and K, b, a."""
     n, m = a["n"], a["m"]
     K, b = augmented(a)
     lu = spla.splu(K)
@@ -187,13 +198,31 @@ def solve_step(O, p, st, mu, dreg, refine=3):
     names = ("dx", "ds", "y")
     e_aug = {k: float(np.max(np.abs(u - v))) / _scale(v) if len(v) else 0.0 for k, u, v in zip(names, q0, ref)}
     e_cond = {k: float(np.max(np.abs(u - v))) / _scale(v) if len(v) else 0.0 for k, u, v in zip(names, qc, ref)}
+    return dict(q=ref, z=z, e_aug=e_aug, e_cond=e_cond, res=rel, K=K, b=b, a=a)
+
+
+def scatter(sol, nx, ng, free, rows):
+    """a solve_assembled() result over the NLP's own index spaces: free / rows = indices in x / g of the system's variables / rows.  Adds
+    dx [nx] (0 on the other variables), ds [ng] (inequality rows, 0 elsewhere), y_new [ng] (all rows of the system), ineq / eq (masks over ng)."""
+    a = sol["a"]; n = a["n"]
+    free = np.asarray(free); rows = np.asarray(rows)
+    dx = np.zeros(nx); dx[free] = sol["q"][0]
+    ineq = np.zeros(ng, bool); ineq[rows] = a["ineq"]
+    eq = np.zeros(ng, bool); eq[rows] = a["eq"]
+    ds = np.zeros(ng); ds[ineq] = sol["q"][1]
+    y_new = np.zeros(ng); y_new[rows] = sol["z"][n:]
+    out = dict(sol); del out["q"], out["z"]
+    out.update(dx=dx, ds=ds, y_new=y_new, ineq=ineq, eq=eq, free=free, rows=rows)
+    return out
+
+
+def solve_step(O, p, st, mu, dreg, refine=3):
+    """Refined Newton step at st.  Returns dict:
+      dx [nx] (dx[0:12] = 0), ds [ng] (inequality rows, 0 elsewhere), y_new [ng] (all rows >= 12), ineq / eq (row masks over ng),
+      e_aug / e_cond: dict(dx, ds, y) of the two yardsticks, res: relative residual of the refined solution,
+      and what backward_error() needs (K, b, a, free, rows)."""
     nx, ng = O.nx, O.ng
-    dx = np.zeros(nx); dx[12:] = ref[0]
-    ineq = np.zeros(ng, bool); ineq[12:] = a["ineq"]
-    eq = np.zeros(ng, bool); eq[12:] = a["eq"]
-    ds = np.zeros(ng); ds[ineq] = ref[1]
-    y_new = np.zeros(ng); y_new[12:] = z[n:]
-    return dict(dx=dx, ds=ds, y_new=y_new, ineq=ineq, eq=eq, e_aug=e_aug, e_cond=e_cond, res=rel, K=K, b=b, a=a)
+    return scatter(solve_assembled(assemble(O, p, st, mu, dreg), refine), nx, ng, np.arange(12, nx), np.arange(12, ng))
 
 
 def errors(ref, dx, ds, yn):
@@ -218,10 +247,10 @@ def backward_error(ref, dx, ds, yn):
     """normwise backward error of the kernel's step in the augmented system (inequality multipliers from its ds: y = sigma ds + bar), with the
     extended-precision residual: |b - K z|_inf / (|K|_inf |z|_inf + |b|_inf).  Reported, never asserted."""
     a = ref["a"]
-    y = np.array(yn[12:], float)
+    y = np.array(np.asarray(yn)[ref["rows"]], float)
     I = a["ineq"]
-    y[I] = a["sig"][I] * ds[12:][I] + a["bar"][I]
-    z = np.concatenate([dx[12:], y])
+    y[I] = a["sig"][I] * np.asarray(ds)[ref["rows"]][I] + a["bar"][I]
+    z = np.concatenate([np.asarray(dx)[ref["free"]], y])
     K, b = ref["K"], ref["b"]
     r = _res_ld(K.tocoo(), z, b)
     return float(np.max(np.abs(r))) / (float(abs(K).sum(axis=1).max()) * float(np.max(np.abs(z))) + float(np.max(np.abs(b))))
