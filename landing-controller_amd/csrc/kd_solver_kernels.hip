@@ -388,7 +388,7 @@ KD_PHASE bool kd_riccati_stage(const KdMem& M, int N, int k) {
   const int nv = last ? 48 : KD_NV, nu = nv - KD_NSIG;
   // Gauss-Jordan on the control rows / columns 24 .. nv-1 of [M | m] on the fp64 matrix cores (round 5): the 64 x 64 array lives in
   // v_mfma_f64_16x16x4 accumulator tiles (wave w owns column tile w, four row tiles), pivot blocks of 4 x 4 -- kd_pivot_block_step, the
-  // scheme of the SRBM solver's block_eliminate (solver_kernels.hip): 9 exchange + barrier rounds per stage instead of 36.  (Round 4: scalar
+  // scheme of the SRBM solver's stage_eliminate (solver_kernels.hip): 9 exchange + barrier rounds per stage instead of 36.  (Round 4: scalar
   // pivots with the array in registers, one barrier per pivot: 1.1 ms per factorisation.)
   bool ok = true;
   {
@@ -399,7 +399,7 @@ KD_PHASE bool kd_riccati_stage(const KdMem& M, int N, int k) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) { const int row = 16 * rt + lk + 4 * r; T[rt][r] = (row < KD_NV && c < KD_MS) ? S.Ms[row * KD_MS + c] : 0.0; }
     {   // + the cost-to-go of the next stage, sigma+ = (X+, c+) with X+ = A^ (sigma, f) + b:  E' P E and E' (P e + p), formed on the matrix cores where it is consumed (round 6,
-        // the scheme of the SRBM solver's block_eliminate).  The own column of Y = P(:, X) [A^ | b] comes out of the matrix cores in accumulator layout, which IS the
+        // the scheme of the SRBM solver's stage_eliminate).  The own column of Y = P(:, X) [A^ | b] comes out of the matrix cores in accumulator layout, which IS the
         // B-operand layout of the next product; columns of c+ and the p-part of the right-hand side enter P directly.  Rounds 4-5 formed Y and A^' Y in scalar loops through
         // LDS with two barriers: 88 of the 349 us of a backward sweep per member-iteration under load (development timer).
       const bool isg = c == KD_NV, sf = c < 36, cpl = c >= 48 && c < KD_NV;

@@ -22,7 +22,7 @@ struct Layout {
 
   __host__ __device__ int x_X(int k) const { return 12 * k; }
   __host__ __device__ int x_U(int k) const { return 12 * (N + 1) + 24 * k; }
-  __host__ __device__ int g_stage(int k) const { return 36 + 104 * k; }
+  __host__ __device__ static constexpr int g_stage(int k) { return 36 + 104 * k; }      // (no member enters: callable without a Layout)
   __host__ __device__ int rows(int k) const { return k == N - 1 ? 80 : 104; }
   // Jacobian CCS: [X_0..X_{N-1} (157 each) | X_N (36) | U_0 (204) | U_1..U_{N-2} (228 each) | U_{N-1} (180)]
   __host__ __device__ int jx(int k) const { return 157 * k; }

@@ -254,7 +254,7 @@ __device__ __forceinline__ double lane_bcast(double v, int src) {
 // Elimination of the controls of one stage by ONE wavefront, entirely in registers: Gauss-Jordan on
 // [G_uu | G_us | gamma_u], lane c owning column c (NU + 24 + 1 <= 49 lanes, NU values each).  The pivot of step j is
 // broadcast from lane j, the multipliers from lane j's column; no LDS traffic and no barrier inside the steps.
-// Used for the 12 x 12 block of the free feet of stage 0 only (the stages themselves go through block_eliminate).  On success Kl (LDS, NU x 24, row stride 24) holds
+// Used for the 12 x 12 block of the free feet of stage 0 only (the stages themselves go through stage_eliminate).  On success Kl (LDS, NU x 24, row stride 24) holds
 // K = G_uu^-1 G_us and kl the vector kappa = G_uu^-1 gamma_u.  A non-positive / non-finite pivot (wrong inertia)
 // is reported through *flag = 0; the caller raises delta_w.
 template <int NU>
@@ -328,22 +328,49 @@ __device__ __noinline__ void gauss_jordan_wave(const double* G, const double* ga
 constexpr int ASM_SEG_LEN[7] = {NZ_JU - NZ_JX, NZ_JUN - NZ_JU, NZ_HX - NZ_JUN, NZ_HU - NZ_HX, NZ_HUN - NZ_HU, NZ_TOT - NZ_HUN, RUNC};
 constexpr int ASM_SEG_POS[7] = {NZ_JX, NZ_JU, NZ_JUN, NZ_HX, NZ_HU, NZ_HUN, NZ_TOT};
 static_assert(NZ_JUN - NZ_JU <= SOLVER_THREADS && 2 * 104 <= SOLVER_THREADS, "one load per thread and segment");
-struct AsmRegs { double jh[7], sr, g, rc; };
-// (1) coalesced loads of stage k's nonzeros (one per segment), sigma / rho of its rows, the residual of its dynamics rows; nothing is consumed here
-__device__ __forceinline__ void asm_issue(int k, AsmRegs& R) {
+// What a sweep reads that is the same for every lane and every stage, fetched from the member context in LDS ONCE per sweep and kept in scalar
+// registers from there on (until round 9 the assembly hooks read ctab, c_ml, c_mid, rc_on and the member's pointers back from LDS in every stage)
+__device__ __forceinline__ int uni(int v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_readfirstlane(v);
+#else
+  return v;
+#endif
+}
+template <class P>
+__device__ __forceinline__ P uni_ptr(P q) {
+  const unsigned long long a = (unsigned long long)q;
+  return (P)((unsigned long long)(unsigned)uni((int)(unsigned)a) | ((unsigned long long)(unsigned)uni((int)(unsigned)(a >> 32)) << 32));
+}
+__device__ __forceinline__ double uni(double v) { return __hiloint2double(uni(__double2hiint(v)), uni(__double2loint(v))); }
+struct SweepCtx {
+  landing_gptr JH, SR, Gr, Cd;      // [J | H | Hc] (contiguous), [sigma | rho] (contiguous), g, gradient of the running cost
+  const unsigned long long* ctab; const unsigned long long* ccomb;
+  int c_ml, c_mid, rc_on, ng;
+};
+__device__ __forceinline__ SweepCtx sweep_ctx() {
   const Lds& S = SH;
-  const MemberMem& M = S.M;
-  const int tid = threadIdx.x, ng = S.L.ng;
-  landing_gptr JH = (landing_gptr)M.J;       // [J | H | Hc] are contiguous
-  landing_gptr SR = (landing_gptr)M.sig;     // [sigma | rho] are contiguous
+  SweepCtx X;
+  X.JH = uni_ptr((landing_gptr)S.M.J); X.SR = uni_ptr((landing_gptr)S.M.sig); X.Gr = uni_ptr((landing_gptr)S.M.g); X.Cd = uni_ptr((landing_gptr)S.M.cond);
+  X.ctab = uni_ptr(S.ctab); X.ccomb = uni_ptr(S.ccomb);
+  X.c_ml = uni(S.c_ml); X.c_mid = uni(S.c_mid); X.rc_on = uni(S.rc_on); X.ng = uni(S.L.ng);
+  return X;
+}
+struct AsmRegs { double jh[7], sr, g, rc; int tp; };      // (tp: the stage's type, uniform)
+// (1) coalesced loads of stage k's nonzeros (one per segment), sigma / rho of its rows, the residual of its dynamics rows; nothing is consumed here
+// (the segment bases and the type of the stage are the one thing the hooks still read from LDS per stage: segb, one round trip)
+__device__ __forceinline__ void asm_issue(int k, const SweepCtx& X, AsmRegs& R) {
+  const Lds& S = SH;
+  const int tid = threadIdx.x, ng = X.ng;
   const int* sb = S.segb + k * 8;
-  const int g0 = S.L.g_stage(k);
+  const int g0 = Layout::g_stage(k);
 #pragma unroll
-  for (int sgm = 0; sgm < 7; ++sgm) R.jh[sgm] = JH[sb[sgm] + (tid < ASM_SEG_LEN[sgm] ? tid : 0)];
-  R.sr = SR[tid < 104 ? g0 + tid : (tid < 208 ? ng + g0 + tid - 104 : 0)];      // (the last stage has 80 rows: the tail reads the workspace behind them, never used)
-  R.g = ((landing_gptr)M.g)[g0 + (tid < 12 ? tid : 0)];
+  for (int sgm = 0; sgm < 7; ++sgm) R.jh[sgm] = X.JH[uni(sb[sgm]) + (tid < ASM_SEG_LEN[sgm] ? tid : 0)];
+  R.tp = uni(sb[7]);
+  R.sr = X.SR[tid < 104 ? g0 + tid : (tid < 208 ? ng + g0 + tid - 104 : 0)];      // (the last stage has 80 rows: the tail reads the workspace behind them, never used)
+  R.g = X.Gr[g0 + (tid < 12 ? tid : 0)];
   R.rc = 0.0;
-  if (S.rc_on) R.rc = ((landing_gptr)M.cond)[(size_t)k * RCG + (tid < RCG ? tid : 0)];
+  if (X.rc_on) R.rc = X.Cd[(size_t)k * RCG + (tid < RCG ? tid : 0)];
 }
 // (2) ... into LDS; a barrier follows before asm_terms
 __device__ __forceinline__ void asm_copy(const AsmRegs& R) {
@@ -355,13 +382,13 @@ __device__ __forceinline__ void asm_copy(const AsmRegs& R) {
 }
 // (3) products and stores: G and gamma (dead since the tile fetch of the running elimination), A^ / b of copy `nb`.  ATAB_TB terms
 // at a time: codes, then all operands, then the arithmetic and the stores -- three LDS round trips per batch instead of three per term
-__device__ __forceinline__ void asm_terms(int k, int nb, const AsmRegs& R) {
+__device__ __forceinline__ void asm_terms(const SweepCtx& X, int nb, const AsmRegs& R) {
   Lds& S = SH;
-  const int tid = threadIdx.x, LT = S.c_ml, tp = S.segb[k * 8 + 7];
+  const int tid = threadIdx.x, LT = X.c_ml, tp = R.tp;
   char* const lds0 = reinterpret_cast<char*>(&S);
   const unsigned ahoff = nb ? (unsigned)(12 * YS * sizeof(double)) : 0u;
-  const bool mid = (tp == S.c_mid);
-  const unsigned long long* gt = S.ctab + (size_t)tp * LT * SOLVER_THREADS;
+  const bool mid = (tp == X.c_mid);
+  const unsigned long long* gt = X.ctab + (size_t)tp * LT * SOLVER_THREADS;
   double acc = 0.0;
   for (int j0 = 0; j0 < LT; j0 += ATAB_TB) {
     unsigned long long t[ATAB_TB];
@@ -390,10 +417,10 @@ __device__ __forceinline__ void asm_terms(int k, int nb, const AsmRegs& R) {
   if (tid < RCG) S.rcl[tid] = R.rc;      // gradient of the running cost (w order X, c, f): added to gamma when its tile is fetched
 }
 // (4) behind the next barrier: the destinations whose terms more than one thread summed
-__device__ __forceinline__ void asm_combine(int k, int nb) {
+__device__ __forceinline__ void asm_combine(const SweepCtx& X, int nb, const AsmRegs& R) {
   Lds& S = SH;
-  const int tid = threadIdx.x, tp = S.segb[k * 8 + 7];
-  const unsigned long long code = tp == S.c_mid ? S.acomb_mid[tid] : S.ccomb[tp * SOLVER_THREADS + tid];
+  const int tid = threadIdx.x, tp = R.tp;
+  const unsigned long long code = tp == X.c_mid ? S.acomb_mid[tid] : X.ccomb[tp * SOLVER_THREADS + tid];
   const unsigned lo = (unsigned)code, dd = (unsigned)(code >> 32);
   const int n = (int)(lo & 7u);
   if (n > 0) {
@@ -412,15 +439,7 @@ typedef double* landing_gptr_w;
 #endif
 // A stage record's base as a global pointer in scalar registers (a __noinline__ phase receives its arguments in vector registers; the
 // pointer is the same in every lane): stores through it are global_store with a scalar base and a 32-bit lane offset
-__device__ __forceinline__ landing_gptr_w uniform_record(double* rec) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const unsigned long long a = (unsigned long long)rec;
-  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(a >> 32));
-  return (landing_gptr_w)((unsigned long long)lo | ((unsigned long long)hi << 32));
-#else
-  return rec;
-#endif
-}
+__device__ __forceinline__ landing_gptr_w uniform_record(double* rec) { return uni_ptr((landing_gptr_w)rec); }
 
 // Elimination of the controls of one stage on the matrix cores (waves 0..2): blocked Gauss-Jordan with
 // 4 x 4 pivot blocks on the (NU + 24) x (NU + 25) array  [G_uu G_us gamma_u ; G_su G_ss gamma_s]  (rows/columns: controls
@@ -440,24 +459,91 @@ __device__ __forceinline__ landing_gptr_w uniform_record(double* rec) {
 // SLOWER: the redundant per-lane factorisation grows with the cube of the block size -- about 210 fp64 operations per lane and block at
 // 4 issue cycles each against 2 x 40 -- which costs more than the three barrier rounds it saves: backward sweep 0.353 instead of
 // 0.293 ms per iteration with the CU to itself.
-template <int STEP>
-__device__ __forceinline__ bool pivot_block_step(f64x4 (&T)[3], int ct, int lj, int lk, int c) {
-  constexpr int OFF = 4 * STEP;
+constexpr int G_GAMMA = GS - 1, P_PV = PS - 1, AH_B = YS - 1;
+static_assert(G_GAMMA == 48 && P_PV == 24 && AH_B == 36, "spare columns of G / P / A^ hold gamma / p / b");
+
+// What a lane needs to know about itself in a stage elimination: columns, LDS bases (BYTE offsets inside the LDS block) and masks.  All of it
+// follows from the thread index and NU alone -- not from the member, the iteration or the stage -- so the sweep forms it once (stage_lanes)
+// and every stage of its loop uses it as it stands; until round 9 each of the 40 stages of a sweep worked it out again.  The places inside A^
+// are those of copy 0: a stage adds the distance to its own copy (one scalar, k & 1).
+template <int NU>
+struct StageLanes {
+  int ct, lj, lk, c;                   // column tile (= wave, uniform), column inside the tile, lane group, column
+  bool isg, live, ym, pm, wr;          // the gamma lane; live column; lanes with an operand in A^ | b / in P | p; lanes that write the stage out
+  bool am[3];                          // rows (one per row tile) that have a column of A^
+  int gb, cd384, cm;                   // tile fetch: base of the own column of [G | gamma]; 48 * 8 * (position of the column - lk); c - lk
+  int yb, pa1, pb, p2, fb, ab[3];      // operands of T^T P T and of the closed-loop map
+  int xw, xw0, xcp, xcr;               // exchange buffers of the block steps: own pivot-row entry, own pivot rows, published pivot column, pivot-column operand
+  unsigned iK, iM, iP, rs;             // write-out: byte offsets of the lane's first entry of K | kappa, Mt | mv, P_x | p in the record, byte stride of a row
+  int sw, pw;                          //            own column of A^ | b and of P | p
+};
+template <int NU>
+__device__ __forceinline__ StageLanes<NU> stage_lanes() {
+  constexpr int NR = NU + 24, D = (int)sizeof(double);
+  constexpr int oG = (int)offsetof(Lds, G), oP = (int)offsetof(Lds, P), oAh = (int)offsetof(Lds, Ah), oA1 = (int)offsetof(Lds, A1);
+  StageLanes<NU> Z;
+  const int tid = threadIdx.x, l = tid & 63;
+  Z.ct = uni(tid >> 6); Z.lj = l & 15; Z.lk = l >> 4;
+  const int ct = Z.ct, lj = Z.lj, lk = Z.lk, c = 16 * ct + lj;
+  Z.c = c;
+  Z.isg = (c == NR); Z.live = (c <= NR);
+  const bool isg = Z.isg, live = Z.live;
+  // position of the own column in G; its column of A^ | b (state and force columns, b for gamma); its column of P | p (columns of c+, p for gamma)
+  const int cl = c < NR ? c : NR;
+  const int cp = NU == 24 ? cl : (cl < NU ? cl : cl + (24 - NU));
+  Z.ym = live && (c < 12 || c >= NU);
+  int ycol = c < NU ? c + 24 : c - NU;
+  ycol = Z.ym ? (isg ? AH_B : ycol) : 0;
+  Z.pm = live && c >= 12 && (c < NU || isg);
+  const int pcol = Z.pm ? (isg ? P_PV : c) : 0;
+  Z.gb = oG + (cp + lk * GS) * D; Z.cd384 = (cp - lk) * ((GS - 1) * D); Z.cm = c - lk;
+  Z.yb = oAh + (lk * YS + ycol) * D;
+  Z.pa1 = oP + (lj * PS + lk) * D;
+  Z.pb = oP + (lk * PS + pcol) * D;
+#pragma unroll
+  for (int rt = 0; rt < 3; ++rt) {
+    const int rho = 16 * rt + lj;
+    const int a = rho < NU ? 24 + rho : (rho < NR ? rho - NU : 36);      // column of A^ that belongs to row rho (none for the rows of c+ and the dead rows)
+    Z.am[rt] = a < 36;
+    Z.ab[rt] = oAh + (lk * YS + (Z.am[rt] ? a : 0)) * D;
+  }
+  // (A-operand rows 12..15 feed rows 12..15 of the products, which nothing reads: those lanes re-read row 11 instead of a zero)
+  Z.p2 = oP + ((12 + (lj < 12 ? lj : 11)) * PS + lk) * D;
+  Z.fb = oAh + ((lj < 12 ? lj : 11) * YS + 24 + lk) * D;
+  Z.xw = oA1 + (c * 4 + lk) * D; Z.xw0 = oA1 + (c * 4) * D; Z.xcp = oA1 + (64 * 4 + lk * 4 + lj) * D; Z.xcr = oA1 + (64 * 4 + lj * 4 + lk) * D;
+  // Which field a row goes to is known per accumulator; a lane differs only in "state column or gamma", which is a base and a row stride of its
+  // own (K + sj, stride 24, against kappa, stride 1; alike Mt / mv and P_x / p).  Wave 0 (columns < NU) writes nothing.
+  Z.wr = c >= NU && c <= NR;
+  const unsigned sj = (unsigned)(c - NU), ulk = (unsigned)lk, rs = isg ? 1u : 24u;
+  Z.rs = rs * D;
+  Z.iK = ((isg ? (unsigned)RIC_KAP : (unsigned)RIC_K + sj) + ulk * rs) * D; Z.iM = ((isg ? (unsigned)RIC_MV : (unsigned)RIC_MT + sj) + ulk * rs) * D;
+  Z.iP = ((isg ? (unsigned)RIC_PV : (unsigned)RIC_PX + sj) + ulk * rs) * D;
+  const int scol = isg ? AH_B : (int)sj, pcw = isg ? P_PV : (int)sj;
+  Z.sw = oAh + (lk * YS + scol) * D; Z.pw = oP + (lk * PS + pcw) * D;
+  return Z;
+}
+__device__ __forceinline__ double lds_get(int boff) { return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(&SH) + boff); }
+__device__ __forceinline__ void lds_put(int boff, double v) { *reinterpret_cast<double*>(reinterpret_cast<char*>(&SH) + boff) = v; }
+
+// Returns the inertia key of the block: the largest of the four biased high words of a00, det A, s00, det S -- the block is accepted when it is
+// below PIVOT_KEY_MAX, and a stage when the largest key of its blocks is (one compare per stage; identical in every lane of the workgroup).
+constexpr unsigned PIVOT_KEY_MAX = 0x7e37e43cu - 0x00100000u;
+template <int STEP, int NU>
+__device__ __forceinline__ unsigned pivot_block_step(f64x4 (&T)[3], const StageLanes<NU>& Z) {
+  constexpr int OFF = 4 * STEP, D = (int)sizeof(double);
   static_assert((OFF >> 4) == ((OFF + 3) >> 4), "a pivot block lies inside one row tile");
-  Lds& S = SH;
   constexpr int RTB = OFF >> 4, R0 = (OFF & 15) >> 2;
   constexpr int WSZ = 64 * 4;
   static_assert(WSZ + 48 * 4 <= XCH, "exchange buffer");
-  double* W = S.A1 + (STEP & 1) * XCH;
-  double* C = W + WSZ;
-  // (a one-trip loop: written as a plain store, the same store compiles into another instruction schedule of block_eliminate)
-#pragma unroll
-  for (int q = 0; q < 1; ++q) W[c * 4 + 4 * q + lk] = T[RTB][R0 + q];
-  if (ct == RTB && lj >= (OFF & 15) && lj < (OFF & 15) + 4) {
+  constexpr int XB = (STEP & 1) * XCH * D;                               // buffer STEP & 1 of S.A1: W at its head, C behind WSZ doubles
+  constexpr int CB = (int)offsetof(Lds, A1) + XB + WSZ * D;
+  const bool inblk = (unsigned)(Z.lj - (OFF & 15)) < 4u;                 // lane column inside the pivot block's columns (of its tile)
+  lds_put(Z.xw + XB, T[RTB][R0]);
+  if (Z.ct == RTB && inblk) {
 #pragma unroll
     for (int rt = 0; rt < 3; ++rt)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) C[(16 * rt + lk + 4 * r) * 4 + (lj - (OFF & 15))] = T[rt][r];
+      for (int r = 0; r < 4; ++r) lds_put(Z.xcp + XB + ((16 * rt + 4 * r) * 4 - (OFF & 15)) * D, T[rt][r]);
   }
   __syncthreads();
   // pivot block (uniform reads), pivot rows of the own column, pivot-column operands
@@ -465,13 +551,13 @@ __device__ __forceinline__ bool pivot_block_step(f64x4 (&T)[3], int ct, int lj, 
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int j = 0; j <= i; ++j) a[i][j] = C[(OFF + i) * 4 + j];
+    for (int j = 0; j <= i; ++j) a[i][j] = lds_get(CB + ((OFF + i) * 4 + j) * D);
   double w[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) w[i] = W[c * 4 + i];
+  for (int i = 0; i < 4; ++i) w[i] = lds_get(Z.xw0 + XB + i * D);
   double am[3];
 #pragma unroll
-  for (int rt = 0; rt < 3; ++rt) { const int row = 16 * rt + lj; const double cv = C[row * 4 + lk]; am[rt] = (row >= OFF && row < OFF + 4) ? 0.0 : cv; }   // pivot rows: no update
+  for (int rt = 0; rt < 3; ++rt) { const double cv = lds_get(Z.xcr + XB + 16 * rt * 4 * D); am[rt] = (rt == RTB && inblk) ? 0.0 : cv; }   // pivot rows: no update
   auto recip = [](double d) { double i = __builtin_amdgcn_rcp(d); i = fma(i, fma(-d, i, 1.0), i); return fma(i, fma(-d, i, 1.0), i); };
   // The 4 x 4 pivot block through its 2 x 2 partition  D = [A B^T; B C]:  A^-1 from its determinant, E = B A^-1, Schur complement S = C - E B^T, S^-1 from its
   // determinant, then  r_2 = S^-1 (w_2 - E w_1),  r_1 = A^-1 w_1 - E^T r_2.  Two reciprocals on the serial chain instead of four and ~24 dependent operations
@@ -487,8 +573,8 @@ __device__ __forceinline__ bool pivot_block_step(f64x4 (&T)[3], int ct, int lj, 
   { const double piv[4] = {a00, detA, s00, detS};
 #pragma unroll
     for (int j = 0; j < 4; ++j) { const unsigned h = (unsigned)__double2hiint(piv[j]) - 0x00100000u; hm = h > hm ? h : hm; } }
-  const bool ok = hm < (0x7e37e43cu - 0x00100000u);
   // normalised pivot row of the own column: D r = w, lane group lk keeps r[lk]
+  const int lk = Z.lk;
   auto solve = [&](const double (&wv)[4]) {
     const double t2 = fma(-e01, wv[1], fma(-e00, wv[0], wv[2])), t3 = fma(-e11, wv[1], fma(-e10, wv[0], wv[3]));
     const double r2 = fma(s11, t2, -s10 * t3) * iS, r3 = fma(s00, t3, -s10 * t2) * iS;
@@ -497,13 +583,13 @@ __device__ __forceinline__ bool pivot_block_step(f64x4 (&T)[3], int ct, int lj, 
     return lk == 0 ? r0 : (lk == 1 ? r1 : (lk == 2 ? r2 : r3));
   };
   const double R = solve(w);
-  if (16 * ct + 16 > OFF) {                              // tiles whose columns are all eliminated already stay as they are
+  if (16 * Z.ct + 16 > OFF) {                            // (uniform) tiles whose columns are all eliminated already stay as they are
 #pragma unroll
     for (int rt = 0; rt < 3; ++rt) T[rt] = __builtin_amdgcn_mfma_f64_16x16x4f64(am[rt], -R, T[rt], 0, 0, 0);
     T[RTB][R0] = R;                                      // the pivot rows become the normalised rows, exactly
   }
-  return ok;                                             // identical in every lane of the workgroup (tested after the update so
-}                                                        // that the operand fetches are not held behind it)
+  return hm;
+}
 
 // (`k` = stage, its copy of A^ | b is k & 1; the assembly of stage k - 1 rides along)
 //
@@ -514,34 +600,28 @@ __device__ __forceinline__ bool pivot_block_step(f64x4 (&T)[3], int ct, int lj, 
 //    stage (no c+) uses the same positions, its rows / columns skip the c+ range: the patterns of the stages still nest along the sweep.
 //  * P carries p in its spare column PS - 1 = 24, A^ carries b in its spare column YS - 1 = 36: the gamma lane reads its operands
 //    with the formula of the other lanes, at a column of its own.
-// Every fetch below is then ONE per-lane base, formed here once from (lj, lk, ct), plus a compile-time offset; a lane without an operand
+// Every fetch below is then ONE per-lane base, formed once per sweep from (lj, lk, ct) (stage_lanes), plus a compile-time offset; a lane without an operand
 // (dead column, structural zero) loads from a clamped column and drops the value under a lane mask.  Until round 8 every fetch chose
 // its index through nested conditions on the lane, which the compiler turned into about 30 instructions of exec-mask branches per load.
-constexpr int G_GAMMA = GS - 1, P_PV = PS - 1, AH_B = YS - 1;
-static_assert(G_GAMMA == 48 && P_PV == 24 && AH_B == 36, "spare columns of G / P / A^ hold gamma / p / b");
+// Store to a stage record through its base in scalar registers and a 32-bit BYTE offset of the lane (global_store, scalar base + lane offset)
+__device__ __forceinline__ void rec_put(landing_gptr_w rec, unsigned boff, double v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef char __attribute__((address_space(1)))* gchar_w;
+  *reinterpret_cast<landing_gptr_w>(reinterpret_cast<gchar_w>(rec) + boff) = v;
+#else
+  *reinterpret_cast<double*>(reinterpret_cast<char*>(rec) + boff) = v;
+#endif
+}
+// `rec`, `delta`, `k` and X are uniform (scalar registers); returns whether every pivot was positive, uniform as well.
 template <int NU>
-__device__ __noinline__ bool block_eliminate(double* __restrict__ rec_, double delta, int k) {
-  Lds& S = SH;
-  constexpr int NR = NU + 24;                         // rows; column NR is gamma
-  const int tid = threadIdx.x, ct = tid >> 6, l = tid & 63, lj = l & 15, lk = l >> 4;
-  const int c = 16 * ct + lj;
-  const bool isg = (c == NR), live = (c <= NR);
+__device__ __forceinline__ bool stage_eliminate(const StageLanes<NU>& Z, const SweepCtx& X, landing_gptr_w rec, double delta, int k) {
+  constexpr int NR = NU + 24, D = (int)sizeof(double);          // rows; column NR is gamma
+  const int lk = Z.lk;
+  const bool isg = Z.isg, live = Z.live, ym = Z.ym, pm = Z.pm;
   const int cb = k & 1;
+  const int ah = cb * (12 * YS * D);                             // distance to the stage's copy of A^ | b
   f64x4 T[3];
-  const double* const lds0 = reinterpret_cast<const double*>(&S);
-  constexpr int oG = (int)(offsetof(Lds, G) / sizeof(double)), oP = (int)(offsetof(Lds, P) / sizeof(double));
-  const int oAh = (int)(offsetof(Lds, Ah) / sizeof(double)) + cb * (12 * YS);
-  // per-lane columns and masks, once: position of the own column in G; its column of A^ | b (state and force columns, b for gamma); its
-  // column of P | p (columns of c+, p for gamma)
-  const int cl = c < NR ? c : NR;
-  const int cp = NU == 24 ? cl : (cl < NU ? cl : cl + (24 - NU));
-  const bool ym = live && (c < 12 || c >= NU);
-  int ycol = c < NU ? c + 24 : c - NU;
-  ycol = ym ? (isg ? AH_B : ycol) : 0;
-  const bool pm = live && c >= 12 && (c < NU || isg);
-  const int pcol = pm ? (isg ? P_PV : c) : 0;
   {   // tile fetch: every lane walks its own column of [G | gamma]; delta_w on the diagonal
-    const int gb = oG + cp + lk * GS, cd = cp - lk, cm = c - lk;
 #pragma unroll
     for (int rt = 0; rt < 3; ++rt)
 #pragma unroll
@@ -549,12 +629,13 @@ __device__ __noinline__ bool block_eliminate(double* __restrict__ rec_, double d
         const int rb = 16 * rt + 4 * r;                                  // (compile-time after unrolling) row rho = rb + lk
         if (rb < NR) {
           const int rp = NU == 24 ? rb : (rb < NU ? rb : rb + (24 - NU));      // its position in G, less lk
-          const int m = rp < cd ? rp : cd;
-          const double v = lds0[gb + rp + (GS - 1) * m] + (cm == rb ? delta : 0.0);
+          const int m384 = rp * ((GS - 1) * D) < Z.cd384 ? rp * ((GS - 1) * D) : Z.cd384;      // (GS - 1) * 8 * min(rp, position of the column - lk)
+          const double v = lds_get(Z.gb + rp * D + m384) + (Z.cm == rb ? delta : 0.0);
           T[rt][r] = live ? v : 0.0;
         } else T[rt][r] = 0.0;
       }
-    if (S.rc_on) {      // (uniform) + gradient of the running cost of the stage's variables (X, c, f) in the column of gamma
+    if (X.rc_on) {      // (uniform) + gradient of the running cost of the stage's variables (X, c, f) in the column of gamma
+      Lds& S = SH;
 #pragma unroll
       for (int rt = 0; rt < 3; ++rt)
 #pragma unroll
@@ -575,34 +656,28 @@ __device__ __noinline__ bool block_eliminate(double* __restrict__ rec_, double d
       // Y never touches LDS.  Columns of c+ and the p-part of gamma enter P T directly.
     double be[3];
     {
-      const int yb = oAh + lk * YS + ycol;
+      const int yb = Z.yb + ah;
 #pragma unroll
-      for (int kt = 0; kt < 3; ++kt) { const double v = lds0[yb + 4 * kt * YS]; be[kt] = ym ? v : 0.0; }
+      for (int kt = 0; kt < 3; ++kt) { const double v = lds_get(yb + 4 * kt * YS * D); be[kt] = ym ? v : 0.0; }
     }
     double pa1[3], add1[3];
 #pragma unroll
-    for (int kt = 0; kt < 3; ++kt) pa1[kt] = lds0[oP + lj * PS + 4 * kt + lk];
-    const int pb = oP + lk * PS + pcol;
+    for (int kt = 0; kt < 3; ++kt) pa1[kt] = lds_get(Z.pa1 + 4 * kt * D);
 #pragma unroll
-    for (int r = 0; r < 3; ++r) { const double v = lds0[pb + 4 * r * PS]; add1[r] = pm ? v : 0.0; }
+    for (int r = 0; r < 3; ++r) { const double v = lds_get(Z.pb + 4 * r * PS * D); add1[r] = pm ? v : 0.0; }
     double av[3][3];
 #pragma unroll
     for (int rt = 0; rt < 3; ++rt) {
-      const int rho = 16 * rt + lj;
-      const int a = rho < NU ? 24 + rho : (rho < NR ? rho - NU : 36);      // column of A^ that belongs to row rho (none for the rows of c+ and the dead rows)
-      const bool am = a < 36;
-      const int ab = oAh + lk * YS + (am ? a : 0);
+      const int ab = Z.ab[rt] + ah;
 #pragma unroll
-      for (int kt = 0; kt < 3; ++kt) { const double v = lds0[ab + 4 * kt * YS]; av[rt][kt] = am ? v : 0.0; }
+      for (int kt = 0; kt < 3; ++kt) { const double v = lds_get(ab + 4 * kt * YS * D); av[rt][kt] = Z.am[rt] ? v : 0.0; }
     }
     double pa2[3], add2[3];
     if (NU == 24) {
-      // (A-operand rows 12..15 feed rows 12..15 of Y2, which nothing reads: those lanes re-read row 11 instead of a zero)
-      const int p2 = oP + (12 + (lj < 12 ? lj : 11)) * PS + lk;
 #pragma unroll
-      for (int kt = 0; kt < 3; ++kt) pa2[kt] = lds0[p2 + 4 * kt];
+      for (int kt = 0; kt < 3; ++kt) pa2[kt] = lds_get(Z.p2 + 4 * kt * D);
 #pragma unroll
-      for (int r = 0; r < 3; ++r) { const double v = lds0[pb + (12 + 4 * r) * PS]; add2[r] = pm ? v : 0.0; }
+      for (int r = 0; r < 3; ++r) { const double v = lds_get(Z.pb + (12 + 4 * r) * PS * D); add2[r] = pm ? v : 0.0; }
     }
     f64x4 Y1 = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -630,67 +705,78 @@ __device__ __noinline__ bool block_eliminate(double* __restrict__ rec_, double d
   constexpr int SC = NU == 24 ? 3 : 1;
   AsmRegs nxt;
   const bool more = k > 0;                               // (uniform)
-#define ASM_HOOK(step) do { if constexpr (SC == (step)) { if (more) asm_copy(nxt); } if constexpr (SC + 1 == (step)) { if (more) asm_terms(k - 1, cb ^ 1, nxt); } if constexpr (SC + 2 == (step)) { if (more) asm_combine(k - 1, cb ^ 1); } } while (0)
-  bool ok = pivot_block_step<0>(T, ct, lj, lk, c);
-  if (more) asm_issue(k - 1, nxt);
+#define ASM_HOOK(step) do { if constexpr (SC == (step)) { if (more) asm_copy(nxt); } if constexpr (SC + 1 == (step)) { if (more) asm_terms(X, cb ^ 1, nxt); } if constexpr (SC + 2 == (step)) { if (more) asm_combine(X, cb ^ 1, nxt); } } while (0)
+  unsigned key = pivot_block_step<0>(T, Z), kq;
+#define KEY_MAX(e) do { kq = (e); key = kq > key ? kq : key; } while (0)
+  if (more) asm_issue(k - 1, X, nxt);
   ASM_HOOK(1);
-  ok &= pivot_block_step<1>(T, ct, lj, lk, c);
+  KEY_MAX(pivot_block_step<1>(T, Z));
   ASM_HOOK(2);
-  ok &= pivot_block_step<2>(T, ct, lj, lk, c);
+  KEY_MAX(pivot_block_step<2>(T, Z));
   ASM_HOOK(3);
   if constexpr (NU == 24) {
-    ok &= pivot_block_step<3>(T, ct, lj, lk, c);
+    KEY_MAX(pivot_block_step<3>(T, Z));
     ASM_HOOK(4);
-    ok &= pivot_block_step<4>(T, ct, lj, lk, c);
+    KEY_MAX(pivot_block_step<4>(T, Z));
     ASM_HOOK(5);
-    ok &= pivot_block_step<5>(T, ct, lj, lk, c);
+    KEY_MAX(pivot_block_step<5>(T, Z));
   }
+#undef KEY_MAX
 #undef ASM_HOOK
-  if (!ok) return false;                                 // (identical in every lane)
+  if (!((unsigned)uni((int)key) < PIVOT_KEY_MAX)) return false;      // (the key is identical in every lane: a scalar test)
   // closed-loop state map for the forward sweep: X+ = A^_sigma sigma + A^_f f + b with f = -(K_f sigma + kappa_f), i.e.
   // Mt = A^_sigma - A^_f K_f, mv = b - A^_f kappa_f.  K_f / kappa_f are rows 0..11 of the first row tile, already in
   // B-operand layout (k-step kt = accumulator kt).  (Rows 12..15 of the product are not read: their lanes re-read row 11 of A^.)
   f64x4 Mq = {0.0, 0.0, 0.0, 0.0};
   {
-    const int fb = oAh + (lj < 12 ? lj : 11) * YS + 24 + lk;
+    const int fb = Z.fb + ah;
 #pragma unroll
-    for (int kt = 0; kt < 3; ++kt) Mq = __builtin_amdgcn_mfma_f64_16x16x4f64(lds0[fb + 4 * kt], T[0][kt], Mq, 0, 0, 0);
+    for (int kt = 0; kt < 3; ++kt) Mq = __builtin_amdgcn_mfma_f64_16x16x4f64(lds_get(fb + 4 * kt * D), T[0][kt], Mq, 0, 0, 0);
   }
-  // Mt | mv and the gains to the stage record, cost-to-go to LDS (+ its state rows to the record).  Which field a row goes to is known
-  // per accumulator; a lane differs only in "state column or gamma", which is a base and a row stride of its own (K + sj, stride 24,
-  // against kappa, stride 1; alike Mt / mv and P_x / p): one store per accumulator under ONE lane mask.  Wave 0 (columns < NU) skips it.
-  if (c >= NU && c <= NR) {
-    const unsigned sj = (unsigned)(c - NU), ulk = (unsigned)lk;
-    const unsigned rs = isg ? 1u : 24u;                                    // row stride in the record
-    const unsigned iK = (isg ? (unsigned)RIC_KAP : (unsigned)RIC_K + sj) + ulk * rs, iM = (isg ? (unsigned)RIC_MV : (unsigned)RIC_MT + sj) + ulk * rs,
-                   iP = (isg ? (unsigned)RIC_PV : (unsigned)RIC_PX + sj) + ulk * rs;
-    const int scol = isg ? AH_B : (int)sj, pcw = isg ? P_PV : (int)sj;      // the own column of A^ | b and of P | p
-    landing_gptr_w rec = uniform_record(rec_);
-    double* const Pw = S.P + lk * PS + pcw;
+  // Mt | mv and the gains to the stage record, cost-to-go to LDS (+ its state rows to the record): one store per accumulator under ONE lane
+  // mask.  Nothing waits for these stores: the forward sweep is the first to read the record.
+  if (Z.wr) {
+    const int sw = Z.sw + ah;
 #pragma unroll
-    for (int r = 0; r < 3; ++r) rec[iM + (unsigned)(4 * r) * rs] = lds0[oAh + (lk + 4 * r) * YS + scol] - Mq[r];
+    for (int r = 0; r < 3; ++r) rec_put(rec, Z.iM + (unsigned)(4 * r) * Z.rs, lds_get(sw + 4 * r * YS * D) - Mq[r]);
 #pragma unroll
     for (int rt = 0; rt < 3; ++rt)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int rb = 16 * rt + 4 * r;                                    // (compile-time) row rho = rb + lk
         const double v = T[rt][r];
-        if (rb < NU) rec[iK + (unsigned)rb * rs] = v;
+        if (rb < NU) rec_put(rec, Z.iK + (unsigned)rb * Z.rs, v);
         else if (rb < NR) {
-          Pw[(rb - NU) * PS] = v;
-          if (rb - NU < 12) rec[iP + (unsigned)(rb - NU) * rs] = v;
+          lds_put(Z.pw + (rb - NU) * PS * D, v);
+          if (rb - NU < 12) rec_put(rec, Z.iP + (unsigned)(rb - NU) * Z.rs, v);
         }
       }
   }
   return true;
 }
 
-// One backward Riccati step (templated on the control dimension: 24 = (f_k, c_{k+1}), 12 = last stage): elimination of the
-// controls of stage k (G + T^T P T; P_k, p_k -> LDS, gains -> record k) with the assembly of stage k - 1 riding along.
-template <int NU>
-__device__ __forceinline__ bool riccati_step(double* rec, double delta, int k) {
-  const bool ok = block_eliminate<NU>(rec, delta, k);
-  __syncthreads();
+// The last stage (NU = 12: no c+) is eliminated once per sweep, out of line, with lane constants of its own
+__device__ __noinline__ bool last_stage_eliminate(double* rec_, double delta_, int k_) {
+  const StageLanes<12> Z = stage_lanes<12>();
+  const SweepCtx X = sweep_ctx();
+  return stage_eliminate<12>(Z, X, uniform_record(rec_), uni(delta_), uni(k_));
+}
+
+// The stages N - 2 .. 0 of a sweep (NU = 24: controls (f_k, c_{k+1})): ONE resident loop with the elimination inlined -- no call, no return
+// and no wait for the record's stores per stage; the record's base, delta, the context X and the loop condition live in scalar registers,
+// the lane constants Z in vector registers.  Two instances: the timed one (profile buffer set) reads the clock around every stage, the
+// other carries no trace of the timers.  `n_try` counts the eliminations attempted.
+template <bool TIMED>
+__device__ __forceinline__ bool stage_loop(const StageLanes<24>& Z, const SweepCtx& X, landing_gptr_w rec, double delta, int k, int& n_try) {
+  bool ok = true;
+  for (; k >= 0 && ok; --k, rec -= RIC_STRIDE) {
+    long long tb_ = 0;
+    if (TIMED) tb_ = (long long)wall_clock64();
+    ok = stage_eliminate<24>(Z, X, rec, delta, k);
+    __syncthreads();
+    ++n_try;
+    if (TIMED) { const long long n_ = (long long)wall_clock64(); if (threadIdx.x == 0) SH.prof[PH_B_ELIM] += (double)(n_ - tb_); }
+  }
   return ok;
 }
 
@@ -723,24 +809,32 @@ __device__ __noinline__ bool riccati_backward(double delta) {
   for (int e = lane; e < 48 * GS; e += NT) S.G[e] = 0.0;
   for (int e = lane; e < 2 * 12 * YS; e += NT) S.Ah[e] = 0.0;
   __syncthreads();
+  const SweepCtx X = sweep_ctx();
+  const bool timed = uni(S.prof_on) != 0;
   {   // the only exposed assembly of the sweep
     AsmRegs first;
-    asm_issue(N - 1, first);
+    asm_issue(N - 1, X, first);
     asm_copy(first);
     __syncthreads();
-    asm_terms(N - 1, (N - 1) & 1, first);
+    asm_terms(X, (N - 1) & 1, first);
     __syncthreads();
-    asm_combine(N - 1, (N - 1) & 1);
+    asm_combine(X, (N - 1) & 1, first);
   }
   __syncthreads();
-  for (int k = N - 1; k >= 0 && ok; --k) {
-    const bool last = (k == N - 1);
-    long long tb_ = S.prof_on ? (long long)wall_clock64() : 0;
-    // ---- G + T^T P T, elimination of the controls: P_k, p_k, gains -> record k; the assembly of stage k - 1 rides along
-    double* rec = M.ric + (size_t)k * RIC_STRIDE;
-    ok = last ? riccati_step<12>(rec, delta, k) : riccati_step<24>(rec, delta, k);
+  // ---- per stage: G + T^T P T, elimination of the controls: P_k, p_k, gains -> record k; the assembly of stage k - 1 rides along
+  {
+    long long tb_ = timed ? (long long)wall_clock64() : 0;
+    ok = uni(last_stage_eliminate(M.ric + (size_t)(N - 1) * RIC_STRIDE, delta, N - 1) ? 1 : 0) != 0;
+    __syncthreads();
     ++n_try;
-    PROF_ADD(PH_B_ELIM, tb_);
+    if (timed) { const long long n_ = (long long)wall_clock64(); if (lane == 0) S.prof[PH_B_ELIM] += (double)(n_ - tb_); }
+  }
+  if (ok && N > 1) {
+    const StageLanes<24> Z = stage_lanes<24>();
+    const int Nu = uni(N);
+    const landing_gptr_w rec = uniform_record(M.ric) + (size_t)(Nu - 2) * RIC_STRIDE;
+    const double du = uni(delta);
+    ok = timed ? stage_loop<true>(Z, X, rec, du, Nu - 2, n_try) : stage_loop<false>(Z, X, rec, du, Nu - 2, n_try);
   }
   if (ok) {
     // ---- stage 0: X_0 fixed, feet c_0 free: P_cc dc0 = -(p_c + P_cx dX0), same elimination on a 12x12 block
@@ -919,7 +1013,7 @@ __device__ __noinline__ void rc_add_grad() {     // objective gradient of the st
   const Layout& L = SH.L; const MemberMem& M = SH.M;
   for (int k = threadIdx.x; k < L.N; k += blockDim.x) { double* gU = M.gx + L.x_U(k); (void)run_cost_stage(L, M.x, SH.p, k, M.gx + L.x_X(k), gU, gU + 12); }
 }
-__device__ __noinline__ void rc_add_gamma() {    // ... and, per stage, for the right-hand sides gamma_k (w order X, c, f): added when the tile of gamma is fetched (block_eliminate)
+__device__ __noinline__ void rc_add_gamma() {    // ... and, per stage, for the right-hand sides gamma_k (w order X, c, f): added when the tile of gamma is fetched (stage_eliminate)
   const Layout& L = SH.L; const MemberMem& M = SH.M;
   for (int k = threadIdx.x; k < L.N; k += blockDim.x) {
     double gr[36];

@@ -3,7 +3,8 @@
 
 Compiles landing-controller_amd/csrc/capi.hip to assembly with the flags of csrc/Makefile (device side only) and prints, for every
 function whose demangled name contains one of --match (default: the solver kernel and the phases of its backward sweep), what the
-function is made of: instructions, instructions up to the first matrix-core instruction (operand fetch), instructions behind the last
+function is made of (and, for a function with outermost loops that hold a barrier -- the stage loops of the backward sweep -- what one
+trip of each such loop is made of): instructions, instructions up to the first matrix-core instruction (operand fetch), instructions behind the last
 barrier (write-out), MFMA / LDS / flat / global / branch counts, vector registers and the private segment.  For kernels the LDS block
 and the private segment of the kernel descriptor are added.
 
@@ -22,7 +23,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "landing-controller_amd", "csrc")
-DEFAULT_MATCH = ["block_eliminate", "riccati_backward", "landing_ipm_kernel", "forward_pass"]
+DEFAULT_MATCH = ["block_eliminate", "last_stage_eliminate", "riccati_backward", "landing_ipm_kernel", "forward_pass"]
 
 
 def makefile_flags():
@@ -53,6 +54,64 @@ def demangle(names):
 
 INSTR = re.compile(r"^\t([a-z][a-z0-9_]+)(\s|$)")
 KD = re.compile(r"^\t\t\.amdhsa_(group_segment_fixed_size|private_segment_fixed_size|next_free_vgpr|accum_offset)\s+(\d+)")
+
+
+def count_ops(ops):
+    """what a list of instruction mnemonics is made of"""
+    cnt = lambda f: sum(1 for o in ops if f(o))
+    fp64 = {k: cnt(lambda o, k=k: o.startswith("v_" + k + "_f64")) for k in ("fma", "mul", "add", "rcp")}
+    return {
+        "instructions": len(ops),
+        "mfma": cnt(lambda o: o.startswith("v_mfma")),
+        "fp64_valu": fp64,
+        "lds_read": cnt(lambda o: o.startswith("ds_read") or o.startswith("ds_load")),
+        "lds_write": cnt(lambda o: o.startswith("ds_write") or o.startswith("ds_store")),
+        "flat_load": cnt(lambda o: o.startswith("flat_load")), "flat_store": cnt(lambda o: o.startswith("flat_store")),
+        "global_load": cnt(lambda o: o.startswith("global_load")), "global_store": cnt(lambda o: o.startswith("global_store")),
+        "scratch": cnt(lambda o: o.startswith("scratch_") or o.startswith("buffer_")),
+        "branch": cnt(lambda o: o.startswith("s_cbranch") or o == "s_branch"),
+        "call": cnt(lambda o: o.startswith("s_swappc")), "clock": cnt(lambda o: o.startswith("s_memrealtime") or o.startswith("s_memtime")),
+        "s_waitcnt": cnt(lambda o: o == "s_waitcnt"),
+        "v_cmp": cnt(lambda o: o.startswith("v_cmp")), "v_cndmask": cnt(lambda o: o.startswith("v_cndmask")),
+        "exec_mask_salu": cnt(lambda o: re.match(r"s_(and|or|xor|andn2|orn2)(_saveexec)?_b64", o) is not None),
+        "int_address_valu": cnt(lambda o: re.match(r"v_(add_u32|sub_u32|subrev_u32|add_co_u32|mad_u32_u24|mul_u32_u24|mad_u64_u32|lshl|lshr|ashr|or_b32|and_b32|and_or|add3|add_lshl|lshl_add|lshl_or|min_[iu]32|max_[iu]32)", o) is not None),
+        "barrier": cnt(lambda o: o == "s_barrier"),
+    }
+
+
+LOOP_HEAD = re.compile(r"^(\.LBB\d+_\d+):\s*; =>This (?:Inner )?Loop Header: Depth=1")
+
+
+def barrier_loops(body):
+    """The outermost loops of a function that hold a barrier (the stage loops of the backward sweep), each counted twice: `body` = from the
+    loop's header label to its last back branch, `with_tail_blocks` = that plus the blocks of the loop the compiler laid out behind the back
+    branch (blocks commented `in Loop: Header=<label>`; they are executed inside the loop as well)."""
+    out = []
+    for i, line in enumerate(body):
+        m = LOOP_HEAD.match(line)
+        if not m:
+            continue
+        label = m.group(1)
+        back = max((j for j in range(i + 1, len(body)) if re.match(r"^\ts_c?branch\S*\s+" + re.escape(label) + r"\s*$", body[j].split(";")[0].rstrip())), default=None)
+        if back is None:
+            continue
+        inner = [mm.group(1) for mm in (INSTR.match(b) for b in body[i:back + 1]) if mm]
+        if "s_barrier" not in inner:
+            continue
+        tail, j, inside = [], back + 1, False
+        while j < len(body):
+            lm = re.match(r"^\.LBB\d+_\d+:(.*)$", body[j])
+            if lm:
+                inside = ("Header=" + label[2:]) in lm.group(1)
+                if not inside:
+                    break
+            elif inside:
+                mm = INSTR.match(body[j])
+                if mm:
+                    tail.append(mm.group(1))
+            j += 1
+        out.append({"header": label, "body": count_ops(inner), "with_tail_blocks": count_ops(inner + tail)})
+    return out
 
 
 def census(path, match):
@@ -87,26 +146,12 @@ def census(path, match):
         ops = [m.group(1) for m in (INSTR.match(b) for b in body) if m]
         first_mfma = next((k for k, o in enumerate(ops) if o.startswith("v_mfma")), None)
         last_bar = max((k for k, o in enumerate(ops) if o == "s_barrier"), default=None)
-        cnt = lambda f: sum(1 for o in ops if f(o))
-        fp64 = {k: cnt(lambda o, k=k: o.startswith("v_" + k + "_f64")) for k in ("fma", "mul", "add", "rcp")}
-        row = {
-            "instructions": len(ops),
-            "to_first_mfma": first_mfma,
-            "behind_last_barrier": None if last_bar is None else len(ops) - 1 - last_bar,
-            "mfma": cnt(lambda o: o.startswith("v_mfma")),
-            "fp64_valu": fp64,
-            "lds_read": cnt(lambda o: o.startswith("ds_read") or o.startswith("ds_load")),
-            "lds_write": cnt(lambda o: o.startswith("ds_write") or o.startswith("ds_store")),
-            "flat_load": cnt(lambda o: o.startswith("flat_load")), "flat_store": cnt(lambda o: o.startswith("flat_store")),
-            "global_load": cnt(lambda o: o.startswith("global_load")), "global_store": cnt(lambda o: o.startswith("global_store")),
-            "scratch": cnt(lambda o: o.startswith("scratch_") or o.startswith("buffer_")),
-            "branch": cnt(lambda o: o.startswith("s_cbranch") or o == "s_branch"),
-            "v_cmp": cnt(lambda o: o.startswith("v_cmp")), "v_cndmask": cnt(lambda o: o.startswith("v_cndmask")),
-            "exec_mask_salu": cnt(lambda o: re.match(r"s_(and|or|xor|andn2|orn2)(_saveexec)?_b64", o) is not None),
-            "int_address_valu": cnt(lambda o: re.match(r"v_(add_u32|sub_u32|subrev_u32|add_co_u32|mad_u32_u24|mul_u32_u24|mad_u64_u32|lshl|lshr|ashr|or_b32|and_b32|and_or|add3|add_lshl|lshl_add|lshl_or|min_[iu]32|max_[iu]32)", o) is not None),
-            "barrier": cnt(lambda o: o == "s_barrier"),
-            "vgprs": info.get("NumVgprs"), "private_segment": info.get("ScratchSize"), "code_bytes": info.get("codeLenInByte"),
-        }
+        row = count_ops(ops)
+        row.update({"to_first_mfma": first_mfma, "behind_last_barrier": None if last_bar is None else len(ops) - 1 - last_bar,
+                    "vgprs": info.get("NumVgprs"), "private_segment": info.get("ScratchSize"), "code_bytes": info.get("codeLenInByte")})
+        loops = barrier_loops(body)
+        if loops:
+            row["barrier_loops"] = loops
         if name in kd:
             row["kernel_descriptor"] = kd[name]
         out[pretty[name]] = row
@@ -132,6 +177,9 @@ def main():
     print("%-58s" % "function" + "".join(" %9s" % k[:9] for k in keys))
     for f, row in sorted(res.items()):
         print("%-58s" % f[:58] + "".join(" %9s" % ("-" if row[k] is None else row[k]) for k in keys))
+        for lp in row.get("barrier_loops", []):
+            print("    loop %s: %d instructions to the back branch, %d with the loop's blocks behind it; clock reads %d, calls %d, scratch %d" % (
+                lp["header"], lp["body"]["instructions"], lp["with_tail_blocks"]["instructions"], lp["with_tail_blocks"]["clock"], lp["with_tail_blocks"]["call"], lp["with_tail_blocks"]["scratch"]))
         if "kernel_descriptor" in row:
             print("    kernel descriptor: " + ", ".join("%s %d" % kv for kv in sorted(row["kernel_descriptor"].items())))
     if a.json:

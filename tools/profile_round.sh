@@ -24,4 +24,4 @@ python3 tools/pmc_sweep_summary.py $tag $out/sw_fetch $out/sw_write 23 > $out/su
 cp profiles/${tag}_pmc_ipm.json profiles/${tag}_pmc_sweep.json $out/ 2>/dev/null || true
 find $out -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats.csv \;
 find $out -name "*_kernel_trace.csv" -delete; find $out -name "*agent_info.csv" -delete
-du -sh $out; tail -3 $out/*.err | tail -20
+du -sh $out; for f in $out/*.err; do tail -n 3 $f; done | tail -20
