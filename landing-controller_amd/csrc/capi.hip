@@ -58,6 +58,54 @@ template <typename T> class DevBuf {
  private:
   T* p_ = nullptr; size_t n_ = 0;
 };
+
+// Device twins of the host arrays of one call, for the entry points that take host pointers.  Bound to a stream: nullptr = blocking copies and a
+// device-wide wait (the null-stream entry points), else asynchronous copies on that stream and a wait for it.  Sizes are element counts.  Every
+// block is a DevBuf of the object: whatever path leaves the caller frees them all, after the stream's queued work has drained.  An error is sticky:
+// once an allocation or a copy has failed the later calls do nothing and return nullptr, so a site checks error() once, before its launch.
+class Staging {
+ public:
+  explicit Staging(hipStream_t s) : s_(s) {}
+  ~Staging() { if (busy_) (void)hipStreamSynchronize(s_); }      // (an error path: nothing queued on the stream may outlive the blocks)
+  template <typename T> T* block(size_t n) {      // neither copied in nor back: scratch of the call, or an output its caller reads with pull()
+    if (err_ != hipSuccess) return nullptr;
+    blocks_.emplace_back();
+    err_ = blocks_.back().alloc(n * sizeof(T));
+    return reinterpret_cast<T*>(blocks_.back().get());
+  }
+  template <typename T> T* in(const T* host, size_t n) {      // (an optional input that is absent stays absent: nullptr)
+    T* d = host ? block<T>(n) : nullptr;
+    if (d) err_ = copy(d, host, n * sizeof(T), true);
+    return err_ == hipSuccess ? d : nullptr;
+  }
+  template <typename T> T* out(T* host, size_t n) { return host ? out_always(host, n) : nullptr; }
+  template <typename T> T* out_always(T* host, size_t n) {      // for the kernels that write an output whether the caller keeps it or not
+    T* d = block<T>(n);
+    if (d && host) back_.push_back({host, d, n * sizeof(T)});
+    return d;
+  }
+  hipError_t error() const { return err_; }
+  hipError_t fetch() {      // waits for the work queued so far, then copies every output back
+    if (err_ == hipSuccess) err_ = s_ ? hipStreamSynchronize(s_) : hipDeviceSynchronize();
+    for (const Back& b : back_) if (err_ == hipSuccess) err_ = copy(b.host, b.dev, b.bytes, false);
+    if (s_ && err_ == hipSuccess && (err_ = hipStreamSynchronize(s_)) == hipSuccess) busy_ = false;
+    return err_;
+  }
+  template <typename T> hipError_t pull(T* host, const T* dev, size_t n) {      // after fetch(): a part of a block whose size the results decide
+    if (err_ == hipSuccess) err_ = copy(host, dev, n * sizeof(T), false);
+    if (s_ && err_ == hipSuccess && (err_ = hipStreamSynchronize(s_)) == hipSuccess) busy_ = false;
+    return err_;
+  }
+ private:
+  struct Back { void* host; const void* dev; size_t bytes; };
+  hipError_t copy(void* dst, const void* src, size_t bytes, bool to_device) {
+    if (!s_) return hipMemcpy(dst, src, bytes, to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost);
+    busy_ = true;
+    return hipMemcpyAsync(dst, src, bytes, to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, s_);
+  }
+  hipStream_t s_; hipError_t err_ = hipSuccess; bool busy_ = false;
+  std::vector<DevBuf<unsigned char>> blocks_; std::vector<Back> back_;
+};
 struct KdCasadi;      // kd_casadi_capi.inc
 struct KdCasadiFree { void operator()(KdCasadi* k) const; };
 }  // namespace
@@ -434,30 +482,14 @@ int landing_eval_batch_host(landing_ctx* ctx, int B, const double* x, const doub
   if (!ctx || B <= 0 || !x || !p) return fail(LANDING_E_ARG, "landing_eval_batch_host: bad argument");
   const Layout& L = ctx->L;
   HIP_TRY(hipSetDevice(ctx->device));
-  DevBuf<double> dx, dp, dlf, dlg, df, dg, dgf, dj, dh, dgx, dgp;
+  Staging st(nullptr);
   const size_t b = (size_t)B;
-  HIP_TRY(dx.alloc(b * L.nx)); HIP_TRY(dp.alloc(b * L.np));
-  HIP_TRY(hipMemcpy(dx.get(), x, b * L.nx * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dp.get(), p, b * L.np * 8, hipMemcpyHostToDevice));
-  if (lam_f) { HIP_TRY(dlf.alloc(b)); HIP_TRY(hipMemcpy(dlf.get(), lam_f, b * 8, hipMemcpyHostToDevice)); }
-  if (lam_g) { HIP_TRY(dlg.alloc(b * L.ng)); HIP_TRY(hipMemcpy(dlg.get(), lam_g, b * L.ng * 8, hipMemcpyHostToDevice)); }
-  if (f) HIP_TRY(df.alloc(b));
-  if (g) HIP_TRY(dg.alloc(b * L.ng));
-  if (grad_f) HIP_TRY(dgf.alloc(b * L.nx));
-  if (jac) HIP_TRY(dj.alloc(b * L.nnz_jac));
-  if (hess) HIP_TRY(dh.alloc(b * L.nnz_hess));
-  if (ggx) HIP_TRY(dgx.alloc(b * L.nx));
-  if (ggp) HIP_TRY(dgp.alloc(b * L.np));
-  int rc = landing_eval_batch(ctx, B, dx.get(), dp.get(), dlf.get(), dlg.get(), df.get(), dg.get(), dgf.get(), dj.get(), dh.get(), dgx.get(), dgp.get(), nullptr);
-  if (rc) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  if (f) HIP_TRY(hipMemcpy(f, df.get(), b * 8, hipMemcpyDeviceToHost));
-  if (g) HIP_TRY(hipMemcpy(g, dg.get(), b * L.ng * 8, hipMemcpyDeviceToHost));
-  if (grad_f) HIP_TRY(hipMemcpy(grad_f, dgf.get(), b * L.nx * 8, hipMemcpyDeviceToHost));
-  if (jac) HIP_TRY(hipMemcpy(jac, dj.get(), b * L.nnz_jac * 8, hipMemcpyDeviceToHost));
-  if (hess) HIP_TRY(hipMemcpy(hess, dh.get(), b * L.nnz_hess * 8, hipMemcpyDeviceToHost));
-  if (ggx) HIP_TRY(hipMemcpy(ggx, dgx.get(), b * L.nx * 8, hipMemcpyDeviceToHost));
-  if (ggp) HIP_TRY(hipMemcpy(ggp, dgp.get(), b * L.np * 8, hipMemcpyDeviceToHost));
+  const double* dx = st.in(x, b * L.nx); const double* dp = st.in(p, b * L.np); const double* dlf = st.in(lam_f, b); const double* dlg = st.in(lam_g, b * L.ng);
+  double* df = st.out(f, b); double* dg = st.out(g, b * L.ng); double* dgf = st.out(grad_f, b * L.nx); double* dj = st.out(jac, b * L.nnz_jac);
+  double* dh = st.out(hess, b * L.nnz_hess); double* dgx = st.out(ggx, b * L.nx); double* dgp = st.out(ggp, b * L.np);
+  HIP_TRY(st.error());
+  if (int rc = landing_eval_batch(ctx, B, dx, dp, dlf, dlg, df, dg, dgf, dj, dh, dgx, dgp, nullptr)) return rc;
+  HIP_TRY(st.fetch());
   return 0;
 }
 
@@ -466,16 +498,13 @@ int landing_eval_hess_rc_batch_host(landing_ctx* ctx, int B, const double* x, co
   if (!ctx || B <= 0 || !x || !p || !lam_g || !hess_rc) return fail(LANDING_E_ARG, "landing_eval_hess_rc_batch_host: bad argument");
   const Layout& L = ctx->L;
   HIP_TRY(hipSetDevice(ctx->device));
-  DevBuf<double> dx, dp, dlf, dlg, dh;
+  Staging st(nullptr);
   const size_t b = (size_t)B, nrc = (size_t)landing_nnz_hess_rc(L.N);
-  HIP_TRY(dx.alloc(b * L.nx)); HIP_TRY(dp.alloc(b * L.np)); HIP_TRY(dlg.alloc(b * L.ng)); HIP_TRY(dh.alloc(b * nrc));
-  HIP_TRY(hipMemcpy(dx.get(), x, b * L.nx * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dp.get(), p, b * L.np * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dlg.get(), lam_g, b * L.ng * 8, hipMemcpyHostToDevice));
-  if (lam_f) { HIP_TRY(dlf.alloc(b)); HIP_TRY(hipMemcpy(dlf.get(), lam_f, b * 8, hipMemcpyHostToDevice)); }
-  if (int rc = landing_eval_hess_rc_batch(ctx, B, dx.get(), dp.get(), dlf.get(), dlg.get(), dh.get(), nullptr)) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(hess_rc, dh.get(), b * nrc * 8, hipMemcpyDeviceToHost));
+  const double* dx = st.in(x, b * L.nx); const double* dp = st.in(p, b * L.np); const double* dlf = st.in(lam_f, b); const double* dlg = st.in(lam_g, b * L.ng);
+  double* dh = st.out(hess_rc, b * nrc);
+  HIP_TRY(st.error());
+  if (int rc = landing_eval_hess_rc_batch(ctx, B, dx, dp, dlf, dlg, dh, nullptr)) return rc;
+  HIP_TRY(st.fetch());
   return 0;
 }
 
@@ -492,6 +521,7 @@ int landing_bounds_batch(landing_ctx* ctx, int B, const double* d_p, double* d_l
 }  // extern "C"
 
 #include "solver_capi.inc"
+#include "rbd_capi.inc"
 #include "multi_capi.inc"
 #include "stream_capi.inc"
 #include "kd_capi.inc"

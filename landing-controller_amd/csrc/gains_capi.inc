@@ -81,30 +81,13 @@ int landing_tracking_gains_host(landing_ctx* ctx, int B, const double* x, const 
     if (!ctx->host_stream) HIP_TRY(hipStreamCreateWithFlags(&ctx->host_stream, hipStreamNonBlocking)); }
   hipStream_t hs = ctx->host_stream;
   const size_t b = (size_t)B, pts = b * n;
-  DevBuf<double> dx, dp, dP, dK, dA, dB, dxr, dfr;
-  DevBuf<int> ds;
-  HIP_TRY(dx.alloc(b * L.nx)); HIP_TRY(dp.alloc(b * L.np));
-  if (status) HIP_TRY(ds.alloc(b));
-  if (P) HIP_TRY(dP.alloc(pts * 576));
-  if (K) HIP_TRY(dK.alloc(pts * 288));
-  if (A) HIP_TRY(dA.alloc(pts * 576));
-  if (Bm) HIP_TRY(dB.alloc(pts * 288));
-  if (xref) HIP_TRY(dxr.alloc(pts * 24));
-  if (fref) HIP_TRY(dfr.alloc(pts * 12));
-  HIP_TRY(hipMemcpyAsync(dx.get(), x, b * L.nx * 8, hipMemcpyHostToDevice, hs));
-  HIP_TRY(hipMemcpyAsync(dp.get(), p, b * L.np * 8, hipMemcpyHostToDevice, hs));
-  if (status) HIP_TRY(hipMemcpyAsync(ds.get(), status, b * sizeof(int), hipMemcpyHostToDevice, hs));
-  int rc = landing_tracking_gains_batch(ctx, B, dx.get(), dp.get(), ds.get(), dt_r, n, Ib3x3, mass, Q, r_diag, F, rk4,
-                                        dP.get(), dK.get(), dA.get(), dB.get(), dxr.get(), dfr.get(), hs);
-  if (rc == 0 && hipStreamSynchronize(hs) != hipSuccess) rc = fail(LANDING_E_HIP, std::string(who) + ": kernel failed");
-  if (rc) { (void)hipStreamSynchronize(hs); return rc; }
-  if (P) HIP_TRY(hipMemcpyAsync(P, dP.get(), pts * 576 * 8, hipMemcpyDeviceToHost, hs));
-  if (K) HIP_TRY(hipMemcpyAsync(K, dK.get(), pts * 288 * 8, hipMemcpyDeviceToHost, hs));
-  if (A) HIP_TRY(hipMemcpyAsync(A, dA.get(), pts * 576 * 8, hipMemcpyDeviceToHost, hs));
-  if (Bm) HIP_TRY(hipMemcpyAsync(Bm, dB.get(), pts * 288 * 8, hipMemcpyDeviceToHost, hs));
-  if (xref) HIP_TRY(hipMemcpyAsync(xref, dxr.get(), pts * 24 * 8, hipMemcpyDeviceToHost, hs));
-  if (fref) HIP_TRY(hipMemcpyAsync(fref, dfr.get(), pts * 12 * 8, hipMemcpyDeviceToHost, hs));
-  HIP_TRY(hipStreamSynchronize(hs));
+  Staging st(hs);
+  const double* dx = st.in(x, b * L.nx); const double* dp = st.in(p, b * L.np); const int* ds = st.in(status, b);
+  double* dP = st.out(P, pts * 576); double* dK = st.out(K, pts * 288); double* dA = st.out(A, pts * 576); double* dB = st.out(Bm, pts * 288);
+  double* dxr = st.out(xref, pts * 24); double* dfr = st.out(fref, pts * 12);
+  HIP_TRY(st.error());
+  if (const int rc = landing_tracking_gains_batch(ctx, B, dx, dp, ds, dt_r, n, Ib3x3, mass, Q, r_diag, F, rk4, dP, dK, dA, dB, dxr, dfr, hs)) return rc;      // (st drains the stream)
+  HIP_TRY(st.fetch());
   return 0;
 }
 

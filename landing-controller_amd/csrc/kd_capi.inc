@@ -17,6 +17,35 @@ static void kd_launch_hess(landing_ctx* ctx, const landing::KdNlpArgs& a, long l
   else hipLaunchKernelGGL(landing::landing_kinodyn_nlp_hess_kernel<0>, grid, block, 0, st, a, pi, pj, npair);
 }
 
+// The constants of a call in the kernels' form: dt padded to its 64 slots, the base form from the context's model
+static landing::KdNlpParams kd_params(const landing_ctx* ctx, const landing_kinodyn_params* prm, int N) {
+  landing::KdNlpParams P;
+  for (int k = 0; k < 64; ++k) P.dt[k] = k < N ? prm->dt[k] : 0.0;
+  P.mass = prm->mass; P.mu = prm->mu; P.std_base = ctx->rbd_std_base;
+  for (int i = 0; i < 3; ++i) { P.Ib[i] = prm->Ib[i]; P.Ibi[i] = prm->Ib_inv[i]; }
+  return P;
+}
+// The constants of the structure probes below.  The structure must not depend on a caller's parameter VALUES (ADVICE r5: with Ib = (0.03, 0.03, 0.03) the omega-omega entries
+// of omega x I omega vanish and a later call with the real inertia got 36 wrong zeros): fixed generic ones -- distinct inertias, mu > 0, unit mass, a uniform grid -- so that
+// only the model (landing_rbd_set_model invalidates the tables) and the formulation decide what is kept.
+static landing::KdNlpParams kd_probe_params(const landing_ctx* ctx, int N) {
+  landing_kinodyn_params prm;
+  for (int k = 0; k < 64; ++k) prm.dt[k] = 0.03;
+  prm.mass = 1.0; prm.mu = 0.7; prm.Ib[0] = 0.05; prm.Ib[1] = 0.2; prm.Ib[2] = 0.3; prm.Ib_inv[0] = 17.0; prm.Ib_inv[1] = 4.3; prm.Ib_inv[2] = 3.6;
+  return kd_params(ctx, &prm, N);
+}
+// Arguments of the function-layer kernels for B members of N intervals: the model and the sizes; dense strides, no array, no list
+static landing::KdNlpArgs kd_nlp_args(const landing_ctx* ctx, int B, int N) {
+  landing::KdNlpArgs a{};
+  a.model = ctx->d_rbd.get(); a.B = B; a.N = N;
+  return a;
+}
+// The probes' random points: uniform in [0, 1) from a 64-bit linear congruential generator
+struct KdRand {
+  unsigned long long s;
+  double operator()() { s = s * 6364136223846793005ull + 1442695040888963407ull; return (double)((s >> 11) & 0xFFFFFFFFFFFFFull) / 4503599627370496.0; }
+};
+
 int landing_kinodyn_nlp_dims(int N, long long* nx, long long* ng) {
   if (N < 2 || N > 64) return fail(LANDING_E_ARG, "landing_kinodyn_nlp_dims: 2 <= N <= 64");
   if (nx) *nx = landing::kd_nx(N);
@@ -29,20 +58,13 @@ int landing_kinodyn_nlp_eval(landing_ctx* ctx, int B, int N, const double* d_x, 
   if (!ctx || B < 0 || N < 2 || N > 64 || !d_x || !prm || (!d_g && !d_jac)) return fail(LANDING_E_ARG, "landing_kinodyn_nlp_eval: bad argument");
   if (!ctx->d_rbd) return fail(LANDING_E_ARG, "landing_kinodyn_nlp_eval: no model (landing_rbd_set_model)");
   HIP_TRY(hipSetDevice(ctx->device));
-  landing::KdNlpArgs a;
-  a.sx = a.sg = a.sj = a.sh = 0; a.skip = nullptr;
-  a.model = ctx->d_rbd.get(); a.B = B; a.N = N; a.x = d_x; a.g = d_g; a.jac = d_jac; a.lam = nullptr; a.hess = nullptr;
-  for (int k = 0; k < 64; ++k) a.P.dt[k] = k < N ? prm->dt[k] : 0.0;
-  a.P.mass = prm->mass; a.P.mu = prm->mu; a.P.std_base = ctx->rbd_std_base;
-  for (int i = 0; i < 3; ++i) { a.P.Ib[i] = prm->Ib[i]; a.P.Ibi[i] = prm->Ib_inv[i]; }
+  landing::KdNlpArgs a = kd_nlp_args(ctx, B, N);
+  a.P = kd_params(ctx, prm, N); a.x = d_x; a.g = d_g; a.jac = d_jac;
   if (d_g) {
     const long long n = (long long)B * N;
     hipLaunchKernelGGL(landing::landing_kinodyn_nlp_g_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
   }
-  if (d_jac) {
-    const long long n = (long long)B * N * landing::KD_NW;
-    kd_launch_jac(ctx, a, B, N, (hipStream_t)stream);
-  }
+  if (d_jac) kd_launch_jac(ctx, a, B, N, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -54,7 +76,7 @@ int landing_kinodyn_nlp_eval(landing_ctx* ctx, int B, int N, const double* d_x, 
 // exactly 0.0 when no row couples the two variables (friction and contact rows are linear in the forces, the FK band is linear in the feet and the
 // body position, omega x I omega has no squares, ...).  286 of the 561 remain; tests/test_n1_rows.py checks EVERY column of the blocks against
 // central differences of the exact Jacobian, which also proves this list.  Caller holds ctx->mu.
-static int kd_ensure_pairs(landing_ctx* ctx, const landing::KdNlpParams& P) {
+static int kd_ensure_pairs(landing_ctx* ctx) {
   if (ctx->d_kd_pairs) return 0;
   const int NP = landing::KD_NPAIR;
   unsigned char host[2 * landing::KD_NPAIR];
@@ -62,27 +84,18 @@ static int kd_ensure_pairs(landing_ctx* ctx, const landing::KdNlpParams& P) {
   const int B = 6, N = 3, NW = landing::KD_NW;
   const size_t nx = (size_t)landing::kd_nx(N), ng = (size_t)landing::kd_ng(N), nh = (size_t)B * N * NW * NW;
   std::vector<double> hx(B * nx), hl(B * ng), hh(nh);
-  unsigned long long sdd = 0x9E3779B97F4A7C15ull;
-  auto rnd = [&]() { sdd = sdd * 6364136223846793005ull + 1442695040888963407ull; return (double)((sdd >> 11) & 0xFFFFFFFFFFFFFull) / 4503599627370496.0; };      // [0, 1)
+  KdRand rnd{0x9E3779B97F4A7C15ull};
   for (auto& v : hx) v = rnd() - 0.5;
   for (auto& v : hl) v = (0.5 + rnd()) * (rnd() < 0.5 ? -1.0 : 1.0);
-  DevBuf<unsigned char> d_full; DevBuf<double> d_x, d_l, d_h;
-  HIP_TRY(d_full.alloc(sizeof(host))); HIP_TRY(hipMemcpy(d_full.get(), host, sizeof(host), hipMemcpyHostToDevice));
-  HIP_TRY(d_x.alloc(hx.size())); HIP_TRY(hipMemcpy(d_x.get(), hx.data(), hx.size() * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(d_l.alloc(hl.size())); HIP_TRY(hipMemcpy(d_l.get(), hl.data(), hl.size() * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(d_h.alloc(nh)); HIP_TRY(hipMemset(d_h.get(), 0, nh * sizeof(double)));
-  landing::KdNlpArgs a;
-  a.sx = a.sg = a.sj = a.sh = 0; a.skip = nullptr;
-  a.model = ctx->d_rbd.get(); a.B = B; a.N = N; a.x = d_x.get(); a.g = nullptr; a.jac = nullptr; a.lam = d_l.get(); a.hess = d_h.get(); a.P = P;
-  // The structure must not depend on the caller's parameter VALUES (ADVICE r5: with Ib = (0.03, 0.03, 0.03) the omega-omega entries of omega x I omega vanish and a later
-  // call with the real inertia got 36 wrong zeros): the probe runs with fixed generic constants -- distinct inertias, mu > 0, unit mass, a uniform grid -- so that only the model
-  // (landing_rbd_set_model invalidates the table) and the formulation decide which pairs are kept.
-  for (int k = 0; k < 64; ++k) a.P.dt[k] = k < N ? 0.03 : 0.0;
-  a.P.mass = 1.0; a.P.mu = 0.7; a.P.Ib[0] = 0.05; a.P.Ib[1] = 0.2; a.P.Ib[2] = 0.3; a.P.Ibi[0] = 17.0; a.P.Ibi[1] = 4.3; a.P.Ibi[2] = 3.6;
-  const long long n = (long long)B * N * NP;
-  kd_launch_hess(ctx, a, B, N, d_full.get(), d_full.get() + NP, NP, (hipStream_t)nullptr);
+  Staging st(nullptr);
+  const unsigned char* d_full = st.in(host, sizeof(host));
+  landing::KdNlpArgs a = kd_nlp_args(ctx, B, N);
+  a.P = kd_probe_params(ctx, N); a.x = st.in(hx.data(), hx.size()); a.lam = st.in(hl.data(), hl.size()); a.hess = st.out(hh.data(), nh);
+  HIP_TRY(st.error());
+  HIP_TRY(hipMemset(a.hess, 0, nh * sizeof(double)));
+  kd_launch_hess(ctx, a, B, N, d_full, d_full + NP, NP, (hipStream_t)nullptr);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(hh.data(), d_h.get(), nh * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(st.fetch());
   unsigned char keep[2 * landing::KD_NPAIR]; int nk = 0;
   for (int q = 0; q < NP; ++q) {
     const int i = host[q], j = host[NP + q];
@@ -121,20 +134,16 @@ static int kd_ensure_jpat(landing_ctx* ctx) {
   const int B = 6, N = 4, NW = landing::KD_NW, NR = landing::KD_ROWS;
   const size_t nx = (size_t)landing::kd_nx(N), nj = (size_t)B * N * NR * NW;
   std::vector<double> hx(B * nx), hj(nj);
-  unsigned long long sdd = 0x2545F4914F6CDD1Dull;
-  auto rnd = [&]() { sdd = sdd * 6364136223846793005ull + 1442695040888963407ull; return (double)((sdd >> 11) & 0xFFFFFFFFFFFFFull) / 4503599627370496.0; };      // [0, 1)
+  KdRand rnd{0x2545F4914F6CDD1Dull};
   for (auto& v : hx) v = rnd() - 0.4;
-  DevBuf<double> d_x, d_j;
-  HIP_TRY(d_x.alloc(hx.size())); HIP_TRY(hipMemcpy(d_x.get(), hx.data(), hx.size() * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(d_j.alloc(nj)); HIP_TRY(hipMemset(d_j.get(), 0, nj * sizeof(double)));
-  landing::KdNlpArgs a;
-  a.sx = a.sg = a.sj = a.sh = 0; a.skip = nullptr;
-  a.model = ctx->d_rbd.get(); a.B = B; a.N = N; a.x = d_x.get(); a.g = nullptr; a.jac = d_j.get(); a.lam = nullptr; a.hess = nullptr;
-  for (int k = 0; k < 64; ++k) a.P.dt[k] = k < N ? 0.03 : 0.0;
-  a.P.mass = 1.0; a.P.mu = 0.7; a.P.Ib[0] = 0.05; a.P.Ib[1] = 0.2; a.P.Ib[2] = 0.3; a.P.Ibi[0] = 17.0; a.P.Ibi[1] = 4.3; a.P.Ibi[2] = 3.6; a.P.std_base = ctx->rbd_std_base;
+  Staging st(nullptr);
+  landing::KdNlpArgs a = kd_nlp_args(ctx, B, N);
+  a.P = kd_probe_params(ctx, N); a.x = st.in(hx.data(), hx.size()); a.jac = st.out(hj.data(), nj);
+  HIP_TRY(st.error());
+  HIP_TRY(hipMemset(a.jac, 0, nj * sizeof(double)));
   kd_launch_jac(ctx, a, B, N, (hipStream_t)nullptr);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(hj.data(), d_j.get(), nj * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(st.fetch());
   auto nz = [&](int k, int r, int c) { for (int b = 0; b < B; ++b) { const double v = hj[(((size_t)b * N + k) * NR + r) * NW + c]; if (v != 0.0 || v != v) return true; } return false; };
   for (int r = 12; r < NR; ++r) for (int c = 0; c < NW; ++c)
     if (nz(0, r, c) != nz(1, r, c) || nz(1, r, c) != nz(2, r, c)) return fail(LANDING_E_ARG, "kinodynamic NLP: the Jacobian blocks of two middle intervals differ in structure");
@@ -215,14 +224,10 @@ int landing_kinodyn_nlp_hess(landing_ctx* ctx, int B, int N, const double* d_x, 
   if (!ctx || B < 0 || N < 2 || N > 64 || !d_x || !prm || !d_lam_g || !d_hess) return fail(LANDING_E_ARG, "landing_kinodyn_nlp_hess: bad argument");
   if (!ctx->d_rbd) return fail(LANDING_E_ARG, "landing_kinodyn_nlp_hess: no model (landing_rbd_set_model)");
   HIP_TRY(hipSetDevice(ctx->device));
-  landing::KdNlpArgs a;
-  a.sx = a.sg = a.sj = a.sh = 0; a.skip = nullptr;
-  a.model = ctx->d_rbd.get(); a.B = B; a.N = N; a.x = d_x; a.g = nullptr; a.jac = nullptr; a.lam = d_lam_g; a.hess = d_hess;
-  for (int k = 0; k < 64; ++k) a.P.dt[k] = k < N ? prm->dt[k] : 0.0;
-  a.P.mass = prm->mass; a.P.mu = prm->mu; a.P.std_base = ctx->rbd_std_base;
-  for (int i = 0; i < 3; ++i) { a.P.Ib[i] = prm->Ib[i]; a.P.Ibi[i] = prm->Ib_inv[i]; }
+  landing::KdNlpArgs a = kd_nlp_args(ctx, B, N);
+  a.P = kd_params(ctx, prm, N); a.x = d_x; a.lam = d_lam_g; a.hess = d_hess;
   std::lock_guard<std::mutex> lock(ctx->mu);      // (the lazily built table below, like every other lazily created resource of the context)
-  { const int rc = kd_ensure_pairs(ctx, a.P); if (rc) return rc; }      // the list of structurally non-zero pairs of a block, built once per context
+  { const int rc = kd_ensure_pairs(ctx); if (rc) return rc; }      // the list of structurally non-zero pairs of a block, built once per context
   const long long n = (long long)B * N * ctx->kd_npair;
   if (n > 0x7fffffffLL * 64) return fail(LANDING_E_ARG, "landing_kinodyn_nlp_hess: batch too large for one launch");
   HIP_TRY(hipMemsetAsync(d_hess, 0, (size_t)B * N * landing::KD_NW * landing::KD_NW * sizeof(double), (hipStream_t)stream));
@@ -315,10 +320,8 @@ int landing_kinodyn_solve_batch(landing_ctx* ctx, int B, int N, const landing_ki
   A.ov[0].clip_k = o.clip_k > 4 ? 4 : 16;
   A.ov[1].clip_k = 16; A.ov[1].bound_push = 0.1; A.ov[1].bound_frac = 0.1;
   A.ov[2].mu_init = 1.0;
-  for (int k = 0; k < 64; ++k) A.P.dt[k] = k < N ? prm->dt[k] : 0.0;
-  A.P.mass = prm->mass; A.P.mu = prm->mu; A.P.std_base = ctx->rbd_std_base;
-  for (int i = 0; i < 3; ++i) { A.P.Ib[i] = prm->Ib[i]; A.P.Ibi[i] = prm->Ib_inv[i]; }
-  { const int rc = kd_ensure_pairs(ctx, A.P); if (rc) return rc; }      // structurally non-zero pairs of a Hessian block
+  A.P = kd_params(ctx, prm, N);
+  { const int rc = kd_ensure_pairs(ctx); if (rc) return rc; }      // structurally non-zero pairs of a Hessian block
   { const int rc = kd_ensure_jpat(ctx); if (rc) return rc; }            // structurally non-zero entries of a Jacobian block
   A.jpat = (const landing::KdJPat*)ctx->d_kd_jpat.get(); A.cpat = (const landing::KdCPat*)(ctx->d_kd_jpat.get() + ctx->kd_cpat_off);
   A.x0 = d_x0; A.lb = d_lbg; A.ub = d_ubg; A.cost = d_cost; A.ws = ctx->d_kd_ws.get(); A.ws_stride = stride;
@@ -326,23 +329,16 @@ int landing_kinodyn_solve_batch(landing_ctx* ctx, int B, int N, const landing_ki
   A.x_out = d_x; A.f_out = d_f; A.lam_out = d_lam_g; A.status = d_status; A.iters = d_iters; A.kkt = d_kkt; A.n_active = cnt + 1; A.n_cond = cnt + 2; A.done = ctx->d_kd_done.get();
   int* const dlist[2] = {A.cond_list + BT, A.cond_list + 2 * BT}; int* const dcnt[2] = {cnt, cnt + 3};
   A.dlist_next = dlist[0]; A.n_dnext = dcnt[0];      // (the init kernel fills the list of round 0)
-  // function-layer launches straight into the workspace of every member
-  const size_t nx = (size_t)landing::kd_nx(N), ng = (size_t)landing::kd_ng(N);
-  landing::KdNlpArgs F;
-  F.model = ctx->d_rbd.get(); F.P = A.P; F.B = BT; F.N = N;
-  F.x = A.ws;                           // M.x is the first array of a member's block
-  F.lam = A.ws + 4 * nx + 6 * ng;       // M.y
-  F.g = nullptr;
-  F.jac = A.ws + 4 * nx + 10 * ng;      // M.J
+  // function-layer launches straight into the workspace of every member: the arrays of member 0's block, one block further per member
+  const landing::KdMem M = landing::kd_carve(N, A.ws);
+  landing::KdNlpArgs F = kd_nlp_args(ctx, BT, N);
+  F.P = A.P; F.x = M.x; F.lam = M.y; F.jac = M.J; F.hess = M.H; F.jty = M.jty;
   F.jcol = &A.cpat->jcol[0][0][0];               // the Jacobian kernel writes compact blocks (rbd_kernels.hip KD_JCS)
-  F.hess = F.jac + (size_t)N * landing::KD_JCS;      // (compact Jacobian blocks)
-  F.jty = F.hess + (size_t)N * landing::KD_NW * landing::KD_NW + (size_t)(N + 1) * landing::KD_REC + (size_t)N * landing::KD_NW;      // M.jty (behind H, the records and wbuf)
   F.sx = F.sg = F.sj = F.sh = (long long)stride; F.skip = A.done;
   // structural zeros of the Hessian blocks are written once; the kernel rewrites the 561 pairs of every block each iteration.  (The whole
   // workspace is cleared: the blocks are its largest part.)
-  const long long nj = (long long)BT * N * landing::KD_NW, nh = (long long)BT * N * ctx->kd_npair;
+  const long long nh = (long long)BT * N * ctx->kd_npair;
   if (nh > 0x7fffffffLL * 64) return fail(LANDING_E_ARG, "landing_kinodyn_solve_batch: batch too large for one launch");      // (before anything is queued: ADVICE r5)
-  (void)nj;
   HIP_TRY(scratch_acquire(ctx, st));      // an earlier call's finish kernel (any stream) may still read the workspace, the flags and the counter
   // whatever path leaves this function from here on, the work queued so far is fenced for the next user of the context's scratch blocks (ADVICE r5: the error returns
   // below used to skip scratch_release, and the next call on another stream was then not ordered behind the memsets and launches already queued)
@@ -480,22 +476,13 @@ int landing_kinodyn_solve_batch_host(landing_ctx* ctx, int B, int N, const landi
   const size_t nx = (size_t)landing::kd_nx(N), ng = (size_t)landing::kd_ng(N);
   const size_t b = (size_t)B;
   {
-    DevBuf<double> d_lb, d_ub, d_cost, d_x0, d_x, d_f, d_lam, d_kkt;
-    DevBuf<int> d_st, d_it;
-    HIP_TRY(d_lb.alloc(b * ng)); HIP_TRY(d_ub.alloc(b * ng)); HIP_TRY(d_cost.alloc(b * 24)); HIP_TRY(d_x0.alloc(b * nx));
-    HIP_TRY(d_x.alloc(b * nx)); HIP_TRY(d_f.alloc(b)); HIP_TRY(d_lam.alloc(b * ng)); HIP_TRY(d_kkt.alloc(b * 3));
-    HIP_TRY(d_st.alloc(b)); HIP_TRY(d_it.alloc(b));
-    HIP_TRY(hipMemcpy(d_lb.get(), lbg, b * ng * sizeof(double), hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(d_ub.get(), ubg, b * ng * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_cost.get(), cost, b * 24 * sizeof(double), hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(d_x0.get(), x0, b * nx * sizeof(double), hipMemcpyHostToDevice));
-    const int rc = landing_kinodyn_solve_batch(ctx, B, N, prm, d_lb.get(), d_ub.get(), d_cost.get(), d_x0.get(), opts, d_x.get(), d_f.get(), d_lam.get(), d_st.get(), d_it.get(), d_kkt.get(), nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(x, d_x.get(), b * nx * sizeof(double), hipMemcpyDeviceToHost));
-    if (f) HIP_TRY(hipMemcpy(f, d_f.get(), b * sizeof(double), hipMemcpyDeviceToHost));
-    if (lam_g) HIP_TRY(hipMemcpy(lam_g, d_lam.get(), b * ng * sizeof(double), hipMemcpyDeviceToHost));
-    if (status) HIP_TRY(hipMemcpy(status, d_st.get(), b * sizeof(int), hipMemcpyDeviceToHost));
-    if (iters) HIP_TRY(hipMemcpy(iters, d_it.get(), b * sizeof(int), hipMemcpyDeviceToHost));
-    if (kkt) HIP_TRY(hipMemcpy(kkt, d_kkt.get(), b * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    Staging st(nullptr);
+    const double* d_lb = st.in(lbg, b * ng); const double* d_ub = st.in(ubg, b * ng); const double* d_cost = st.in(cost, b * 24); const double* d_x0 = st.in(x0, b * nx);
+    double* d_x = st.out(x, b * nx); double* d_f = st.out_always(f, b); double* d_lam = st.out_always(lam_g, b * ng); double* d_kkt = st.out_always(kkt, b * 3);
+    int* d_st = st.out_always(status, b); int* d_it = st.out_always(iters, b);
+    HIP_TRY(st.error());
+    if (const int rc = landing_kinodyn_solve_batch(ctx, B, N, prm, d_lb, d_ub, d_cost, d_x0, opts, d_x, d_f, d_lam, d_st, d_it, d_kkt, nullptr)) return rc;
+    HIP_TRY(st.fetch());
   }      // (the staging blocks go before the retry ladder allocates its own)
   // ---- retry ladder (default options only): the members the first pass left undecided (iteration limit / numerical failure) are solved again
   // from the same initial guess with another slack initialisation, then with a smaller first barrier parameter.  Which members end undecided
@@ -598,25 +585,15 @@ int landing_kinodyn_pattern(landing_ctx* ctx, int N, int which /* 0 = jac_g_x, 1
   const size_t no = (size_t)T * N * (which ? NW * NW : NR * NW);
   std::vector<double> out(no);
   {
-    DevBuf<double> d_x, d_l, d_o;
-    HIP_TRY(d_x.alloc(x.size())); HIP_TRY(d_l.alloc(lam.size())); HIP_TRY(d_o.alloc(no));
-    HIP_TRY(hipMemcpy(d_x.get(), x.data(), x.size() * 8, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(d_l.get(), lam.data(), lam.size() * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(d_o.get(), 0, no * 8));
-    const int rc = which ? landing_kinodyn_nlp_hess(ctx, T, N, d_x.get(), &prm, d_l.get(), d_o.get(), nullptr) : landing_kinodyn_nlp_eval(ctx, T, N, d_x.get(), &prm, nullptr, d_o.get(), nullptr);
+    Staging st(nullptr);
+    const double* d_x = st.in(x.data(), x.size()); const double* d_l = st.in(lam.data(), lam.size());
+    double* d_o = st.out(out.data(), no);
+    HIP_TRY(st.error());
+    HIP_TRY(hipMemset(d_o, 0, no * sizeof(double)));
+    const int rc = which ? landing_kinodyn_nlp_hess(ctx, T, N, d_x, &prm, d_l, d_o, nullptr) : landing_kinodyn_nlp_eval(ctx, T, N, d_x, &prm, nullptr, d_o, nullptr);
     if (rc) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out.data(), d_o.get(), no * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(st.fetch());
   }
-  // x index of block column j of interval k (kd_w_index, host copy)
-  auto widx = [&](int k, int j) {
-    const int oJ = 12 * (N + 1), oU = oJ + 12 * N;
-    if (j < 12) return 12 * k + j;
-    if (j < 24) return oU + 24 * k + (j - 12);
-    if (j < 36) return oU + 24 * k + 12 + (j - 24);
-    if (j < 48) return oJ + 12 * k + (j - 36);
-    if (j < 60) return 12 * (k + 1) + (j - 48);
-    return k + 1 < N ? oU + 24 * (k + 1) + (j - 60) : -1;
-  };
   std::vector<std::set<long long>> cols(nx);
   if (!which) {
     const int oU = 12 * (N + 1) + 12 * N;
@@ -625,7 +602,7 @@ int landing_kinodyn_pattern(landing_ctx* ctx, int N, int which /* 0 = jac_g_x, 1
     for (int k = 0; k < N; ++k) {
       const int nr = k == N - 1 ? landing::KD_ROWS_LAST : NR;
       for (int r = 0; r < nr; ++r) for (int j = 0; j < NW; ++j) {
-        const int xi = widx(k, j); if (xi < 0) continue;
+        const int xi = landing::kd_w_index(N, k, j); if (xi < 0) continue;
         bool nz = false;
         for (int t = 0; t < T; ++t) nz = nz || out[(((size_t)t * N + k) * NR + r) * NW + j] != 0.0;
         if (nz) cols[xi].insert(landing::KD_BND + (long long)k * NR + r);
@@ -634,7 +611,7 @@ int landing_kinodyn_pattern(landing_ctx* ctx, int N, int which /* 0 = jac_g_x, 1
   } else {
     for (int i = 0; i < 12; ++i) cols[12 * N + i].insert(12 * N + i);      /* terminal cost 2 QN on X(:, N+1) (entries with QN = 0 are structural too: QN is a parameter) */
     for (int k = 0; k < N; ++k) for (int a = 0; a < NW; ++a) for (int b2 = 0; b2 < NW; ++b2) {
-      const int xa = widx(k, a), xb = widx(k, b2); if (xa < 0 || xb < 0) continue;
+      const int xa = landing::kd_w_index(N, k, a), xb = landing::kd_w_index(N, k, b2); if (xa < 0 || xb < 0) continue;
       bool nz = false;
       for (int t = 0; t < T; ++t) nz = nz || out[(((size_t)t * N + k) * NW + a) * NW + b2] != 0.0;
       if (nz) { const int lo = xa < xb ? xa : xb, hi = xa < xb ? xb : xa; cols[hi].insert(lo); }
@@ -703,52 +680,22 @@ int landing_debug_kd_state(landing_ctx* ctx, int member, double* out) {
   return 0;
 }
 
-/* The reference's 'quad3D' Mini-Cheetah tree with the 'mc3D' parameters (get_robot_model.m:134-234, get_robot_params.m:50-115) in the compact
- * form of landing_rbd_model -- what landing-controller_amd/rbd.py::quad3d_model builds for the Python callers, for C / mex callers. */
-void landing_rbd_model_mc3d(landing_rbd_model* M) {
-  memset(M, 0, sizeof(*M));
-  struct Rbi { double m, h[3], I[6]; };
-  auto rbi = [](double m, const double* com, const double (*rot)[3]) {      /* spatialInertia.m: (m, m c, rot + m (c'c 1 - c c')) about the origin */
-    Rbi o; o.m = m;
-    const double cc = com[0] * com[0] + com[1] * com[1] + com[2] * com[2];
-    double Ib[3][3];
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) Ib[i][j] = rot[i][j] + m * ((i == j ? cc : 0.0) - com[i] * com[j]);
-    for (int i = 0; i < 3; ++i) o.h[i] = m * com[i];
-    o.I[0] = Ib[0][0]; o.I[1] = Ib[0][1]; o.I[2] = Ib[0][2]; o.I[3] = Ib[1][1]; o.I[4] = Ib[1][2]; o.I[5] = Ib[2][2];
-    return o;
-  };
-  auto flip_y = [](Rbi a) { a.h[1] = -a.h[1]; a.I[1] = -a.I[1]; a.I[4] = -a.I[4]; return a; };      /* flipAlongAxis(I, 'Y'), get_robot_model.m:852-889 */
-  const double c_ab[3] = {0, 0.036, 0}, c_hip[3] = {0, 0.016, -0.02}, c_kn[3] = {0, 0, -0.061}, c_b[3] = {0, 0, 0};
-  const double r_ab[3][3] = {{381e-6, 58e-6, 0.45e-6}, {58e-6, 560e-6, 0.95e-6}, {0.45e-6, 0.95e-6, 444e-6}};
-  const double r_hip[3][3] = {{1983e-6, 245e-6, 13e-6}, {245e-6, 2103e-6, 1.5e-6}, {13e-6, 1.5e-6, 408e-6}};
-  const double r_kn[3][3] = {{6e-6, 0, 0}, {0, 248e-6, 0}, {0, 0, 245e-6}};
-  const double r_b[3][3] = {{11253e-6, 0, 0}, {0, 36203e-6, 0}, {0, 0, 42673e-6}};
-  const Rbi abad = rbi(0.54, c_ab, r_ab), hip = rbi(0.634, c_hip, r_hip), knee = rbi(0.064, c_kn, r_kn), body = rbi(3.3, c_b, r_b);
-  const double abad_loc[3] = {0.19, 0.049, 0.0}, hip_loc[3] = {0, 0.062, 0.0}, knee_loc[3] = {0, 0, -0.209}, foot_loc[3] = {0, 0, -0.195};
-  const double side[3][4] = {{1, 1, -1, -1}, {-1, 1, -1, 1}, {1, 1, 1, 1}};
-  const double cpi = cos(M_PI), spi = sin(M_PI);      /* rz(pi) as the reference (and rbd.py) forms it: sin(pi) = 1.2e-16, not 0 */
-  const double eye[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, rzpi[9] = {cpi, spi, 0, -spi, cpi, 0, 0, 0, 1};
-  auto put = [&](int i, int parent, int jt, const double* E, const double* r, const Rbi* in) {
-    M->parent[i] = parent; M->jtype[i] = jt;
-    for (int j = 0; j < 9; ++j) M->E[i][j] = E[j];
-    for (int j = 0; j < 3; ++j) { M->r[i][j] = r[j]; M->h[i][j] = in ? in->h[j] : 0.0; }
-    M->m[i] = in ? in->m : 0.0;
-    for (int j = 0; j < 6; ++j) M->I[i][j] = in ? in->I[j] : 0.0;
-  };
-  const double zero3[3] = {0, 0, 0};
-  const int base_jt[6] = {3, 4, 5, 0, 1, 2};      /* Px Py Pz Rx Ry Rz */
-  for (int i = 0; i < 6; ++i) put(i, i, base_jt[i], eye, zero3, i == 5 ? &body : nullptr);
-  int nb = 6, leg_side = -1;
-  for (int leg = 0; leg < 4; ++leg) {
-    const double s[3] = {side[0][leg], side[1][leg], side[2][leg]};
-    const Rbi la = leg_side > 0 ? abad : flip_y(abad), lh = leg_side > 0 ? hip : flip_y(hip), lk = leg_side > 0 ? knee : flip_y(knee);
-    double r1[3], r2[3], r3[3];
-    for (int j = 0; j < 3; ++j) { r1[j] = s[j] * abad_loc[j]; r2[j] = s[j] * hip_loc[j]; r3[j] = s[j] * knee_loc[j]; M->foot_r[leg][j] = s[j] * foot_loc[j]; }
-    put(nb, 6, 0, eye, r1, &la); put(nb + 1, nb + 1, 1, rzpi, r2, &lh); put(nb + 2, nb + 2, 1, eye, r3, &lk);
-    M->b_foot[leg] = nb + 3;
-    nb += 3; leg_side = -leg_side;
+/* The contexts behind the one-call entry points (landing_solve_kinodyn_24_on*, landing_pipeline_21_on): one per (N, device) with the 'mc3D' model, shared by
+ * all of them, built at the first call and kept until the process ends.  (Calls on one context from several host threads are serialised by the context.) */
+static int cached_mc3d_ctx(int N, int device, landing_ctx** out) {
+  static std::mutex cache_mu; static std::map<std::pair<int, int>, landing_ctx*> cache;
+  std::lock_guard<std::mutex> lock(cache_mu);
+  auto it = cache.find({N, device});
+  if (it == cache.end()) {
+    landing_ctx* ctx = landing_create(N, device, nullptr);
+    if (!ctx) return LANDING_E_ARG;
+    landing_rbd_model mdl; landing_rbd_model_mc3d(&mdl);
+    const int rc = landing_rbd_set_model(ctx, &mdl);
+    if (rc) { landing_destroy(ctx); return rc; }
+    it = cache.emplace(std::make_pair(N, device), ctx).first;
   }
-  M->l1 = 0.062; M->l2 = 0.209; M->l3 = 0.195; M->l4 = 0.004;      /* get_foot_jacobians_mc.m:5-8 */
+  *out = it->second;
+  return 0;
 }
 
 /* One-call form for FFI stubs (matlab/landing_refine_mex.c): a context per (N, device) with the 'mc3D' model is cached inside the library. */
@@ -758,18 +705,8 @@ int landing_solve_kinodyn_24_on_form(int device, int N, int B, const landing_kin
                                      const double* QN, const double* x0, const double* jpos_min, const double* jpos_max, const double* kin_box, const double* mu,
                                      const double* l_leg_max, const double* mass, const double* Ib, const double* Ib_inv, const landing_solver_opts* opts,
                                      double* x_star, double* f_star, double* lam_g, int* status, int* iters, double* kkt) {
-  static std::mutex cache_mu; static std::map<std::pair<int, int>, landing_ctx*> cache;
   landing_ctx* ctx;
-  { std::lock_guard<std::mutex> lock(cache_mu);
-    auto it = cache.find({N, device});
-    if (it == cache.end()) {
-      ctx = landing_create(N, device, nullptr);
-      if (!ctx) return LANDING_E_ARG;
-      landing_rbd_model mdl; landing_rbd_model_mc3d(&mdl);
-      const int rc = landing_rbd_set_model(ctx, &mdl);
-      if (rc) { landing_destroy(ctx); return rc; }
-      cache[{N, device}] = ctx;
-    } else ctx = it->second; }
+  if (const int rc = cached_mc3d_ctx(N, device, &ctx)) return rc;
   return landing_solve_kinodyn_24(ctx, N, B, form, Xref, Uref, dt, q_min, q_max, qd_min, qd_max, q_init, qd_init, c_init, q_term_min, q_term_max, qd_term_min,
                                   qd_term_max, QN, x0, jpos_min, jpos_max, kin_box, mu, l_leg_max, mass, Ib, Ib_inv, opts, x_star, f_star, lam_g, status, iters, kkt);
 }

@@ -24,16 +24,6 @@ struct KdCasadi {
   DevBuf<double> d_x, d_l, d_g, d_j, d_h;
 };
 void KdCasadiFree::operator()(KdCasadi* k) const { delete k; }
-
-int kdc_widx(int N, int k, int j) {
-  const int oJ = 12 * (N + 1), oU = oJ + 12 * N;
-  if (j < 12) return 12 * k + j;
-  if (j < 24) return oU + 24 * k + (j - 12);
-  if (j < 36) return oU + 24 * k + 12 + (j - 24);
-  if (j < 48) return oJ + 12 * k + (j - 36);
-  if (j < 60) return 12 * (k + 1) + (j - 48);
-  return k + 1 < N ? oU + 24 * (k + 1) + (j - 60) : -1;
-}
 }  // namespace
 
 extern "C" {
@@ -74,9 +64,9 @@ static KdCasadi* kdc_get(landing_ctx* ctx, int N) {
     r.assign((size_t)nnz, 0);
     if (landing_kinodyn_pattern(ctx, N, which, c.data(), r.data(), &nnz)) return nullptr;
   }
-  // inverse of kdc_widx per interval: x index -> block column
+  // inverse of kd_w_index per interval: x index -> block column
   std::vector<std::vector<int>> inv(N, std::vector<int>(nx, -1));
-  for (int k = 0; k < N; ++k) for (int j = 0; j < NW; ++j) { const int xi = kdc_widx(N, k, j); if (xi >= 0) inv[k][xi] = j; }
+  for (int k = 0; k < N; ++k) for (int j = 0; j < NW; ++j) { const int xi = landing::kd_w_index(N, k, j); if (xi >= 0) inv[k][xi] = j; }
   K->jsrc.assign(K->jr.size(), -1);
   for (int c = 0; c < nx; ++c) for (long long q = K->jc[c]; q < K->jc[c + 1]; ++q) {
     const long long r = K->jr[q];
@@ -145,12 +135,12 @@ int landing_kinodyn_casadi_eval_host(landing_ctx* ctx, int N, const double* x, c
   if (!g && !jac && !hess && !ggx && !ggp) return 0;
   HIP_TRY(hipSetDevice(ctx->device));
   std::lock_guard<std::mutex> lk(ctx->kdc_mu);      // the device buffers of K are used by one call at a time (CasADi calls sequentially from IPOPT's / KNITRO's thread)
-  HIP_TRY(hipMemcpy(K->d_x.get(), x, (size_t)nx * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(K->d_x.get(), x, (size_t)nx * sizeof(double), hipMemcpyHostToDevice));
   const bool need_j = jac || ggx;
   { const int rc = landing_kinodyn_nlp_eval(ctx, 1, N, K->d_x.get(), &prm, g ? K->d_g.get() : nullptr, need_j ? K->d_j.get() : nullptr, nullptr); if ((g || need_j) && rc) return rc; }
   std::vector<double> blk;
-  if (need_j) { blk.resize((size_t)N * NR * NW); HIP_TRY(hipMemcpy(blk.data(), K->d_j.get(), blk.size() * 8, hipMemcpyDeviceToHost)); }
-  if (g) HIP_TRY(hipMemcpy(g, K->d_g.get(), (size_t)ng * 8, hipMemcpyDeviceToHost));
+  if (need_j) { blk.resize((size_t)N * NR * NW); HIP_TRY(hipMemcpy(blk.data(), K->d_j.get(), blk.size() * sizeof(double), hipMemcpyDeviceToHost)); }
+  if (g) HIP_TRY(hipMemcpy(g, K->d_g.get(), (size_t)ng * sizeof(double), hipMemcpyDeviceToHost));
   if (jac) for (size_t q = 0; q < K->jr.size(); ++q) jac[q] = K->jsrc[q] < 0 ? 1.0 : blk[K->jsrc[q]];
   if (ggx) {      // lam_f grad f + J' lam
     for (int i = 0; i < nx; ++i) ggx[i] = 0.0;
@@ -158,10 +148,10 @@ int landing_kinodyn_casadi_eval_host(landing_ctx* ctx, int N, const double* x, c
     for (int c = 0; c < nx; ++c) { double a = 0.0; for (long long q = K->jc[c]; q < K->jc[c + 1]; ++q) a += (K->jsrc[q] < 0 ? 1.0 : blk[K->jsrc[q]]) * lam_g[K->jr[q]]; ggx[c] += a; }
   }
   if (hess) {
-    HIP_TRY(hipMemcpy(K->d_l.get(), lam_g, (size_t)ng * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(K->d_l.get(), lam_g, (size_t)ng * sizeof(double), hipMemcpyHostToDevice));
     { const int rc = landing_kinodyn_nlp_hess(ctx, 1, N, K->d_x.get(), &prm, K->d_l.get(), K->d_h.get(), nullptr); if (rc) return rc; }
     std::vector<double> hb((size_t)N * NW * NW);
-    HIP_TRY(hipMemcpy(hb.data(), K->d_h.get(), hb.size() * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(hb.data(), K->d_h.get(), hb.size() * sizeof(double), hipMemcpyDeviceToHost));
     for (size_t q = 0; q < K->hr.size(); ++q) {
       double v = 0.0;
       for (int n = 0; n < 2; ++n) if (K->hsrc[q][n] >= 0) v += hb[K->hsrc[q][n]];
@@ -184,7 +174,7 @@ int landing_kinodyn_casadi_eval_host(landing_ctx* ctx, int N, const double* x, c
         pp[ip] = p[ip] + (s ? -h : h);
         set_prm(pp.data());
         { const int rc = landing_kinodyn_nlp_eval(ctx, 1, N, K->d_x.get(), &prm, K->d_g.get(), nullptr, nullptr); if (rc) return rc; }
-        HIP_TRY(hipMemcpy((s ? gm : gp).data(), K->d_g.get(), (size_t)ng * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy((s ? gm : gp).data(), K->d_g.get(), (size_t)ng * sizeof(double), hipMemcpyDeviceToHost));
       }
       pp[ip] = p[ip];
       double a = 0.0;

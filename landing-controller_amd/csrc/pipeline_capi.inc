@@ -196,27 +196,18 @@ int landing_pipeline_21(landing_ctx* ctx, int B, const double* Xref, const doubl
   std::vector<double> p(b * L.np);
   { const int rc = landing_pack_args21(L.N, B, &a, p.data()); if (rc) return rc; }
   HIP_TRY(hipSetDevice(ctx->device));
-  DevBuf<double> d_p, d_x0, d_x, d_f, d_lam, d_kkt, d_in, d_out;
-  DevBuf<int> d_st, d_it, d_idx;
-  HIP_TRY(d_p.alloc(p.size())); HIP_TRY(d_x0.alloc(b * L.nx)); HIP_TRY(d_x.alloc(b * nxk)); HIP_TRY(d_f.alloc(b)); HIP_TRY(d_kkt.alloc(3 * b));
-  if (lam_g) HIP_TRY(d_lam.alloc(b * ng));
-  HIP_TRY(d_in.alloc(9 * b)); HIP_TRY(d_out.alloc(b * nxk)); HIP_TRY(d_st.alloc(3 * b)); HIP_TRY(d_it.alloc(3 * b)); HIP_TRY(d_idx.alloc(b + 1));
-  HIP_TRY(hipMemcpy(d_p.get(), p.data(), p.size() * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_x0.get(), x0, b * L.nx * sizeof(double), hipMemcpyHostToDevice));
-  const int rc = landing_pipeline_batch(ctx, B, d_p.get(), d_x0.get(), opts, nullptr, d_x.get(), d_f.get(), d_lam.get(), d_st.get(), d_it.get(), d_kkt.get(),
-                                        d_in.get(), d_out.get(), d_idx.get(), d_idx.get() + B, nullptr);
-  if (rc) return rc;
-  HIP_TRY(hipDeviceSynchronize());
+  Staging st(nullptr);
+  const double* d_p = st.in(p.data(), p.size()); const double* d_x0 = st.in(x0, b * L.nx);
+  double* d_x = st.out(x, b * nxk); double* d_f = st.out_always(f, b); double* d_kkt = st.out_always(kkt, 3 * b); double* d_lam = st.out(lam_g, b * ng);
+  double* d_in = st.block<double>(9 * b); double* d_out = st.block<double>(b * nxk);      // (the first `kept` rows are the caller's: read below)
+  int* d_st = st.out(status, 3 * b); int* d_it = st.out_always(iters, 3 * b); int* d_idx = st.block<int>(b + 1);
+  HIP_TRY(st.error());
+  if (const int rc = landing_pipeline_batch(ctx, B, d_p, d_x0, opts, nullptr, d_x, d_f, d_lam, d_st, d_it, d_kkt, d_in, d_out, d_idx, d_idx + B, nullptr)) return rc;
+  HIP_TRY(st.fetch());
   int kept = 0;
-  HIP_TRY(hipMemcpy(&kept, d_idx.get() + B, sizeof(int), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(x, d_x.get(), b * nxk * sizeof(double), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(status, d_st.get(), 3 * b * sizeof(int), hipMemcpyDeviceToHost));
-  if (f) HIP_TRY(hipMemcpy(f, d_f.get(), b * sizeof(double), hipMemcpyDeviceToHost));
-  if (lam_g) HIP_TRY(hipMemcpy(lam_g, d_lam.get(), b * ng * sizeof(double), hipMemcpyDeviceToHost));
-  if (iters) HIP_TRY(hipMemcpy(iters, d_it.get(), 3 * b * sizeof(int), hipMemcpyDeviceToHost));
-  if (kkt) HIP_TRY(hipMemcpy(kkt, d_kkt.get(), 3 * b * sizeof(double), hipMemcpyDeviceToHost));
-  if (pair_in && kept) HIP_TRY(hipMemcpy(pair_in, d_in.get(), 9 * (size_t)kept * sizeof(double), hipMemcpyDeviceToHost));
-  if (pair_out && kept) HIP_TRY(hipMemcpy(pair_out, d_out.get(), (size_t)kept * nxk * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(st.pull(&kept, d_idx + B, 1));
+  if (pair_in && kept) HIP_TRY(st.pull(pair_in, d_in, 9 * (size_t)kept));
+  if (pair_out && kept) HIP_TRY(st.pull(pair_out, d_out, (size_t)kept * nxk));
   if (n_kept) *n_kept = kept;
   return 0;
 }
@@ -228,19 +219,9 @@ int landing_pipeline_21_on(int device, int N, int B, const double* Xref, const d
                            const double* mu, const double* l_leg_max, const double* f_max, const double* mass,
                            const double* Ib, const double* Ib_inv, const landing_pipeline_opts* opts,
                            double* x, double* f, double* lam_g, int* status, int* iters, double* kkt, double* pair_in, double* pair_out, int* n_kept) {
-  static std::mutex cache_mu; static std::map<std::pair<int, int>, landing_ctx*> cache;
   if (N < 2 || N > 64) return fail(LANDING_E_ARG, "landing_pipeline_21_on: the refinement takes 2 <= N <= 64 intervals");
   landing_ctx* ctx;
-  { std::lock_guard<std::mutex> lock(cache_mu);
-    auto it = cache.find({N, device});
-    if (it == cache.end()) {
-      ctx = landing_create(N, device, nullptr);
-      if (!ctx) return LANDING_E_ARG;
-      landing_rbd_model mdl; landing_rbd_model_mc3d(&mdl);
-      const int rc = landing_rbd_set_model(ctx, &mdl);
-      if (rc) { landing_destroy(ctx); return rc; }
-      cache[{N, device}] = ctx;
-    } else ctx = it->second; }
+  if (const int rc = cached_mc3d_ctx(N, device, &ctx)) return rc;      // (kd_capi.inc: the context landing_solve_kinodyn_24_on uses for this N and device)
   return landing_pipeline_21(ctx, B, Xref, Uref, dt, q_min, q_max, qd_min, qd_max, q_init, qd_init, q_term_min, q_term_max, qd_term_min, qd_term_max, QN, x0,
                              mu, l_leg_max, f_max, mass, Ib, Ib_inv, opts, x, f, lam_g, status, iters, kkt, pair_in, pair_out, n_kept);
 }

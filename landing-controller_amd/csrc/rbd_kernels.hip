@@ -812,7 +812,7 @@ struct KdNlpArgs {
   __host__ __device__ size_t oh(int b) const { return (size_t)b * (sh ? (size_t)sh : (size_t)N * 72 * 72); }
 };
 // index of w[j] of interval k in x
-__device__ __forceinline__ int kd_w_index(int N, int k, int j) {
+__host__ __device__ __forceinline__ int kd_w_index(int N, int k, int j) {
   const int oJ = 12 * (N + 1), oU = oJ + 12 * N;
   if (j < 12) return 12 * k + j;
   if (j < 24) return oU + 24 * k + (j - 12);

@@ -368,23 +368,13 @@ int landing_solve_batch_host(landing_ctx* ctx, int B, const double* p, const dou
     if (!ctx->host_stream) HIP_TRY(hipStreamCreateWithFlags(&ctx->host_stream, hipStreamNonBlocking)); }
   hipStream_t hs = ctx->host_stream;
   const size_t b = (size_t)B;
-  DevBuf<double> dp, dx0, dx, df, dl, dk;
-  DevBuf<int> dsi;          // status | iters
-  HIP_TRY(dp.alloc(b * L.np)); HIP_TRY(dx0.alloc(b * L.nx)); HIP_TRY(dx.alloc(b * L.nx)); HIP_TRY(df.alloc(b));
-  HIP_TRY(dl.alloc(b * L.ng)); HIP_TRY(dk.alloc(b * 3)); HIP_TRY(dsi.alloc(2 * b));
-  int* ds = dsi.get(); int* di = ds + b;
-  HIP_TRY(hipMemcpyAsync(dp.get(), p, b * L.np * 8, hipMemcpyHostToDevice, hs));
-  HIP_TRY(hipMemcpyAsync(dx0.get(), x0, b * L.nx * 8, hipMemcpyHostToDevice, hs));
-  int rc = landing_solve_batch(ctx, B, dp.get(), dx0.get(), opts, dx.get(), df.get(), dl.get(), ds, di, dk.get(), hs);
-  if (rc == 0 && hipStreamSynchronize(hs) != hipSuccess) rc = fail(LANDING_E_HIP, "landing_solve_batch_host: kernel failed");
-  if (rc) { (void)hipStreamSynchronize(hs); return rc; }
-  HIP_TRY(hipMemcpyAsync(x, dx.get(), b * L.nx * 8, hipMemcpyDeviceToHost, hs));
-  if (f) HIP_TRY(hipMemcpyAsync(f, df.get(), b * 8, hipMemcpyDeviceToHost, hs));
-  if (lam_g) HIP_TRY(hipMemcpyAsync(lam_g, dl.get(), b * L.ng * 8, hipMemcpyDeviceToHost, hs));
-  if (status) HIP_TRY(hipMemcpyAsync(status, ds, b * sizeof(int), hipMemcpyDeviceToHost, hs));
-  if (iters) HIP_TRY(hipMemcpyAsync(iters, di, b * sizeof(int), hipMemcpyDeviceToHost, hs));
-  if (kkt) HIP_TRY(hipMemcpyAsync(kkt, dk.get(), b * 3 * 8, hipMemcpyDeviceToHost, hs));
-  HIP_TRY(hipStreamSynchronize(hs));
+  Staging st(hs);
+  const double* dp = st.in(p, b * L.np); const double* dx0 = st.in(x0, b * L.nx);
+  double* dx = st.out(x, b * L.nx); double* df = st.out_always(f, b); double* dl = st.out_always(lam_g, b * L.ng); double* dk = st.out_always(kkt, b * 3);
+  int* ds = st.out_always(status, b); int* di = st.out_always(iters, b);
+  HIP_TRY(st.error());
+  if (const int rc = landing_solve_batch(ctx, B, dp, dx0, opts, dx, df, dl, ds, di, dk, hs)) return rc;      // (st drains the stream before its blocks go)
+  HIP_TRY(st.fetch());
   return 0;
 }
 
@@ -532,160 +522,6 @@ int landing_mpc_shift(landing_ctx* ctx, int B, const double* d_x_prev, const dou
   HIP_TRY(hipSetDevice(ctx->device));
   const size_t n = (size_t)B * ctx->L.nx;
   hipLaunchKernelGGL(landing::landing_mpc_shift_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ctx->L, B, d_x_prev, d_state, d_p, d_x0);
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-// ---- floating-base rigid-body routines (rbd_kernels.hip) ------------------------------------------------------------------
-int landing_rbd_set_model(landing_ctx* ctx, const landing_rbd_model* model) {
-  if (!ctx || !model) return fail(LANDING_E_ARG, "landing_rbd_set_model: bad argument");
-  static_assert(sizeof(landing_rbd_model) == sizeof(landing::RbdModel), "C ABI and device model layouts agree");
-  for (int i = 0; i < 18; ++i) {
-    if (model->parent[i] < 0 || model->parent[i] > i || model->jtype[i] < 0 || model->jtype[i] > 5) return fail(LANDING_E_ARG, "landing_rbd_set_model: parent must precede its child, joint type 0..5");
-  }
-  for (int l = 0; l < 4; ++l) if (model->b_foot[l] < 3 || model->b_foot[l] > 18) return fail(LANDING_E_ARG, "landing_rbd_set_model: foot bodies are the third link of a leg chain");
-  HIP_TRY(hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  if (!ctx->d_rbd) HIP_TRY(ctx->d_rbd.alloc(1));
-  HIP_TRY(hipMemcpy(ctx->d_rbd.get(), model, sizeof(landing::RbdModel), hipMemcpyHostToDevice));
-  if (ctx->d_kd_pairs) {      // the Hessian pair table of the kinodynamic NLP was probed with the previous model (kd_ensure_pairs): built again at the next use
-    HIP_TRY(hipDeviceSynchronize());      // (a launch of an earlier call may still read it)
-    ctx->d_kd_pairs.reset(); ctx->kd_npair = 0;
-  }
-  if (ctx->d_kd_jpat) { HIP_TRY(hipDeviceSynchronize()); ctx->d_kd_jpat.reset(); }      // (kd_ensure_jpat: the same)
-  { bool arrow = true;       // parent = [0 1 2 3 4 5 | 6 7 8 | 6 10 11 | 6 13 14 | 6 16 17]
-    for (int i = 0; i < 6; ++i) arrow = arrow && model->parent[i] == i;
-    for (int l = 0; l < 4; ++l) arrow = arrow && model->parent[6 + 3 * l] == 6 && model->parent[7 + 3 * l] == 7 + 3 * l && model->parent[8 + 3 * l] == 8 + 3 * l;
-    ctx->rbd_arrow = arrow; }
-  { bool sb = true;      // base joints Px Py Pz Rx Ry Rz in a chain, identity tree transforms: the kinodynamic rows take the base transform from R and pos (rbd_kernels.hip kd_stage_rows)
-    const int want[6] = {3, 4, 5, 0, 1, 2};
-    for (int i = 0; i < 6; ++i) {
-      sb = sb && model->parent[i] == i && model->jtype[i] == want[i];
-      for (int j = 0; j < 9; ++j) sb = sb && model->E[i][j] == ((j % 4 == 0) ? 1.0 : 0.0);
-      for (int j = 0; j < 3; ++j) sb = sb && model->r[i][j] == 0.0;
-    }
-    ctx->rbd_std_base = sb ? 1 : 0; }
-  return 0;
-}
-
-int landing_fb_dynamics_batch(landing_ctx* ctx, int npts, const double* d_q, const double* d_qd, const double* d_tau, const double* d_f_foot,
-                              double* d_H, double* d_C, double* d_qdd, double* d_A, double* d_Hinv, double fd_h, void* stream) {
-  if (ctx && npts == 0) return 0;
-  if (!ctx || npts < 0 || !d_q || !d_qd) return fail(LANDING_E_ARG, "landing_fb_dynamics_batch: bad argument");
-  if (!ctx->d_rbd) return fail(LANDING_E_ARG, "landing_fb_dynamics_batch: no model (landing_rbd_set_model)");
-  if ((d_qdd || d_A) && !d_tau) return fail(LANDING_E_ARG, "landing_fb_dynamics_batch: qdd / A need tau");
-  HIP_TRY(hipSetDevice(ctx->device));
-  landing::FbArgs a{ctx->d_rbd.get(), npts, d_q, d_qd, d_tau, d_f_foot, d_H, d_C, d_qdd, d_A, d_Hinv, fd_h > 0.0 ? fd_h : 1e-6, ctx->rbd_arrow ? 1 : 0};
-  if (d_H || d_C || (d_qdd && !(d_A && fd_h <= 0.0))) hipLaunchKernelGGL(landing::landing_fb_hc_kernel, dim3((npts + 63) / 64), dim3(64), 0, (hipStream_t)stream, a);
-  if (d_A && fd_h <= 0.0) {
-    // exact linearisation (forward mode): pass 1 leaves qdd and H^-1 per knot in the caller's buffers or in a context scratch
-    // (stream-ordered reuse: one linearisation in flight per context), pass 2 pushes the 36 tangent directions through the recursion
-    double* qs = d_qdd; double* hs = d_Hinv;
-    std::lock_guard<std::mutex> lock(ctx->mu);      // the scratch belongs to the context (host threads sharing it are serialised here)
-    if (!qs || !hs) {
-      HIP_TRY(ctx->d_fb_scratch.grow((size_t)npts * (18 + 324)));      // hipFree waits for the device: no launch still reads the old block
-      if (!qs) qs = ctx->d_fb_scratch.get();
-      if (!hs) hs = ctx->d_fb_scratch.get() + (size_t)npts * 18;
-    }
-    const bool own = (qs == ctx->d_fb_scratch.get()) || (hs == ctx->d_fb_scratch.get() + (size_t)npts * 18);
-    if (own) HIP_TRY(scratch_acquire(ctx, (hipStream_t)stream));
-    hipLaunchKernelGGL(landing::landing_fb_lin_exact_prep_kernel, dim3((npts + 63) / 64), dim3(64), 0, (hipStream_t)stream, a, qs, hs);
-    const long long n = 36LL * npts;
-    if (a.arrow) hipLaunchKernelGGL(landing::landing_fb_lin_exact_kernel<true>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a, (const double*)qs, (const double*)hs);
-    else hipLaunchKernelGGL(landing::landing_fb_lin_exact_kernel<false>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a, (const double*)qs, (const double*)hs);
-    if (own) HIP_TRY(scratch_release(ctx, (hipStream_t)stream));
-  } else if (d_A || d_Hinv) {
-    const long long n = 54LL * npts;
-    hipLaunchKernelGGL(landing::landing_fb_lin_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
-  }
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-int landing_leg_ik_batch(landing_ctx* ctx, int npts, const double* d_q6, const double* d_c, const double* jpos_min3, const double* jpos_max3,
-                         int iters, double* d_jpos, double* d_res, void* stream) {
-  if (ctx && npts == 0) return 0;
-  if (!ctx || npts < 0 || !d_q6 || !d_c || !d_jpos || !jpos_min3 || !jpos_max3 || iters < 1) return fail(LANDING_E_ARG, "landing_leg_ik_batch: bad argument");
-  if (!ctx->d_rbd) return fail(LANDING_E_ARG, "landing_leg_ik_batch: no model (landing_rbd_set_model)");
-  HIP_TRY(hipSetDevice(ctx->device));
-  landing::IkArgs a{ctx->d_rbd.get(), npts, d_q6, d_c, d_jpos, d_res, iters, {jpos_min3[0], jpos_min3[1], jpos_min3[2]}, {jpos_max3[0], jpos_max3[1], jpos_max3[2]}};
-  const long long n = 4LL * npts;
-  hipLaunchKernelGGL(landing::landing_leg_ik_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-int landing_kinodyn_rows_batch(landing_ctx* ctx, int npts, const double* d_q6, const double* d_c, const double* d_f, const double* d_jpos,
-                               double* d_fk, double* d_fk_err, double* d_tau, void* stream) {
-  if (ctx && npts == 0) return 0;
-  if (!ctx || npts < 0 || !d_q6 || !d_jpos || (d_fk_err && !d_c) || (d_tau && !d_f)) return fail(LANDING_E_ARG, "landing_kinodyn_rows_batch: bad argument");
-  if (!ctx->d_rbd) return fail(LANDING_E_ARG, "landing_kinodyn_rows_batch: no model (landing_rbd_set_model)");
-  HIP_TRY(hipSetDevice(ctx->device));
-  landing::KdArgs a{ctx->d_rbd.get(), npts, d_q6, d_c, d_f, d_jpos, d_fk, d_fk_err, d_tau};
-  hipLaunchKernelGGL(landing::landing_kinodyn_rows_kernel, dim3((npts + 63) / 64), dim3(64), 0, (hipStream_t)stream, a);
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-int landing_wb_backward(landing_ctx* ctx, int B, int N, double dt, double reg, const double* d_x, const double* d_u, const double* d_xref,
-                        const double* d_A, const double* d_Hinv, const double* Q36, const double* R12, const double* QN36,
-                        double* d_K, double* d_kff, double* d_dV, int* d_ok, void* stream) {
-  if (ctx && B == 0) return 0;
-  if (!ctx || B < 0 || N < 1 || !(dt > 0.0) || !d_x || !d_u || !d_xref || !d_A || !d_Hinv || !Q36 || !R12 || !QN36 || !d_K || !d_kff || !d_dV || !d_ok)
-    return fail(LANDING_E_ARG, "landing_wb_backward: bad argument");
-  HIP_TRY(hipSetDevice(ctx->device));
-  landing::WbBackArgs a;
-  a.B = B; a.N = N; a.dt = dt; a.reg = reg; a.semi = ctx->wb_semi; a.x = d_x; a.u = d_u; a.xref = d_xref; a.A = d_A; a.Hinv = d_Hinv;
-  for (int i = 0; i < 36; ++i) { a.Q[i] = Q36[i]; a.QN[i] = QN36[i]; }
-  for (int i = 0; i < 12; ++i) a.R[i] = R12[i];
-  a.K = d_K; a.kff = d_kff; a.dV = d_dV; a.ok = d_ok;
-  hipLaunchKernelGGL(landing::landing_wb_backward_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, a);
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-int landing_wb_set_integrator(landing_ctx* ctx, int semi_implicit) {
-  if (!ctx) return fail(LANDING_E_ARG, "landing_wb_set_integrator: bad argument");
-  ctx->wb_semi = semi_implicit ? 1 : 0;
-  return 0;
-}
-
-/* the NEXT landing_wb_rollout call on this context skips the members whose d_step entry is non-zero (second stage of a two-stage step-length search) */
-int landing_wb_skip_taken(landing_ctx* ctx, const double* d_step) {
-  if (!ctx) return fail(LANDING_E_ARG, "landing_wb_skip_taken: bad argument");
-  ctx->wb_skip = d_step;
-  return 0;
-}
-
-int landing_wb_select(landing_ctx* ctx, int B, int N, int nalpha, const double* d_alphas, const int* d_ok, const double* d_xnew, const double* d_unew,
-                      const double* d_costnew, double* d_x, double* d_u, double* d_cost, double* d_step, void* stream) {
-  if (ctx && B == 0) return 0;
-  if (!ctx || B < 0 || N < 1 || nalpha == 0 || !d_alphas || !d_ok || !d_xnew || !d_unew || !d_costnew || !d_x || !d_u || !d_cost || (nalpha < 0 && !d_step)) return fail(LANDING_E_ARG, "landing_wb_select: bad argument");
-  HIP_TRY(hipSetDevice(ctx->device));
-  landing::WbSelArgs a{B, N, nalpha < 0 ? -nalpha : nalpha, nalpha < 0 ? 1 : 0, d_alphas, d_ok, d_xnew, d_unew, d_costnew, d_x, d_u, d_cost, d_step};
-  hipLaunchKernelGGL(landing::landing_wb_select_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-int landing_wb_rollout(landing_ctx* ctx, int B, int N, int nalpha, const double* d_alphas, double dt, const double* d_x, const double* d_u,
-                       const double* d_xref, const double* d_f_foot, const double* d_K, const double* d_kff, const double* Q36, const double* R12,
-                       const double* QN36, double* d_xnew, double* d_unew, double* d_cost, void* stream) {
-  if (ctx && B == 0) return 0;
-  if (!ctx || B < 0 || N < 1 || nalpha < 1 || !(dt > 0.0) || !d_alphas || !d_x || !d_u || !d_xref || !Q36 || !R12 || !QN36 || !d_xnew || !d_unew || !d_cost ||
-      ((d_K == nullptr) != (d_kff == nullptr)))
-    return fail(LANDING_E_ARG, "landing_wb_rollout: bad argument");
-  if (!ctx->d_rbd) return fail(LANDING_E_ARG, "landing_wb_rollout: no model (landing_rbd_set_model)");
-  HIP_TRY(hipSetDevice(ctx->device));
-  landing::WbRollArgs a;
-  a.model = ctx->d_rbd.get(); a.B = B; a.N = N; a.nalpha = nalpha; a.dt = dt; a.semi = ctx->wb_semi; a.alphas = d_alphas; a.x = d_x; a.u = d_u; a.xref = d_xref; a.f_foot = d_f_foot;
-  a.K = d_K; a.kff = d_kff; a.skip = ctx->wb_skip; ctx->wb_skip = nullptr;
-  a.arrow = ctx->rbd_arrow ? 1 : 0;
-  for (int i = 0; i < 36; ++i) { a.Q[i] = Q36[i]; a.QN[i] = QN36[i]; }
-  for (int i = 0; i < 12; ++i) a.R[i] = R12[i];
-  a.xnew = d_xnew; a.unew = d_unew; a.cost = d_cost;
-  const long long n = (long long)nalpha * B;
-  hipLaunchKernelGGL(landing::landing_wb_rollout_lds_kernel, dim3((unsigned)((n + landing::WB_TPB - 1) / landing::WB_TPB)), dim3(64), 0, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
   return 0;
 }

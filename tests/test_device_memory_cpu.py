@@ -39,6 +39,7 @@ def emu():
 
 RC = dict(QX=[1.0] * 12, Qc=[0.1] * 3, Qf=[0.01] * 3)
 NS, NK = 4, 2      # horizons of the SRBM and the kinodynamic cases
+NG, NP = 6, 3      # ... of the tracking gains and of the drop-state chain (tests/test_gains_chain_cpu.py, tests/test_pipeline_cpu.py)
 
 
 def _srbm(L):
@@ -109,8 +110,30 @@ def kinodyn_casadi_pattern(lib, L):      # the CasADi face builds its cache in t
     return lib.landing_kinodyn_casadi_pattern(L.ctx, NK, 0, C.byref(ci), C.byref(r), C.byref(nnz))
 
 
+def tracking_gains_host(lib, L):      # every output and the status mask; the Riccati launch keeps a device block and a pinned one in the context
+    P, X = _srbm(L)
+    n = 3
+    Ib = np.ascontiguousarray(lc("constants").composite_body_inertia()[0:3, 0:3])
+    out = [np.zeros(2 * n * k) for k in (576, 288, 576, 288, 24, 12)]
+    return lib.landing_tracking_gains_host(L.ctx, 2, _p(X), _p(P), _p(np.zeros(2, np.int32)), 0.03, n, _p(Ib), 8.252, _p(np.eye(24)), _p(np.ones(12)), None, 0,
+                                           *map(_p, out))
+
+
+def pipeline_21(lib, L):      # SRBM solve, refinement and warm re-solve of one iteration each, every output
+    capi = lc("capi")
+    a, keep, B = capi.matlab_args21(NP, lc("problem").make_args21(2, NP, 0.6, seed=5))
+    o = capi.PipelineOpts()
+    lib.landing_pipeline_opts_default(C.byref(o))
+    for s in (o.srbm, o.refine, o.resolve):
+        _opts(s)
+    nx, ng = lc("kinodyn").dims(NP)
+    out = [np.zeros(B * nx), np.zeros(B), np.zeros(B * ng), np.zeros(3 * B, np.int32), np.zeros(3 * B, np.int32), np.zeros(3 * B), np.zeros(9 * B), np.zeros(B * nx)]
+    return lib.landing_pipeline_21(L.ctx, B, *[getattr(a, n) for n in capi.ARGS21], C.byref(o), *map(_p, out), C.byref(C.c_int()))
+
+
 CASES = [(eval_batch_host, NS, None), (eval_hess_rc_batch_host, NS, RC), (solve_batch_host, NS, None), (solve_stream_host, NS, None),
-         (kinodyn_pattern, NK, None), (kinodyn_block_nonzeros, NK, None), (kinodyn_solve_batch_host, NK, None), (kinodyn_casadi_pattern, NK, None)]
+         (kinodyn_pattern, NK, None), (kinodyn_block_nonzeros, NK, None), (kinodyn_solve_batch_host, NK, None), (kinodyn_casadi_pattern, NK, None),
+         (tracking_gains_host, NG, None), (pipeline_21, NP, None)]
 
 
 def _run(emu, call, N, run_cost, fail_at):
@@ -118,7 +141,7 @@ def _run(emu, call, N, run_cost, fail_at):
     start = emu.hip_emu_live_blocks()
     L = lc("capi").LandingLib(N, lib_path=EMU, run_cost=run_cost)
     try:
-        if N == NK:
+        if N in (NK, NP):
             lc("rbd").Rbd(L)      # (sets the model)
         emu.hip_emu_fail_alloc(fail_at)
         rc = call(emu, L)
