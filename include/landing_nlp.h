@@ -575,6 +575,14 @@ typedef struct {
   int b_foot[4]; double foot_r[4][3];
   double l1, l2, l3, l4;
 } landing_rbd_model;
+/* landing_rbd_set_model takes any tree of 18 single-DoF bodies whose parents precede their children: H, C, qdd, Hinv and A WITHOUT foot forces, and
+ * landing_wb_rollout without foot forces, follow the parent table (a tree that is not the quadruped's "base chain + four 3-joint legs" in the order of
+ * landing_rbd_model_mc3d takes the generic recursion and the dense 18 x 18 solve).  Everything that reaches a FOOT composes bodies 1..6 and then
+ * b_foot-2 .. b_foot (1-based), so it needs the numbering rule
+ *     parent[0..5] = 0..5 (the base chain), and for every leg  parent[b_foot-3] = 6, parent[b_foot-2] = b_foot-2, parent[b_foot-1] = b_foot-1  (0-based entries),
+ * i.e. each leg is three consecutive bodies hanging off body 6 and ending at b_foot.  With a model that breaks the rule these return LANDING_E_ARG:
+ * landing_fb_dynamics_batch and landing_wb_rollout when d_f_foot is given, landing_leg_ik_batch, landing_kinodyn_rows_batch, the landing_kinodyn_*
+ * function layer, patterns and solves, and the landing_pipeline_* chain. */
 int landing_rbd_set_model(landing_ctx* ctx, const landing_rbd_model* model);
 int landing_fb_dynamics_batch(landing_ctx* ctx, int npts, const double* d_q, const double* d_qd, const double* d_tau, const double* d_f_foot,
                               double* d_H, double* d_C, double* d_qdd, double* d_A, double* d_Hinv, double fd_h, void* stream);

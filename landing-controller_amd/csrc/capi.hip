@@ -159,6 +159,8 @@ struct landing_ctx {
   DevBuf<double> d_pl; DevBuf<int> d_pl_int; hipEvent_t pl_done = nullptr; std::mutex pl_mu;
   const double* wb_skip = nullptr;      // landing_wb_skip_taken: consumed by the next landing_wb_rollout
   int wb_semi = 0;             // integrator of the whole-body loop: 0 explicit Euler, 1 semi-implicit Euler (landing_wb_set_integrator)
+  bool rbd_legs = false;       // bodies 0..5 are the base chain and every leg is the three consecutive bodies b_foot-3 .. b_foot-1 hanging off body 6 (landing_rbd_set_model): what
+                               // the foot-force, forward-kinematics and IK code composes (rbd_need_legs, rbd_capi.inc)
   bool rbd_arrow = false;      // the model set by landing_rbd_set_model is "six base joints + four 3-joint legs on the base": H is block-arrow (wb_kernels.hip)
   std::mutex mu;      // serialises landing_solve_batch calls on one context (the workspace belongs to the context)
   std::mutex hs_mu; landing_stream* hs_obj = nullptr; int hs_lanes = 0;      // stream of landing_solve_stream_host, one call at a time (child contexts and their workspaces are kept between calls)

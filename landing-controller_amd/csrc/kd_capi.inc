@@ -57,6 +57,7 @@ int landing_kinodyn_nlp_eval(landing_ctx* ctx, int B, int N, const double* d_x, 
   if (ctx && B == 0) return 0;
   if (!ctx || B < 0 || N < 2 || N > 64 || !d_x || !prm || (!d_g && !d_jac)) return fail(LANDING_E_ARG, "landing_kinodyn_nlp_eval: bad argument");
   if (!ctx->d_rbd) return fail(LANDING_E_ARG, "landing_kinodyn_nlp_eval: no model (landing_rbd_set_model)");
+  if (const int rc = rbd_need_legs(ctx, "landing_kinodyn_nlp_eval")) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   landing::KdNlpArgs a = kd_nlp_args(ctx, B, N);
   a.P = kd_params(ctx, prm, N); a.x = d_x; a.g = d_g; a.jac = d_jac;
@@ -223,6 +224,7 @@ int landing_kinodyn_nlp_hess(landing_ctx* ctx, int B, int N, const double* d_x, 
   if (ctx && B == 0) return 0;
   if (!ctx || B < 0 || N < 2 || N > 64 || !d_x || !prm || !d_lam_g || !d_hess) return fail(LANDING_E_ARG, "landing_kinodyn_nlp_hess: bad argument");
   if (!ctx->d_rbd) return fail(LANDING_E_ARG, "landing_kinodyn_nlp_hess: no model (landing_rbd_set_model)");
+  if (const int rc = rbd_need_legs(ctx, "landing_kinodyn_nlp_hess")) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   landing::KdNlpArgs a = kd_nlp_args(ctx, B, N);
   a.P = kd_params(ctx, prm, N); a.x = d_x; a.lam = d_lam_g; a.hess = d_hess;
@@ -285,6 +287,7 @@ int landing_kinodyn_solve_batch(landing_ctx* ctx, int B, int N, const landing_ki
   if (ctx && B == 0) return 0;
   if (!ctx || B < 0 || N < 2 || N > 64 || !prm || !d_lbg || !d_ubg || !d_cost || !d_x0 || !d_x) return fail(LANDING_E_ARG, "landing_kinodyn_solve_batch: bad argument");
   if (!ctx->d_rbd) return fail(LANDING_E_ARG, "landing_kinodyn_solve_batch: no model (landing_rbd_set_model)");
+  if (const int rc = rbd_need_legs(ctx, "landing_kinodyn_solve_batch")) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   landing_solver_opts o;
   if (opts) o = *opts; else landing_kinodyn_solver_opts_default(&o);
@@ -570,6 +573,7 @@ int landing_solve_kinodyn_24(landing_ctx* ctx, int N, int B, const landing_kinod
 int landing_kinodyn_pattern(landing_ctx* ctx, int N, int which /* 0 = jac_g_x, 1 = triu hess */, long long* colind, long long* row, long long* nnz) {
   if (!ctx || N < 2 || N > 64 || !colind || !nnz || which < 0 || which > 1) return fail(LANDING_E_ARG, "landing_kinodyn_pattern: bad argument");
   if (!ctx->d_rbd) return fail(LANDING_E_ARG, "landing_kinodyn_pattern: no model (landing_rbd_set_model)");
+  if (const int rc = rbd_need_legs(ctx, "landing_kinodyn_pattern")) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   const int nx = landing::kd_nx(N), ng = landing::kd_ng(N), NW = landing::KD_NW, NR = landing::KD_ROWS;
   landing_kinodyn_params prm;
@@ -627,6 +631,7 @@ int landing_kinodyn_pattern(landing_ctx* ctx, int N, int which /* 0 = jac_g_x, 1
 int landing_kinodyn_block_nonzeros(landing_ctx* ctx, int* nnz_mid, int* nnz_last, unsigned char* entries) {
   if (!ctx || !nnz_mid || !nnz_last) return fail(LANDING_E_ARG, "landing_kinodyn_block_nonzeros: bad argument");
   if (!ctx->d_rbd) return fail(LANDING_E_ARG, "landing_kinodyn_block_nonzeros: no model (landing_rbd_set_model)");
+  if (const int rc = rbd_need_legs(ctx, "landing_kinodyn_block_nonzeros")) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   std::lock_guard<std::mutex> lock(ctx->mu);
   { const int rc = kd_ensure_jpat(ctx); if (rc) return rc; }

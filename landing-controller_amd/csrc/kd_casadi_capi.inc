@@ -111,6 +111,7 @@ int landing_kinodyn_casadi_eval_host(landing_ctx* ctx, int N, const double* x, c
   if (!ctx || N < 2 || N > 64 || !x || !p) return fail(LANDING_E_ARG, "landing_kinodyn_casadi_eval_host: bad argument");
   if ((hess || ggx || ggp) && !lam_g) return fail(LANDING_E_ARG, "landing_kinodyn_casadi_eval_host: lam_g needed");
   if (!ctx->d_rbd) return fail(LANDING_E_ARG, "landing_kinodyn_casadi_eval_host: no model (landing_rbd_set_model)");
+  if (const int rc = rbd_need_legs(ctx, "landing_kinodyn_casadi_eval_host")) return rc;
   KdCasadi* K = kdc_get(ctx, N);
   if (!K) return LANDING_E_HIP;
   long long o[19];

@@ -14,6 +14,7 @@ static int pl_check_ctx(landing_ctx* ctx, const char* who, bool need_model) {
   if (ctx->L.run_cost != 0) return fail(LANDING_E_ARG, std::string(who) + ": the chain poses the refinement from the terminal-cost NLP's p (run_cost = 0)");
   if (ctx->L.N < 2 || ctx->L.N > 64) return fail(LANDING_E_ARG, std::string(who) + ": the refinement takes 2 <= N <= 64 intervals");
   if (need_model && !ctx->d_rbd) return fail(LANDING_E_ARG, std::string(who) + ": no model (landing_rbd_set_model)");
+  if (need_model) if (const int rc = rbd_need_legs(ctx, who)) return rc;
   return 0;
 }
 

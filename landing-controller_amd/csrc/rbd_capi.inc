@@ -1,6 +1,13 @@
 // rbd_capi.inc -- host side of the rigid-body entry points (included by capi.hip; kernels in rbd_kernels.hip and wb_kernels.hip): the model upload,
 // floating-base dynamics, leg IK, the kinodynamic rows, the whole-body backward pass / roll-out / selection, and the reference's Mini-Cheetah model.
 
+// Foot forces, foot positions and the leg IK reach a foot by composing bodies 0..5 and then b_foot-3 .. b_foot-1: a tree numbered otherwise (landing_rbd_set_model
+// accepts any) would give wrong numbers without an error, so the entry points that touch a foot refuse it.
+static int rbd_need_legs(const landing_ctx* ctx, const std::string& who) {
+  if (!ctx->rbd_legs) return fail(LANDING_E_ARG, who + ": needs a model whose bodies 0..5 are the base chain and whose legs are the consecutive bodies b_foot-3 .. b_foot-1 on body 6 (landing_rbd_set_model)");
+  return 0;
+}
+
 extern "C" {
 
 // ---- floating-base rigid-body routines (rbd_kernels.hip) ------------------------------------------------------------------
@@ -24,6 +31,10 @@ int landing_rbd_set_model(landing_ctx* ctx, const landing_rbd_model* model) {
     for (int i = 0; i < 6; ++i) arrow = arrow && model->parent[i] == i;
     for (int l = 0; l < 4; ++l) arrow = arrow && model->parent[6 + 3 * l] == 6 && model->parent[7 + 3 * l] == 7 + 3 * l && model->parent[8 + 3 * l] == 8 + 3 * l;
     ctx->rbd_arrow = arrow; }
+  { bool legs = true;        // what hand_c, rnea_tangent, the kinodynamic rows and the IK compose for a foot: bodies 0..5, then b_foot-3 .. b_foot-1 (0-based), each on its predecessor
+    for (int i = 0; i < 6; ++i) legs = legs && model->parent[i] == i;
+    for (int l = 0; l < 4; ++l) { const int jb = model->b_foot[l] - 1; legs = legs && model->parent[jb - 2] == 6 && model->parent[jb - 1] == jb - 1 && model->parent[jb] == jb; }
+    ctx->rbd_legs = legs; }
   { bool sb = true;      // base joints Px Py Pz Rx Ry Rz in a chain, identity tree transforms: the kinodynamic rows take the base transform from R and pos (rbd_kernels.hip kd_stage_rows)
     const int want[6] = {3, 4, 5, 0, 1, 2};
     for (int i = 0; i < 6; ++i) {
@@ -41,6 +52,7 @@ int landing_fb_dynamics_batch(landing_ctx* ctx, int npts, const double* d_q, con
   if (!ctx || npts < 0 || !d_q || !d_qd) return fail(LANDING_E_ARG, "landing_fb_dynamics_batch: bad argument");
   if (!ctx->d_rbd) return fail(LANDING_E_ARG, "landing_fb_dynamics_batch: no model (landing_rbd_set_model)");
   if ((d_qdd || d_A) && !d_tau) return fail(LANDING_E_ARG, "landing_fb_dynamics_batch: qdd / A need tau");
+  if (d_f_foot) if (const int rc = rbd_need_legs(ctx, "landing_fb_dynamics_batch with foot forces")) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   landing::FbArgs a{ctx->d_rbd.get(), npts, d_q, d_qd, d_tau, d_f_foot, d_H, d_C, d_qdd, d_A, d_Hinv, fd_h > 0.0 ? fd_h : 1e-6, ctx->rbd_arrow ? 1 : 0};
   if (d_H || d_C || (d_qdd && !(d_A && fd_h <= 0.0))) hipLaunchKernelGGL(landing::landing_fb_hc_kernel, dim3((npts + 63) / 64), dim3(64), 0, (hipStream_t)stream, a);
@@ -74,6 +86,7 @@ int landing_leg_ik_batch(landing_ctx* ctx, int npts, const double* d_q6, const d
   if (ctx && npts == 0) return 0;
   if (!ctx || npts < 0 || !d_q6 || !d_c || !d_jpos || !jpos_min3 || !jpos_max3 || iters < 1) return fail(LANDING_E_ARG, "landing_leg_ik_batch: bad argument");
   if (!ctx->d_rbd) return fail(LANDING_E_ARG, "landing_leg_ik_batch: no model (landing_rbd_set_model)");
+  if (const int rc = rbd_need_legs(ctx, "landing_leg_ik_batch")) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   landing::IkArgs a{ctx->d_rbd.get(), npts, d_q6, d_c, d_jpos, d_res, iters, {jpos_min3[0], jpos_min3[1], jpos_min3[2]}, {jpos_max3[0], jpos_max3[1], jpos_max3[2]}};
   const long long n = 4LL * npts;
@@ -87,6 +100,7 @@ int landing_kinodyn_rows_batch(landing_ctx* ctx, int npts, const double* d_q6, c
   if (ctx && npts == 0) return 0;
   if (!ctx || npts < 0 || !d_q6 || !d_jpos || (d_fk_err && !d_c) || (d_tau && !d_f)) return fail(LANDING_E_ARG, "landing_kinodyn_rows_batch: bad argument");
   if (!ctx->d_rbd) return fail(LANDING_E_ARG, "landing_kinodyn_rows_batch: no model (landing_rbd_set_model)");
+  if (const int rc = rbd_need_legs(ctx, "landing_kinodyn_rows_batch")) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   landing::KdArgs a{ctx->d_rbd.get(), npts, d_q6, d_c, d_f, d_jpos, d_fk, d_fk_err, d_tau};
   hipLaunchKernelGGL(landing::landing_kinodyn_rows_kernel, dim3((npts + 63) / 64), dim3(64), 0, (hipStream_t)stream, a);
@@ -143,6 +157,7 @@ int landing_wb_rollout(landing_ctx* ctx, int B, int N, int nalpha, const double*
       ((d_K == nullptr) != (d_kff == nullptr)))
     return fail(LANDING_E_ARG, "landing_wb_rollout: bad argument");
   if (!ctx->d_rbd) return fail(LANDING_E_ARG, "landing_wb_rollout: no model (landing_rbd_set_model)");
+  if (d_f_foot) if (const int rc = rbd_need_legs(ctx, "landing_wb_rollout with foot forces")) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   landing::WbRollArgs a;
   a.model = ctx->d_rbd.get(); a.B = B; a.N = N; a.nalpha = nalpha; a.dt = dt; a.semi = ctx->wb_semi; a.alphas = d_alphas; a.x = d_x; a.u = d_u; a.xref = d_xref; a.f_foot = d_f_foot;

@@ -177,7 +177,10 @@ struct WbRollArgs {
 // memory (8.5 KB per thread): the 18-body recursion indexes them through the model's parent array, so they live in scratch and one forward-dynamics
 // evaluation costs ~325 us of dependent scratch round trips (13 ms per rollout of 40 knots).  Here the arrays of WB_TPB
 // threads sit in LDS, element-major ([element][thread]: the WB_TPB lanes of a wave touch consecutive banks), one workgroup = one wave with WB_TPB
-// active lanes.  Same arithmetic in the same order as hand_c / chol_solve18 (rbd_kernels.hip): results are identical bit for bit.
+// active lanes.  hand_c_lds / chol_solve18_lds do the arithmetic of hand_c / chol_solve18 (rbd_kernels.hip) in the same order: with the dense solve (a model
+// that is not arrow) qd + dt qdd of landing_fb_dynamics_batch reproduces the rollout's velocities bit for bit on the host emulation; with the arrow solve the
+// elimination order differs and the two agree to rounding (6e-16 relative).  On the GPU neither is bit-equal (the compiler contracts the two copies of the recursion into
+// FMAs differently): 1e-16 and 6e-16 relative (tests/test_wb_kernels_cpu.py, tests/test_gpu_wb_kernels.py).
 constexpr int WB_TPB = 16;
 constexpr int WS_E = 0, WS_R = 162, WS_V = 216, WS_F = 324, WS_U = 432, WS_H = 612, WS_C = 936, WS_RHS = 954, WS_X = 972, WS_UN = 1008, WS_PER = 1020;
 static_assert(WB_TPB * WS_PER * 8 + 4096 <= 160 * 1024, "LDS of one workgroup");

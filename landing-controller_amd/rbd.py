@@ -73,7 +73,8 @@ class KinodynParams(C.Structure):
 class Rbd:
     """binds the three entry points on an existing LandingLib (its context owns the uploaded model)"""
 
-    def __init__(self, lib):
+    def __init__(self, lib, model=None):
+        """model: an RbdModel to upload instead of quad3d_model() (any tree landing_rbd_set_model takes; include/landing_nlp.h states what needs the quadruped's numbering)"""
         self.L = lib
         vp = C.c_void_p
         lib.lib.landing_rbd_set_model.argtypes = [vp, C.POINTER(RbdModel)]
@@ -87,7 +88,7 @@ class Rbd:
         ip = C.POINTER(C.c_int)
         lib.lib.landing_kinodyn_solve_batch_host.argtypes = [vp, C.c_int, C.c_int, C.POINTER(KinodynParams), dp, dp, dp, dp, vp, dp, dp, dp, ip, ip, dp]
         lib.lib.landing_kinodyn_solve_batch.argtypes = [vp, C.c_int, C.c_int, C.POINTER(KinodynParams)] + [vp] * 4 + [vp] + [vp] * 6 + [vp]
-        self.model = quad3d_model()
+        self.model = quad3d_model() if model is None else model
         lib._check(lib.lib.landing_rbd_set_model(lib.ctx, C.byref(self.model)), "landing_rbd_set_model")
 
     def fb_dynamics(self, npts, d_q, d_qd, d_tau=0, d_f_foot=0, d_H=0, d_C=0, d_qdd=0, d_A=0, d_Hinv=0, fd_h=0.0, stream=0):

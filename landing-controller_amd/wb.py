@@ -80,7 +80,7 @@ class WholeBodySQP:
             K0 = torch.as_tensor(K_init, dtype=torch.float64, device=self.dev).reshape(1, 1, 12, 36).expand(B, self.N, 12, 36).contiguous()
             xn, un, c0 = self.rollout(nom.contiguous(), u, xref, f_foot, K0, self._mk(B, self.N, 12), alphas=self._mk(1))
         x, u, cost = xn[0].contiguous(), un[0].contiguous(), c0[0].clone()
-        hist, steps = [cost.clone()], []
+        hist, steps, dV = [cost.clone()], [], None      # (iters = 0: the initial rollout alone)
         for _ in range(iters):
             A, Hinv = self.linearise(x, u, f_foot)
             K, kff, dV, ok = self.backward(x, u, xref, A, Hinv, reg)

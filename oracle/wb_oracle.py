@@ -34,25 +34,29 @@ def rollout(x0, us, xs_nom, K, kff, alpha, f_foot, dt):
     return xs, un
 
 
-def backward(xs, us, xref, f_foot, dt, Q, R, QN, reg=0.0):
+def stage_matrices(Ad, Hinv, dt):
+    """x+ = A x + B u of one Euler step linearised: A [36, 36], B [36, 12]"""
+    A = np.eye(36); A[18:, :] += dt * Ad
+    Bm = np.zeros((36, 12)); Bm[18:, :] = dt * Hinv[:, 6:]
+    if SEMI:      # q+ = q + dt qd+: the q rows are [I 0] + dt x (the qd rows)
+        A[:18, :] += dt * A[18:, :]; Bm[:18, :] = dt * Bm[18:, :]
+    else:
+        A[:18, 18:] += dt * np.eye(18)
+    return A, Bm
+
+
+def lq_backward(xs, us, xref, Ads, Hinvs, dt, Q, R, QN, reg=0.0, quu_out=None):
+    """the LQ recursion on given stage data: Ads [N, 18, 36] = d qdd / d [q; qd], Hinvs [N, 18, 18] = d qdd / d tau.  quu_out: a list that receives Quu of every
+    stage (k = N-1 first)"""
     N = us.shape[0]
     V = np.diag(QN).astype(float); v = QN * (xs[N] - xref[N])
     K = np.zeros((N, 12, 36)); kff = np.zeros((N, 12)); d1 = 0.0
     for k in range(N - 1, -1, -1):
-        q, qd = xs[k, :18], xs[k, 18:]
-        tau = np.concatenate([np.zeros(6), us[k]])
-        ff = None if f_foot is None else f_foot[k].reshape(4, 3)
-        Ad = ro.richardson_linearisation(q, qd, tau, ff)
-        H, _ = ro.hand_c(q, qd, ff)
-        Hinv = np.linalg.inv(H)
-        A = np.eye(36); A[18:, :] += dt * Ad
-        Bm = np.zeros((36, 12)); Bm[18:, :] = dt * Hinv[:, 6:]
-        if SEMI:      # q+ = q + dt qd+: the q rows are [I 0] + dt x (the qd rows)
-            A[:18, :] += dt * A[18:, :]; Bm[:18, :] = dt * Bm[18:, :]
-        else:
-            A[:18, 18:] += dt * np.eye(18)
+        A, Bm = stage_matrices(Ads[k], Hinvs[k], dt)
         Qx = Q * (xs[k] - xref[k]) + A.T @ v; Qu = R * us[k] + Bm.T @ v
         Qxx = np.diag(Q) + A.T @ V @ A; Quu = np.diag(R) + Bm.T @ V @ Bm + reg * np.eye(12); Qux = Bm.T @ V @ A
+        if quu_out is not None:
+            quu_out.append(Quu.copy())
         K[k] = -np.linalg.solve(Quu, Qux); kff[k] = -np.linalg.solve(Quu, Qu)
         d1 += kff[k] @ Qu
         V = Qxx + Qux.T @ K[k]; V = 0.5 * (V + V.T)
@@ -60,20 +64,36 @@ def backward(xs, us, xref, f_foot, dt, Q, R, QN, reg=0.0):
     return K, kff, np.array([d1, -0.5 * d1])
 
 
-def solve(x0, u_init, xref, f_foot, dt, Q, R, QN, iters, alphas=(1.0, 0.5, 0.25, 0.1, 0.03), K_init=None):
+def backward(xs, us, xref, f_foot, dt, Q, R, QN, reg=0.0):
+    N = us.shape[0]
+    Ads = np.zeros((N, 18, 36)); Hinvs = np.zeros((N, 18, 18))
+    for k in range(N):
+        q, qd = xs[k, :18], xs[k, 18:]
+        tau = np.concatenate([np.zeros(6), us[k]])
+        ff = None if f_foot is None else f_foot[k].reshape(4, 3)
+        Ads[k] = ro.richardson_linearisation(q, qd, tau, ff)
+        H, _ = ro.hand_c(q, qd, ff)
+        Hinvs[k] = np.linalg.inv(H)
+    return lq_backward(xs, us, xref, Ads, Hinvs, dt, Q, R, QN, reg)
+
+
+def solve(x0, u_init, xref, f_foot, dt, Q, R, QN, iters, alphas=(1.0, 0.5, 0.25, 0.1, 0.03), K_init=None, return_alphas=False):
+    """return_alphas: also the step length taken in every iteration (0 = none lowered the cost)"""
     if K_init is None:
         xs, us = rollout(x0, u_init, None, None, None, 0.0, f_foot, dt)
     else:       # initial rollout under u = u_init + K_init (x - xref)
         nom = xref.copy(); nom[0] = x0
         xs, us = rollout(x0, u_init, nom, np.broadcast_to(K_init, (u_init.shape[0], 12, 36)), np.zeros_like(u_init), 0.0, f_foot, dt)
-    cost = cost_of(xs, us, xref, Q, R, QN); hist = [cost]
+    cost = cost_of(xs, us, xref, Q, R, QN); hist = [cost]; taken = []
     for _ in range(iters):
         K, kff, dV = backward(xs, us, xref, f_foot, dt, Q, R, QN)
+        taken.append(0.0)
         for a in alphas:          # backtracking: the first step length that lowers the cost
             xn, un = rollout(x0, us, xs, K, kff, a, f_foot, dt)
             c = cost_of(xn, un, xref, Q, R, QN)
             if np.isfinite(c) and c < cost:
                 cost, xs, us = c, xn, un
+                taken[-1] = float(a)
                 break
         hist.append(cost)
-    return xs, us, np.array(hist)
+    return (xs, us, np.array(hist), np.array(taken)) if return_alphas else (xs, us, np.array(hist))
