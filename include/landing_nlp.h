@@ -353,7 +353,10 @@ typedef struct {
 #define LANDING_INFEASIBLE 3    /* the feasibility phase (landing_solver_opts::feas_phase) ended at a KKT point of the elastic problem (stationarity,
                                    equality rows and complementarity all within tol) with positive violation: a certificate of LOCAL
                                    infeasibility (what IPOPT reports as "converged to a point of local infeasibility"); x is that point,
-                                   kkt[0] its largest violation.  Since round 6 nothing else is reported under this code                     */
+                                   kkt[0] its largest violation, kkt[1] the elastic problem's dual infeasibility (<= tol), kkt[2] = max |lam_r| x
+                                   distance on the NLP's bounds (landing_solve_batch, d_kkt); lam_g = zU - zL of the elastic rows, the
+                                   fixed initial rows from stationarity: J' lam_g = 0 to tol, |lam_g| = feas_rho on the violated rows
+                                   (tests/certificate_reference.py).  Since round 6 nothing else is reported under this code                */
 #define LANDING_STALLED 4       /* no certificate and no solution: the feasibility phase ended at a violation that had been stationary for feas_stat
                                    iterations at mu <= 1e-4 (equality rows within 1e-3) without being a KKT point of the elastic problem, or the
                                    line search jammed again with no entry into the phase left (feas_max).  x is the last iterate, kkt[0] its largest
@@ -406,7 +409,18 @@ int landing_bounds_batch(landing_ctx* ctx, int B, const double* d_p, double* d_l
 
 /* Batched solver: B independent NLPs.  Outputs (device, any may be NULL except d_x):
  *   d_x [B][nx] solution, d_f [B] objective, d_lam_g [B][ng] multipliers (CasADi sign: >0 at upper
- *   bounds), d_status [B] (LANDING_*), d_iters [B], d_kkt [B][3] = pr_inf, du_inf, compl (unscaled). */
+ *   bounds), d_status [B] (LANDING_*), d_iters [B], d_kkt [B][3] = pr_inf, du_inf, compl (unscaled).
+ *   d_kkt of a member that did NOT converge (the same for landing_kinodyn_solve_batch):
+ *     kkt[0]  the largest violation of the NLP's rows at the returned x, whatever the status;
+ *     kkt[1]  the dual infeasibility the LAST STOP TEST saw, of the problem the iteration was solving then: |grad f + J' lam|_inf over the
+ *             free variables where the solve ended in the interior-point iteration; where it ended inside the feasibility phase -- always
+ *             at LANDING_INFEASIBLE, and at LANDING_STALLED / LANDING_MAX_ITER when the phase itself stalled or ran out -- the ELASTIC
+ *             problem's: max(|J' lam|_inf over the free variables, no objective; |z + w - feas_rho|_inf over the elastic rows).  At
+ *             LANDING_INFEASIBLE it is <= tol: that is the stationarity the status claims (the kinodynamic solver's PRESOLVE certificate,
+ *             iters = 0, never enters the phase: there kkt[1] is the NLP's dual infeasibility at the initial guess);
+ *     kkt[2]  max_r |lam_r| x distance of g_r to the bound lam_r pushes against, of the returned (x, lam_g) and the NLP's bounds.  At
+ *             LANDING_INFEASIBLE the violated rows carry |lam_r| = feas_rho, so this is feas_rho x kkt[0] to first order: the size of
+ *             the violation in units of its price, not a complementarity error of the elastic problem (that one is <= tol). */
 int landing_solve_batch(landing_ctx* ctx, int B, const double* d_p, const double* d_x0,
                         const landing_solver_opts* opts,
                         double* d_x, double* d_f, double* d_lam_g, int* d_status, int* d_iters,

@@ -1194,7 +1194,7 @@ __global__ void __launch_bounds__(KD_THREADS) landing_kd_finish_kernel(KdSolveAr
     if (A.f_out) A.f_out[m] = fo;
     if (A.status) A.status[m] = status;
     if (A.iters) A.iters[m] = K.it;
-    if (A.kkt) { A.kkt[3 * m] = kp; A.kkt[3 * m + 1] = du; A.kkt[3 * m + 2] = kc; }
+    if (A.kkt) { A.kkt[3 * m] = kp; A.kkt[3 * m + 1] = K.feas ? K.e_du : du; A.kkt[3 * m + 2] = kc; }      // (an exit inside the feasibility phase: the elastic problem's dual infeasibility of the last stop test, landing_nlp.h d_kkt)
   }
 }
 

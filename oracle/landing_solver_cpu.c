@@ -787,7 +787,7 @@ static int solve_one(const lo_form* F, const double* p, const double* x0, const 
   memcpy(x_out, W->x, sizeof(double) * nx);
   if (lam_out) memcpy(lam_out, W->y, sizeof(double) * ng);
   if (iters_out) *iters_out = it;
-  if (kkt_out) { lo_kkt(F, W->x, p, W->y, kkt_out); (void)e_du; }
+  if (kkt_out) { lo_kkt(F, W->x, p, W->y, kkt_out); if (feas) kkt_out[1] = e_du; }      /* an exit inside the feasibility phase (status 3 always): the elastic problem's dual infeasibility, as the kernel reports it (include/landing_nlp.h, d_kkt) */
   free(W->x); free(W->xt); free(W->dx); free(gx); free(W->g); free(W->gt); free(W->s); free(W->ds); free(W->zL); free(W->zU);
   free(W->dzL); free(W->dzU); free(W->y); free(W->yn); free(W->lb); free(W->ub); free(W->sig); free(W->rho); free(W->Jst); free(W->Hst);
   free(W->en); free(W->ep); free(W->wn); free(W->wp); free(W->den); free(W->dep); free(W->dwn); free(W->dwp);

@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import certificate_reference as cr
 from conftest import GOLDEN, lc
 
 pytestmark = pytest.mark.gpu
@@ -164,8 +165,18 @@ def test_feasibility_phase_decides_the_hard_law_in_one_pass(ctx):
     """Round 5: the kinodynamic solver has the SRBM solver's feasibility (restoration) phase (landing_kd_iter_kernel: elastic rows, el_step).  Law "datagen"
     (faster drops, generate_training_data_automated.m:47-50), 1024 drop states, ONE pass with explicit options (the host entry point's retry ladder only
     runs without options): at most 0.5 % undecided (round 4: 19 of 1024 after one pass, 5 after the ladder), every converged member re-certified under the
-    oracle, and every certificate of local infeasibility checked: the violation the kernel reports is the oracle's, the dynamics and the fixed initial rows
-    hold to 1e-3 where the certificate comes from the phase (a presolve certificate does not iterate at all)."""
+    oracle, and every certificate of local infeasibility checked: the violation the kernel reports is the oracle's; where the certificate comes from the phase
+    (iters > 0) the point is a KKT point of the elastic problem with the multipliers returned -- the six residuals of tests/certificate_reference.py under the
+    oracle's rows and complex-step Jacobian, rho / tol / feas_cert from the options struct: the dynamics and the fixed initial rows hold to tol (the round-5 bar
+    was 1e-3), J' lam = 0, |lam| = rho on the violated rows -- and kkt[1] is the elastic problem's dual infeasibility (landing_nlp.h d_kkt).  A presolve
+    certificate (iters == 0) does not iterate at all and claims only its violated row.
+    The portfolio's certificate path (landing_kd_finish_kernel: a clone's elastic KKT point reported under the index of an original that ended undecided, i.e. the
+    clone's x and lam_g against the ORIGINAL's bounds) is posed on purpose: the members that ended with a phase certificate again, their own iteration limit so low
+    that no original can decide (max_iter 25: 75 iterations with the phases, and the loop runs 8 max_iter = 200 rounds), clones after 4 rounds with 200 + 200
+    iterations -- every status 3 that comes back with more iterations than an original can have made is a clone's, and passes the same six residuals.
+    MI355X: 994 converged + 28 certified (26 presolve, 2 from the phase after 425 and 812 iterations, both the original's own) + 2 undecided; the 2 phase certificates: worst
+    E 1.6e-7  S 1.1e-9  rho - |lam| 1.8e-5  C 1.0e-7; posed again: member 580 comes back certified from a clone slot after 154 iterations (E 1.1e-12  S 2.2e-11  rho - |lam| 2.0e-6
+    C 1.0e-7), member 690 ends at the iteration limit."""
     L, R = ctx
     P, kd = lc("problem"), lc("kinodyn")
     from oracle import kinodyn_oracle as ko
@@ -194,7 +205,33 @@ def test_feasibility_phase_decides_the_hard_law_in_one_pass(ctx):
     eq = lbc == ubc
     ineq_v = np.where(~eq, viol, 0.0).max(axis=1); eq_v = np.where(eq, viol, 0.0).max(axis=1)
     pm = phase[cert]
-    assert (eq_v[pm] <= 1e-3 * 1.0001).all() and (ineq_v[pm] > 1e-6).all()
+    assert (eq_v[pm] <= o.tol * 1.0001).all() and (ineq_v[pm] > 1e-6).all()
+    W = cr.Worst()
+    for b in np.nonzero(phase)[0]:
+        res = cr.kd_certificate(s["x"][b], s["lam_g"][b], lb[b], ub[b], N, dt, mass, Ib, Ibi, consts.mu, o.feas_rho, o.tol, feas_cert=o.feas_cert, kkt0=s["kkt"][b, 0])
+        assert cr.failed(res) == [], (b, res)
+        assert s["kkt"][b, 1] <= o.tol * 1.0001
+        W.add(res)
+    print("landing_kd_* phase certificates:", W)
+    # which of them came from a clone slot?  A member alone, without the portfolio, gives the original's own path (batch independence: test above)
+    pi = np.nonzero(phase)[0]
+    off = R.kinodyn_default_opts(); off.kd_clone_after = 0
+    s1 = R.kinodyn_solve_host(N, lb[pi], ub[pi], cost[pi], x0[pi], dt, mass, Ib, Ibi, consts.mu, off)
+    own = np.array([s1["status"][i] == 3 and np.array_equal(s1["x"][i], s["x"][b]) for i, b in enumerate(pi)])
+    print("   of %d phase certificates %d are the original's own, %d were taken from a clone slot" % (len(pi), own.sum(), (~own).sum()))
+    oc = R.kinodyn_default_opts(); oc.max_iter = 25; oc.kd_clone_after = 4; oc.kd_clone_max = len(pi); oc.kd_clone_iter = 200
+    s2 = R.kinodyn_solve_host(N, lb[pi], ub[pi], cost[pi], x0[pi], dt, mass, Ib, Ibi, consts.mu, oc)
+    from_clone = (s2["status"] == 3) & (s2["iters"] > 3 * oc.max_iter)
+    print("   posed again with max_iter 25 and clones after 4 rounds: status %s, %d certificates from clone slots" % (np.bincount(s2["status"], minlength=5), from_clone.sum()))
+    assert from_clone.sum() >= 1
+    Wc = cr.Worst()
+    for i in np.nonzero(s2["status"] == 3)[0]:
+        b = pi[i]
+        res = cr.kd_certificate(s2["x"][i], s2["lam_g"][i], lb[b], ub[b], N, dt, mass, Ib, Ibi, consts.mu, oc.feas_rho, oc.tol, feas_cert=oc.feas_cert, kkt0=s2["kkt"][i, 0])
+        assert cr.failed(res) == [], (b, res)
+        assert np.array_equal(s2["x"][i][:12], lb[b][:12]) and s2["kkt"][i, 1] <= oc.tol * 1.0001      # (the original's fixed initial state)
+        Wc.add(res)
+    print("   clone-slot certificates:", Wc)
     o.feas_phase = 0      # ... and without the phase those members end undecided
     s0 = R.kinodyn_solve_host(N, lb, ub, cost, x0, dt, mass, Ib, Ibi, consts.mu, o)
     assert (s0["status"][phase] != 0).all() and np.isin(s0["status"], (1, 2)).sum() > (~ok & ~cert).sum()

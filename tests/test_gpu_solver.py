@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import certificate_reference as cr
 from conftest import GOLDEN, lc
 
 pytestmark = pytest.mark.gpu
@@ -105,6 +106,9 @@ def test_solver_other_horizons_and_limits(oracle_mod):
         for b in np.nonzero(cert)[0]:      # the certificate: equality rows met, a positive violation of the inequality rows (1-norm above feas_cert)
             g = O.g(r["x"][b], P[b]); lb, ub = O.bounds(P[b]); eq = lb == ub
             assert np.abs(g[eq] - lb[eq]).max() <= 1e-6 and np.maximum(np.maximum(lb - g, g - ub), 0.0)[~eq].sum() > 1e-4
+            o = L.default_opts()      # ... and it is a KKT point of the elastic problem with the multipliers returned (tests/certificate_reference.py)
+            res = cr.srbm_certificate(O, r["x"][b], P[b], r["lam_g"][b], o.feas_rho, o.tol, feas_cert=o.feas_cert, kkt0=r["kkt"][b, 0])
+            assert cr.failed(res) == [], (N, b, res)
         L.close()
     L = capi.LandingLib(100, device=0)
     P, X0, _, _ = lc("problem").make_batch(1, 100, 0.6, seed=4)
@@ -290,7 +294,11 @@ def test_n20_production_problem_full_batch(libs, oracle_mod, law, min_conv):
     <= 1e-6 under the oracle for EVERY certificate; a stationary violation that is not such a point is LANDING_STALLED (4), counted as undecided
     here; no certified member may be one that the plain iteration (no phase) solves within 150 iterations (`lost == 0`); at most 0.5 % undecided.
     The phase now works the way IPOPT's restoration phase does (landing_nlp.h: feas_back, feas_max, feas_ret_push, feas_delta_dec, feas_polish, feas_resume).
-    CPU port on these very batches: main 1020 converged + 4 certified, datagen 994 + 28 + 2 stalled; 16 x 1024 per law on the GPU: profiles/r06_soak_n20_*.json."""
+    CPU port on these very batches: main 1020 converged + 4 certified, datagen 994 + 28 + 2 stalled; 16 x 1024 per law on the GPU: profiles/r06_soak_n20_*.json.
+    EVERY certificate is also held to the elastic problem's KKT conditions with the multipliers the kernel returns (tests/certificate_reference.py: equality rows E, J' lam = 0 S,
+    |lam| <= rho and signs B, |lam| = rho on the violated rows V, complementarity inside the bounds C, the reported violation P; bounds from the stop test).  MI355X, worst
+    values: main, 4 certificates: E 5.8e-7  S 1.0e-9  rho - |lam| 2.2e-4  C 1.0e-7; datagen, 28 certificates: E 8.5e-7  S 8.5e-8  rho - |lam| 4.6e-4  C 1.0e-7 (bounds: 1e-6,
+    1e-6, ten times the value, 1e-6)."""
     N, B = 20, 1024
     Pm = lc("problem")
     O = oracle_mod.Oracle(N)
@@ -301,6 +309,7 @@ def test_n20_production_problem_full_batch(libs, oracle_mod, law, min_conv):
     print("N=20 production grid, law %s: %d / %d converged, iterations mean %.1f p99 %.0f max %d; v_z of the others: %s" %
           (law, ok.sum(), B, r["iters"][ok].mean(), np.percentile(r["iters"][ok], 99), r["iters"][ok].max(), np.round(np.sort(qd[~ok, 5]), 2)[:12]))
     cert = r["status"] == 3
+    worst = cr.Worst()
     print("   certified locally infeasible: %d (largest violation %.1e .. %.1e), stalled: %d, undecided otherwise: %d" % (
         cert.sum(), r["kkt"][cert, 0].min() if cert.any() else 0, r["kkt"][cert, 0].max() if cert.any() else 0, (r["status"] == 4).sum(), np.isin(r["status"], (1, 2)).sum()))
     assert ok.mean() >= min_conv, f"{ok.sum()}/{B}"
@@ -314,6 +323,11 @@ def test_n20_production_problem_full_batch(libs, oracle_mod, law, min_conv):
         assert np.abs(g[eq] - lbb[eq]).max() <= 1e-6 * 1.0001
         viol = np.maximum(np.maximum(lbb - g, g - ubb), 0.0)
         assert abs(viol.max() - r["kkt"][b, 0]) <= 1e-9 and viol.sum() > 1e-4
+        res = cr.srbm_certificate(O, r["x"][b], P[b], r["lam_g"][b], o.feas_rho, o.tol, feas_cert=o.feas_cert, kkt0=r["kkt"][b, 0])      # ... a stationary point of the violation,
+        assert cr.failed(res) == [], (b, res)                                                                                           # with multipliers that prove it (E, S, B, V, C, P)
+        assert r["kkt"][b, 1] <= o.tol * 1.0001      # (kkt[1] at status 3: the elastic problem's dual infeasibility, landing_nlp.h d_kkt)
+        worst.add(res)
+    print("   certificates held to the elastic problem's KKT conditions:", worst)
     o.feas_phase = 0      # ... and without the phase the certified members end undecided (NUMERICAL / MAX_ITER) or converge only after hundreds of
     r0 = libs[N].solve_host(P, X0, o)      # iterations; whoever the jam rule (feas_jam) never touched converges to the same bits
     ok0 = r0["status"] == 0

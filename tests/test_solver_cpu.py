@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import certificate_reference as cr
 from conftest import GOLDEN, ROOT, lc
 
 PKG = os.path.join(ROOT, "landing-controller_amd")
@@ -208,6 +209,9 @@ def test_feasibility_phase_rescues_or_certifies(oracle_mod):
             viol = np.maximum(np.maximum(lb - g, g - ub), 0.0)
             assert np.abs(g[eq] - lb[eq]).max() <= 1e-6 and abs(viol.max() - r1["kkt"][b, 0]) <= 1e-12 and viol.sum() > 1e-4
             assert np.abs(r1["x"][b] - c1["x"][b]).max() <= 1e-6             # the CPU port ends at the same elastic KKT point
+            for r_ in (r1, c1):      # ... which IS one, with the multipliers each returns (tests/certificate_reference.py: E, S, B, V, C, P)
+                res = cr.srbm_certificate(O, r_["x"][b], P[b], r_["lam_g"][b], o.feas_rho, o.tol, feas_cert=o.feas_cert, kkt0=r_["kkt"][b, 0], kkt0_atol=1e-12)
+                assert cr.failed(res) == [], (b, res)
     L.close()
 
 
@@ -236,6 +240,8 @@ def test_feas_jam_and_stat_cut_the_production_tail(emu_lib, oracle_mod):
         g = O.g(new["x"][b], P[b]); lb, ub = O.bounds(P[b]); eq = lb == ub
         viol = np.maximum(np.maximum(lb - g, g - ub), 0.0)
         assert np.abs(g[eq] - lb[eq]).max() <= 1e-6 * 1.0001 and abs(viol.max() - new["kkt"][b, 0]) <= 1e-9 and viol.sum() > 1e-4      # (round 6: status 3 = elastic KKT point, nothing else)
+        res = cr.srbm_certificate(O, new["x"][b], P[b], new["lam_g"][b], 1000.0, 1e-6, kkt0=new["kkt"][b, 0])      # ... with multipliers that prove it
+        assert cr.failed(res) == [], (b, res)
     m = 131      # certified early by the new rules (416 iterations without them); member 40 is another one, but behind its first early return (round 6) it passes through a
     assert new["status"][m] == 3 and new["iters"][m] < 200 and old["iters"][m] > 300      # region with pr ~ 50 where the kernel's and the port's roundings part ways
     L = lc("capi").LandingLib(N, lib_path=emu_lib)
@@ -244,6 +250,8 @@ def test_feas_jam_and_stat_cut_the_production_tail(emu_lib, oracle_mod):
     g = L.solve_host(P[m:m + 1], X0[m:m + 1], o)
     assert g["status"][0] == 3 and g["iters"][0] == new["iters"][m]
     assert np.abs(g["x"][0] - new["x"][m]).max() <= 1e-5 and abs(g["kkt"][0, 0] - new["kkt"][m, 0]) <= 1e-7
+    assert (o.feas_rho, o.tol, o.feas_cert) == (1000.0, 1e-6, 1e-4)      # (what the port's certificates were held to above) ... and the kernel's own multipliers prove the same
+    assert cr.failed(cr.srbm_certificate(O, g["x"][0], P[m], g["lam_g"][0], o.feas_rho, o.tol, feas_cert=o.feas_cert, kkt0=g["kkt"][0, 0])) == []
     L.close()
 
 
@@ -276,8 +284,12 @@ def test_round6_phase_rules_kernel_follows_port(emu_lib, oracle_mod):
             assert old["iters"][0] >= 3 * c["iters"][0]
         if status == 3:
             assert np.abs(gg[eq] - lb[eq]).max() <= 1e-6 and abs(viol.max() - g["kkt"][0, 0]) <= 1e-9 and viol.sum() > 1e-4
+        res = [cr.srbm_certificate(O, r_["x"][0], P[m], r_["lam_g"][0], o.feas_rho, o.tol, feas_cert=o.feas_cert, kkt0=r_["kkt"][0, 0]) for r_ in (g, c)] if status in (3, 4) else None
+        if status == 3:
+            assert cr.failed(res[0]) == [] and cr.failed(res[1]) == [], res
         if status == 4:
             assert abs(viol.max() - g["kkt"][0, 0]) <= 1e-9
+            assert cr.failed(res[0]) != [] and cr.failed(res[1]) != []      # a stalled member is no certificate: the check tells the two apart
     L.close()
 
 
