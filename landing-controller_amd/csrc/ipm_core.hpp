@@ -63,6 +63,31 @@ __device__ __forceinline__ void block_top4(double (&t)[4], double* red) {
   __syncthreads();
 }
 
+// ---- sum over an aligned group of 8 lanes, valid in the group's FIRST lane only (the other lanes end with partial sums) ------------------
+// The first lane adds what the butterfly v += xor 1, v += xor 2, v += xor 4 adds there, in the same order.  On the device the partners share
+// a 16-lane row, so the values travel by DPP inside the vector ALU (two 32-bit moves per double): quad_perm for distance 1 and 2, a row shift
+// by 4 for the last level, which only the first lane needs.  __shfl_xor is ds_bpermute: address, issue and a wait on the LDS counter per
+// level.  The host emulation keeps __shfl_xor.  (The butterflies of block_reduce / block_top4 above were moved to DPP the same way and
+// measured 0.5 % SLOWER on the headline, dual and line-search phases up by 0.001 ms each: they stay as they are)
+#if defined(__HIP_DEVICE_COMPILE__)
+template <int CTRL>
+__device__ __forceinline__ double dpp_move(double v) {      // (lanes whose source lies outside the row keep their own value)
+  const int lo = __builtin_amdgcn_update_dpp(__double2loint(v), __double2loint(v), CTRL, 0xf, 0xf, false);
+  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(v), __double2hiint(v), CTRL, 0xf, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
+enum { DPP_QUAD_XOR1 = 0xb1, DPP_QUAD_XOR2 = 0x4e, DPP_ROW_SHL4 = 0x104 };      // quad_perm:[1,0,3,2], quad_perm:[2,3,0,1], row_shl:4 (lane i reads lane i + 4)
+#endif
+__device__ __forceinline__ double lane_sum8_head(double v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  v += dpp_move<DPP_QUAD_XOR1>(v); v += dpp_move<DPP_QUAD_XOR2>(v);
+  return v + dpp_move<DPP_ROW_SHL4>(v);
+#else
+  v += __shfl_xor(v, 1); v += __shfl_xor(v, 2);
+  return v + __shfl_xor(v, 4);
+#endif
+}
+
 // fp64 matrix-core accumulator tile (v_mfma_f64_16x16x4: 4 doubles per lane)
 typedef double f64x4 __attribute__((vector_size(32)));
 

@@ -343,20 +343,26 @@ __device__ __forceinline__ P uni_ptr(P q) {
   return (P)((unsigned long long)(unsigned)uni((int)(unsigned)a) | ((unsigned long long)(unsigned)uni((int)(unsigned)(a >> 32)) << 32));
 }
 __device__ __forceinline__ double uni(double v) { return __hiloint2double(uni(__double2hiint(v)), uni(__double2loint(v))); }
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef const unsigned long long __attribute__((address_space(1)))* landing_gptr_u;
+#else
+typedef const unsigned long long* landing_gptr_u;
+#endif
 struct SweepCtx {
   landing_gptr JH, SR, Gr, Cd;      // [J | H | Hc] (contiguous), [sigma | rho] (contiguous), g, gradient of the running cost
-  const unsigned long long* ctab; const unsigned long long* ccomb;
+  landing_gptr_u ctab, ccomb;       // term and combine tables of the stage types that are not LDS-resident (global_load: a flat load would also count on the LDS counter)
   int c_ml, c_mid, rc_on, ng;
 };
 __device__ __forceinline__ SweepCtx sweep_ctx() {
   const Lds& S = SH;
   SweepCtx X;
   X.JH = uni_ptr((landing_gptr)S.M.J); X.SR = uni_ptr((landing_gptr)S.M.sig); X.Gr = uni_ptr((landing_gptr)S.M.g); X.Cd = uni_ptr((landing_gptr)S.M.cond);
-  X.ctab = uni_ptr(S.ctab); X.ccomb = uni_ptr(S.ccomb);
+  X.ctab = uni_ptr((landing_gptr_u)S.ctab); X.ccomb = uni_ptr((landing_gptr_u)S.ccomb);
   X.c_ml = uni(S.c_ml); X.c_mid = uni(S.c_mid); X.rc_on = uni(S.rc_on); X.ng = uni(S.L.ng);
   return X;
 }
-struct AsmRegs { double jh[7], sr, g, rc; int tp; };      // (tp: the stage's type, uniform)
+static_assert(ATAB_LTMAX == ATAB_TB, "a thread's terms of a stage are ONE batch: its words travel in AsmRegs");
+struct AsmRegs { double jh[7], sr, g, rc; int tp; unsigned long long tw[ATAB_TB], cw; };      // (tp: the stage's type, uniform; tw, cw: the thread's term words and combine word, live from asm_copy on)
 // (1) coalesced loads of stage k's nonzeros (one per segment), sigma / rho of its rows, the residual of its dynamics rows; nothing is consumed here
 // (the segment bases and the type of the stage are the one thing the hooks still read from LDS per stage: segb, one round trip)
 __device__ __forceinline__ void asm_issue(int k, const SweepCtx& X, AsmRegs& R) {
@@ -372,33 +378,39 @@ __device__ __forceinline__ void asm_issue(int k, const SweepCtx& X, AsmRegs& R) 
   R.rc = 0.0;
   if (X.rc_on) R.rc = X.Cd[(size_t)k * RCG + (tid < RCG ? tid : 0)];
 }
-// (2) ... into LDS; a barrier follows before asm_terms
-__device__ __forceinline__ void asm_copy(const AsmRegs& R) {
+// (2) ... into LDS; a barrier follows before asm_terms.  The thread's packed words of the stage's TYPE (terms: asm_terms, partial-sum slots:
+// asm_combine) are fetched here, one block step early, into the registers the copied values leave: they depend on the type alone, and read
+// behind the barrier they were a round trip of their own in front of the operand reads, which need them for their addresses
+__device__ __forceinline__ void asm_copy(const SweepCtx& X, int nb, AsmRegs& R) {
   Lds& S = SH;
   const int tid = threadIdx.x;
 #pragma unroll
   for (int sgm = 0; sgm < 7; ++sgm) if (tid < ASM_SEG_LEN[sgm]) S.jhl[ASM_SEG_POS[sgm] + tid] = R.jh[sgm];
   if (tid < 208) S.jhl[CX_SR + tid] = R.sr;
+  // b of copy `nb` (no term writes that column; the copy is the NEXT stage's) and the gradient of the running cost (w order X, c, f: added to gamma
+  // when its tile is fetched, which every wave is past): stored here, so that every loaded value has left its register before the words arrive
+  if (tid < 12) { const int i = tid; S.Ah[nb * (12 * YS) + (i < 6 ? i : (i < 9 ? i + 3 : i - 3)) * YS + (YS - 1)] = -R.g; }
+  if (tid < RCG) S.rcl[tid] = R.rc;
+  if (R.tp == X.c_mid) {
+#pragma unroll
+    for (int u = 0; u < ATAB_TB; ++u) R.tw[u] = S.atab_mid[u * SOLVER_THREADS + tid];
+    R.cw = S.acomb_mid[tid];
+  } else {
+    const landing_gptr_u gt = X.ctab + (size_t)R.tp * X.c_ml * SOLVER_THREADS;
+#pragma unroll
+    for (int u = 0; u < ATAB_TB; ++u) R.tw[u] = gt[u * SOLVER_THREADS + tid];
+    R.cw = X.ccomb[R.tp * SOLVER_THREADS + tid];
+  }
 }
 // (3) products and stores: G and gamma (dead since the tile fetch of the running elimination), A^ / b of copy `nb`.  ATAB_TB terms
-// at a time: codes, then all operands, then the arithmetic and the stores -- three LDS round trips per batch instead of three per term
-__device__ __forceinline__ void asm_terms(const SweepCtx& X, int nb, const AsmRegs& R) {
+// at a time: all operands (the codes came with asm_copy), then the arithmetic and the stores
+__device__ __forceinline__ void asm_terms(int nb, const AsmRegs& R) {
   Lds& S = SH;
-  const int tid = threadIdx.x, LT = X.c_ml, tp = R.tp;
   char* const lds0 = reinterpret_cast<char*>(&S);
   const unsigned ahoff = nb ? (unsigned)(12 * YS * sizeof(double)) : 0u;
-  const bool mid = (tp == X.c_mid);
-  const unsigned long long* gt = X.ctab + (size_t)tp * LT * SOLVER_THREADS;
   double acc = 0.0;
-  for (int j0 = 0; j0 < LT; j0 += ATAB_TB) {
-    unsigned long long t[ATAB_TB];
-    if (mid) {
-#pragma unroll
-      for (int u = 0; u < ATAB_TB; ++u) t[u] = S.atab_mid[(j0 + u) * SOLVER_THREADS + tid];
-    } else {
-#pragma unroll
-      for (int u = 0; u < ATAB_TB; ++u) t[u] = gt[(j0 + u) * SOLVER_THREADS + tid];
-    }
+  {
+    const unsigned long long (&t)[ATAB_TB] = R.tw;
     double a[ATAB_TB], b[ATAB_TB], c[ATAB_TB];
 #pragma unroll
     for (int u = 0; u < ATAB_TB; ++u) {
@@ -413,14 +425,11 @@ __device__ __forceinline__ void asm_terms(const SweepCtx& X, int nb, const AsmRe
       acc = (dd & 1u) ? acc : 0.0;
     }
   }
-  if (tid < 12) { const int i = tid; S.Ah[nb * (12 * YS) + (i < 6 ? i : (i < 9 ? i + 3 : i - 3)) * YS + (YS - 1)] = -R.g; }
-  if (tid < RCG) S.rcl[tid] = R.rc;      // gradient of the running cost (w order X, c, f): added to gamma when its tile is fetched
 }
 // (4) behind the next barrier: the destinations whose terms more than one thread summed
-__device__ __forceinline__ void asm_combine(const SweepCtx& X, int nb, const AsmRegs& R) {
+__device__ __forceinline__ void asm_combine(int nb, const AsmRegs& R) {
   Lds& S = SH;
-  const int tid = threadIdx.x, tp = R.tp;
-  const unsigned long long code = tp == X.c_mid ? S.acomb_mid[tid] : X.ccomb[tp * SOLVER_THREADS + tid];
+  const unsigned long long code = R.cw;
   const unsigned lo = (unsigned)code, dd = (unsigned)(code >> 32);
   const int n = (int)(lo & 7u);
   if (n > 0) {
@@ -705,7 +714,7 @@ __device__ __forceinline__ bool stage_eliminate(const StageLanes<NU>& Z, const S
   constexpr int SC = NU == 24 ? 3 : 1;
   AsmRegs nxt;
   const bool more = k > 0;                               // (uniform)
-#define ASM_HOOK(step) do { if constexpr (SC == (step)) { if (more) asm_copy(nxt); } if constexpr (SC + 1 == (step)) { if (more) asm_terms(X, cb ^ 1, nxt); } if constexpr (SC + 2 == (step)) { if (more) asm_combine(X, cb ^ 1, nxt); } } while (0)
+#define ASM_HOOK(step) do { if constexpr (SC == (step)) { if (more) asm_copy(X, cb ^ 1, nxt); } if constexpr (SC + 1 == (step)) { if (more) asm_terms(cb ^ 1, nxt); } if constexpr (SC + 2 == (step)) { if (more) asm_combine(cb ^ 1, nxt); } } while (0)
   unsigned key = pivot_block_step<0>(T, Z), kq;
 #define KEY_MAX(e) do { kq = (e); key = kq > key ? kq : key; } while (0)
   if (more) asm_issue(k - 1, X, nxt);
@@ -814,11 +823,11 @@ __device__ __noinline__ bool riccati_backward(double delta) {
   {   // the only exposed assembly of the sweep
     AsmRegs first;
     asm_issue(N - 1, X, first);
-    asm_copy(first);
+    asm_copy(X, (N - 1) & 1, first);
     __syncthreads();
-    asm_terms(X, (N - 1) & 1, first);
+    asm_terms((N - 1) & 1, first);
     __syncthreads();
-    asm_combine(X, (N - 1) & 1, first);
+    asm_combine((N - 1) & 1, first);
   }
   __syncthreads();
   // ---- per stage: G + T^T P T, elimination of the controls: P_k, p_k, gains -> record k; the assembly of stage k - 1 rides along
@@ -875,17 +884,23 @@ __device__ __noinline__ void forward_pass() {
   Lds& S = SH;
   const Layout& L = S.L;
   const MemberMem& M = S.M;
-  const int N = L.N, tid = threadIdx.x, NT = blockDim.x;
+  const int N = uni(L.N), tid = threadIdx.x, NT = blockDim.x;
   double* sg = S.G;                    // sigma_k, k = 0..N  at sg[24 k]           (N <= SOLVER_NMAX = 96: 2328 of the 2352 doubles of G)
   double* buf = S.jhl;                 // two stage slots of RIC_FWDN doubles: the assembler's copy of a stage's nonzeros (free here) and A1
   double* buf1 = S.A1;
   static_assert(24 * (SOLVER_NMAX + 1) <= 48 * GS && RIC_FWDN <= NZ_TOT + RUNC && RIC_FWDN <= XCH * 2, "forward scratch fits");
   auto slot = [&](int k) { return (k & 1) ? buf1 : buf; };
-  auto fetch = [&](int k, double (&r)[3]) {
-    landing_gptr rec = (landing_gptr)(M.ric + (size_t)(k < N ? k : N - 1) * RIC_STRIDE + RIC_FWD0);   // global_load: a flat load would also tie up the LDS counter
+  // The record base of the sweep lives in scalar registers (uniform_record, as in riccati_backward): the prefetch address of a stage is scalar
+  // arithmetic on it, the member context in LDS is not read inside the loop.  global_load: a flat load would also tie up the LDS counter
+  const landing_gptr fwd0 = (landing_gptr)uniform_record(M.ric) + RIC_FWD0;
+  int fe[3];
 #pragma unroll
-    for (int j = 0; j < 3; ++j) { const int e = tid + j * 256; r[j] = rec[e < RIC_FWDN ? e : RIC_FWDN - 1]; }   // unconditional (clamped):
-  };                                                                                                     // the memory counter stays countable
+  for (int j = 0; j < 3; ++j) { const int e = tid + j * 256; fe[j] = e < RIC_FWDN ? e : RIC_FWDN - 1; }
+  auto fetch = [&](int k, double (&r)[3]) {
+    const landing_gptr rec = fwd0 + (size_t)(k < N ? k : N - 1) * RIC_STRIDE;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) r[j] = rec[fe[j]];      // unconditional (clamped): the memory counter stays countable
+  };
   auto stash = [&](int k, const double (&r)[3]) {
     double* b = slot(k);
 #pragma unroll
@@ -896,18 +911,29 @@ __device__ __noinline__ void forward_pass() {
   fetch(0, r0); fetch(1, r1); fetch(2, r2); fetch(3, r3);
   stash(0, r0); fetch(4, r0);
   __syncthreads();
+  // Lane constants of the recursion: lane (r, j) sums entries 3j..3j+2 of row r of [Mt; -K_c]; a stage reads its row, sigma_k AND the bias of
+  // its row in one batch of LDS reads, the 8-lane sum stays in the vector ALU (lane_sum8_head) and the two cases of a row (state row: bias +
+  // sum, c+ row: -(bias + sum), 0 behind the last stage) are selects on the loaded value -- one trip through the LDS pipe per stage, not six
+  const int fr = tid >> 3, fj = tid & 7;
+  const bool frow = tid < 192, fstate = fr < 12, fhead = frow && fj == 0;
+  const int f_row = (fstate ? 312 + fr * 24 : (fr - 12) * 24) + 3 * fj;      // slot layout: [0,288) K rows of c+ | [288,312) kappa | [312,600) Mt | [600,612) mv
+  const int f_bias = fstate ? 600 + fr : 300 + (fr - 12);
   auto stage = [&](int k, double (&rn)[3]) {
     // rn holds stage k+1 (loaded four stages ago): hand it to LDS, refill it with stage k+5
     if (k < N) {
-      const double* b = slot(k);                 // [0,288) K rows of c+ | [288,312) kappa | [312,600) Mt | [600,612) mv
+      const double* b = slot(k);
       const bool lastk = (k == N - 1);
-      if (tid < 192) {
-        const int r = tid >> 3, j = tid & 7;
-        const double* row = (r < 12) ? b + 312 + r * 24 : b + (r - 12) * 24;
-        const double* sk = sg + 24 * k;
-        double acc = row[3 * j] * sk[3 * j] + row[3 * j + 1] * sk[3 * j + 1] + row[3 * j + 2] * sk[3 * j + 2];
-        acc += __shfl_xor(acc, 1); acc += __shfl_xor(acc, 2); acc += __shfl_xor(acc, 4);
-        if (j == 0) sg[24 * (k + 1) + r] = (r < 12) ? b[600 + r] + acc : (lastk ? 0.0 : -(b[300 + (r - 12)] + acc));
+      if (frow) {
+        const double* row = b + f_row;
+        const double* sk = sg + 24 * k + 3 * fj;
+        double bias = b[f_bias];
+        double prod = row[0] * sk[0] + row[1] * sk[1] + row[2] * sk[2];
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(bias), "+v"(prod));      // the bias arrives with the products: without this the compiler sinks its read behind the sum, into the storing lanes' branch
+#endif
+        const double acc = lane_sum8_head(prod);
+        const double v = bias + acc;
+        if (fhead) sg[24 * (k + 1) + fr] = fstate ? v : (lastk ? 0.0 : -v);
       }
     }
     stash(k + 1, rn);

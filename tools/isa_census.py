@@ -66,6 +66,7 @@ def count_ops(ops):
         "fp64_valu": fp64,
         "lds_read": cnt(lambda o: o.startswith("ds_read") or o.startswith("ds_load")),
         "lds_write": cnt(lambda o: o.startswith("ds_write") or o.startswith("ds_store")),
+        "ds_bpermute": cnt(lambda o: o.startswith("ds_bpermute") or o.startswith("ds_permute") or o.startswith("ds_swizzle")), "dpp": cnt(lambda o: o.endswith("_dpp")),
         "flat_load": cnt(lambda o: o.startswith("flat_load")), "flat_store": cnt(lambda o: o.startswith("flat_store")),
         "global_load": cnt(lambda o: o.startswith("global_load")), "global_store": cnt(lambda o: o.startswith("global_store")),
         "scratch": cnt(lambda o: o.startswith("scratch_") or o.startswith("buffer_")),
@@ -82,10 +83,35 @@ def count_ops(ops):
 LOOP_HEAD = re.compile(r"^(\.LBB\d+_\d+):\s*; =>This (?:Inner )?Loop Header: Depth=1")
 
 
+BLOCK_HEAD = re.compile(r"^(?:(\.LBB\d+_\d+):|; %bb\.\d+:)(.*)$")
+
+
+def loop_blocks(body, label):
+    """mnemonics of ALL blocks of the loop with header `label`, wherever the compiler laid them out: the header's block and every block
+    commented `in Loop: Header=<label>` (labelled or fall-through), the loops nested in it included.  This also covers a loop whose latch block sits in FRONT of the header and
+    falls through into it (the forward recursion of forward_pass), which has no branch back to the header label."""
+    heads = {label[2:]}      # the loop's header and the headers of the loops nested in it (commented `Parent Loop <outer header>`)
+    for line in body:
+        bm = BLOCK_HEAD.match(line)
+        if bm and bm.group(1) and any(("Parent Loop " + h + " ") in bm.group(2) + " " for h in list(heads)):
+            heads.add(bm.group(1)[2:])
+    ops, inside = [], False
+    for line in body:
+        bm = BLOCK_HEAD.match(line)
+        if bm:
+            inside = (bm.group(1) or "..")[2:] in heads or any(("Header=" + h + " ") in bm.group(2) + " " for h in heads)
+        elif inside:
+            mm = INSTR.match(line)
+            if mm:
+                ops.append(mm.group(1))
+    return ops
+
+
 def barrier_loops(body):
-    """The outermost loops of a function that hold a barrier (the stage loops of the backward sweep), each counted twice: `body` = from the
-    loop's header label to its last back branch, `with_tail_blocks` = that plus the blocks of the loop the compiler laid out behind the back
-    branch (blocks commented `in Loop: Header=<label>`; they are executed inside the loop as well)."""
+    """The outermost loops of a function that hold a barrier (the stage loops of the backward sweep, the forward recursion).  `all_blocks` =
+    every block of the loop (loop_blocks).  Where the loop has a branch back to its header label it is also counted as before: `body` = from
+    the loop's header label to its last back branch, `with_tail_blocks` = that plus the blocks of the loop the compiler laid out behind the
+    back branch (blocks commented `in Loop: Header=<label>`; they are executed inside the loop as well)."""
     out = []
     for i, line in enumerate(body):
         m = LOOP_HEAD.match(line)
@@ -94,6 +120,9 @@ def barrier_loops(body):
         label = m.group(1)
         back = max((j for j in range(i + 1, len(body)) if re.match(r"^\ts_c?branch\S*\s+" + re.escape(label) + r"\s*$", body[j].split(";")[0].rstrip())), default=None)
         if back is None:
+            every = loop_blocks(body, label)
+            if "s_barrier" in every:
+                out.append({"header": label, "all_blocks": count_ops(every)})
             continue
         inner = [mm.group(1) for mm in (INSTR.match(b) for b in body[i:back + 1]) if mm]
         if "s_barrier" not in inner:
@@ -110,7 +139,7 @@ def barrier_loops(body):
                 if mm:
                     tail.append(mm.group(1))
             j += 1
-        out.append({"header": label, "body": count_ops(inner), "with_tail_blocks": count_ops(inner + tail)})
+        out.append({"header": label, "body": count_ops(inner), "with_tail_blocks": count_ops(inner + tail), "all_blocks": count_ops(loop_blocks(body, label))})
     return out
 
 
@@ -178,6 +207,11 @@ def main():
     for f, row in sorted(res.items()):
         print("%-58s" % f[:58] + "".join(" %9s" % ("-" if row[k] is None else row[k]) for k in keys))
         for lp in row.get("barrier_loops", []):
+            ab = lp["all_blocks"]
+            print("    loop %s, all its blocks: %d instructions, %d barriers, LDS reads %d / writes %d, ds_bpermute %d, DPP %d, s_waitcnt %d, branches %d, global loads %d" % (
+                lp["header"], ab["instructions"], ab["barrier"], ab["lds_read"], ab["lds_write"], ab["ds_bpermute"], ab["dpp"], ab["s_waitcnt"], ab["branch"], ab["global_load"]))
+            if "body" not in lp:
+                continue
             print("    loop %s: %d instructions to the back branch, %d with the loop's blocks behind it; clock reads %d, calls %d, scratch %d" % (
                 lp["header"], lp["body"]["instructions"], lp["with_tail_blocks"]["instructions"], lp["with_tail_blocks"]["clock"], lp["with_tail_blocks"]["call"], lp["with_tail_blocks"]["scratch"]))
         if "kernel_descriptor" in row:
