@@ -814,6 +814,53 @@ int landing_pipeline_21_on(int device, int N, int B, const double* Xref, const d
                            const double* Ib, const double* Ib_inv, const landing_pipeline_opts* opts,
                            double* x, double* f, double* lam_g, int* status, int* iters, double* kkt, double* pair_in, double* pair_out, int* n_kept);
 
+/* ---- actuator audit of refined trajectories, and the training pairs behind it (csrc/actuator_kernels.hip) ------------------------------------
+ * The reference's production callers look at a refined trajectory before they keep it: utilities_landing/plot_results.m:12-39 computes joint torques,
+ * joint velocities and motor voltages and draws them against tauMax and batteryV (:120-136); generate_training_data_automated.m:200-218 asks "Save
+ * trajectory for training?" behind that figure.  The voltage limit is NOT a row of the refinement NLP (landing_optimization.m:191-199 carries it
+ * commented out, "ignored, because motors experiencing negative work"), so a converged member can ask for more than the battery gives.  The audit is
+ * that look per member, on the device, for x = [X (12 x (N+1)); jpos (12 x N); U (24 x N)] as the refinement returns it and the grid dt [N]:
+ *   tau[k, leg] = J_f(jpos_k)' (-R_world_to_body(rpy_k) f_k,leg)       plot_results.m:14-22 (get_foot_jacobians_mc.m:12-24, rpyToRotMat_xyz.m:2; the
+ *                                                                       torque rows of landing_kinodyn_rows_batch); leg lengths from the context's model
+ *   jvel[k]     = (jpos[k+1] - jpos[k]) / dt[k] for k = 0 .. N-2, jvel[N-1] = 0      plot_results.m:27-29: the script's FORWARD difference with its zero
+ *                                                                       last column -- not the backward difference of generate_training_data_single.m:180
+ *   volt[k]     = tau[k] / gr / (1.5 kt) * Rm + jvel[k] * gr * kt * 2                 plot_results.m:31-38
+ *   landing_actuator_model         gear ratios, torque constants, winding resistances, joint torque limits (abad / hip / knee) and the battery voltage;
+ *                                  landing_actuator_model_mc3d: 6, 6, 9.33 | 0.05 | 0.173 | 3.0 gr = 18, 18, 27.99 | 24 V (get_robot_params.m:109-115,
+ *                                  get_robot_model.m:237-242)
+ *   landing_actuator_screen        the limits a member has to hold to be kept; a limit <= 0 is not screened.  drive_only = 1: volt_max applies to the
+ *                                  samples with tau jvel > 0 only (the reference's stated criterion).  Default: volt_max = 24, drive_only = 1, the others off.
+ *   d_tau, d_jvel, d_volt          [B][N][12], each may be NULL
+ *   d_summary [B][LANDING_AUDIT_NSUM]   0 peak |tau| / tau_max   1 peak |jvel|   2 peak |volt|   3 peak |volt| over the samples with tau jvel > 0 (0 if
+ *                                  there is none)   4 max tau jvel   5 min tau jvel   6 number of samples with |volt| > battery_v   7 the same count over
+ *                                  the samples with tau jvel > 0.  A sample is one (knot, joint); all N x 12 count.  No comparison with a NaN holds: NaN samples are
+ *                                  left out of the peaks and counts.
+ *   d_where [B][4]                 knot and joint (0 .. 11) of peak 2, then of peak 3; -1, -1 for a peak that does not exist; of equal peaks the one
+ *                                  with the lowest 12 knot + joint
+ *   d_ok [B]                       1 if every enabled limit holds (volt_max against entry 3 with drive_only, else entry 2; tau_ratio_max against 0;
+ *                                  jvel_max against 1), else 0; 0 for a member with a non-finite value in x, dt, tau, jvel or volt
+ * A member's outputs depend on that member alone.  d_dt + b * dt_stride is member b's grid: dt_stride = 0 is one grid for all, else dt_stride >= N.
+ * model / screen NULL: the defaults above.  B = 0 returns 0.  LANDING_E_ARG for NULL dt, x, summary, where or ok, for another dt_stride, for a
+ * context with N outside 2 .. 64 or without a model whose legs follow the quadruped's numbering.  Queued on `stream`, no synchronisation inside.
+ *   landing_actuator_audit_host    the same on host arrays (blocking)
+ *   landing_pipeline_screened_pairs_batch   the chain's pair writer behind the screen: final status of every member from the chain's d_status3 [B][3]
+ *                                  (landing_pipeline_final_status of columns 1, 2), the audit with dt read from the members' p, and the pairs of the members
+ *                                  with final status 0 AND ok, through the scan and pair kernels of landing_training_pairs_batch (same outputs).  No host
+ *                                  read.  The statuses stay what the solvers said: a rejection shows in d_ok and d_summary only.                        */
+#define LANDING_AUDIT_NSUM 8
+typedef struct { double gr[3], kt[3], Rm[3], tau_max[3], battery_v; } landing_actuator_model;
+typedef struct { double volt_max, tau_ratio_max, jvel_max; int drive_only; } landing_actuator_screen;
+void landing_actuator_model_mc3d(landing_actuator_model* m);
+void landing_actuator_screen_default(landing_actuator_screen* s);
+int landing_actuator_audit_batch(landing_ctx* ctx, int B, const double* d_dt, int dt_stride, const double* d_x_kd, const landing_actuator_model* model,
+                                 const landing_actuator_screen* screen, double* d_tau, double* d_jvel, double* d_volt, double* d_summary, int* d_where,
+                                 int* d_ok, void* stream);
+int landing_actuator_audit_host(landing_ctx* ctx, int B, const double* dt, int dt_stride, const double* x_kd, const landing_actuator_model* model,
+                                const landing_actuator_screen* screen, double* tau, double* jvel, double* volt, double* summary, int* where, int* ok);
+int landing_pipeline_screened_pairs_batch(landing_ctx* ctx, int B, const double* d_p, const double* d_x_kd, const int* d_status3,
+                                          const landing_actuator_model* model, const landing_actuator_screen* screen, double* d_summary, int* d_where,
+                                          int* d_ok, double* d_in, double* d_out, int* d_index, int* d_count, void* stream);
+
 /* ---- SQP (Gauss-Newton / iLQR) loop on the 18-DoF model (BASELINE configs[3]) --------------------------------
  * Trajectory-tracking problem per member: state x = [q; qd] (36), control u = the 12 joint torques (base unactuated), known foot
  * forces f_k, explicit Euler  q+ = q + dt qd, qd+ = qd + dt qdd(q, qd, [0; u], f)  (the discretisation of the SRBM NLP,

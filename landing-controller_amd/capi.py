@@ -47,6 +47,21 @@ class PipelineOpts(C.Structure):
                 ("jpos_min", C.c_double * 12), ("jpos_max", C.c_double * 12), ("jpos_guess", C.c_double * 3), ("warm", C.c_int)]
 
 
+class ActuatorModel(C.Structure):
+    """landing_actuator_model of include/landing_nlp.h: gear ratios, torque constants, winding resistances and joint torque limits (abad / hip / knee), battery voltage"""
+    _fields_ = [("gr", C.c_double * 3), ("kt", C.c_double * 3), ("Rm", C.c_double * 3), ("tau_max", C.c_double * 3), ("battery_v", C.c_double)]
+
+
+class ActuatorScreen(C.Structure):
+    """landing_actuator_screen of include/landing_nlp.h: the limits a member has to hold to be kept (a limit <= 0 is not screened); drive_only = 1 holds
+    volt_max against the samples with tau * jvel > 0 only"""
+    _fields_ = [("volt_max", C.c_double), ("tau_ratio_max", C.c_double), ("jvel_max", C.c_double), ("drive_only", C.c_int)]
+
+
+AUDIT_NSUM = 8      # LANDING_AUDIT_NSUM
+AUDIT_SUMMARY = ("tau_ratio", "jvel", "volt", "volt_drive", "power_max", "power_min", "n_over", "n_over_drive")      # d_summary's columns
+
+
 ARGS21 = ["Xref", "Uref", "dt", "q_min", "q_max", "qd_min", "qd_max", "q_init", "qd_init", "q_term_min", "q_term_max",
           "qd_term_min", "qd_term_max", "QN", "x0", "mu", "l_leg_max", "f_max", "mass", "Ib", "Ib_inv"]
 
@@ -187,6 +202,13 @@ def load(path=None):
         lib.landing_pipeline_refine_batch.argtypes = [vp, C.c_int, vp, vp, vp, vp, po] + [vp] * 10 + [vp]
         lib.landing_pipeline_batch.argtypes = [vp, C.c_int, vp, vp, po, vp] + [vp] * 10 + [vp]
         lib.landing_pipeline_21.argtypes = [vp, C.c_int] + [_dp] * 21 + [po, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _ip]
+    if hasattr(lib, "landing_actuator_audit_batch"):      # the actuator audit and the pair writer behind it
+        am, sc = C.POINTER(ActuatorModel), C.POINTER(ActuatorScreen)
+        lib.landing_actuator_model_mc3d.argtypes = [am]; lib.landing_actuator_model_mc3d.restype = None
+        lib.landing_actuator_screen_default.argtypes = [sc]; lib.landing_actuator_screen_default.restype = None
+        lib.landing_actuator_audit_batch.argtypes = [vp, C.c_int, vp, C.c_int, vp, am, sc] + [vp] * 6 + [vp]
+        lib.landing_actuator_audit_host.argtypes = [vp, C.c_int, _dp, C.c_int, _dp, am, sc, _dp, _dp, _dp, _dp, _ip, _ip]
+        lib.landing_pipeline_screened_pairs_batch.argtypes = [vp, C.c_int, vp, vp, vp, am, sc] + [vp] * 7 + [vp]
     return lib
 
 

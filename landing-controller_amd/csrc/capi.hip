@@ -29,6 +29,7 @@
 #include "wb_kernels.hip"
 #include "kd_solver_kernels.hip"
 #include "pipeline_kernels.hip"
+#include "actuator_kernels.hip"
 
 using landing::Layout;
 
@@ -529,4 +530,5 @@ int landing_bounds_batch(landing_ctx* ctx, int B, const double* d_p, double* d_l
 #include "kd_capi.inc"
 #include "kd_casadi_capi.inc"
 #include "pipeline_capi.inc"
+#include "actuator_capi.inc"
 #include "gains_capi.inc"

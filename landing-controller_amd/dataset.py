@@ -123,8 +123,10 @@ def denormalise(nn_col, stats, with_jpos=False):
 
 
 def write_member_log(path, status, iters, kkt, f=None, extra=None):
-    """JSON lines, one record per batch member (SURVEY section 5 hook: iterations, pr_inf, du_inf, compl, status)"""
+    """JSON lines, one record per batch member (SURVEY section 5 hook: iterations, pr_inf, du_inf, compl, status).  extra: further fields of every
+    record; a list or array with one entry per member gives each record its own entry"""
     import json
+    per_member = {k: np.asarray(v).tolist() for k, v in (extra or {}).items() if isinstance(v, (list, tuple, np.ndarray)) and len(v) == len(status)}
     with open(path, "a") as fh:
         for m in range(len(status)):
             rec = {"member": m, "status": int(status[m]), "iterations": int(iters[m]), "pr_inf": float(kkt[m][0]), "du_inf": float(kkt[m][1]), "compl": float(kkt[m][2])}
@@ -132,21 +134,26 @@ def write_member_log(path, status, iters, kkt, f=None, extra=None):
                 rec["f"] = float(f[m])
             if extra:
                 rec.update(extra)
+                rec.update({k: v[m] for k, v in per_member.items()})
             fh.write(json.dumps(rec) + "\n")
 
 
-def generate_streamed(N, n_batches, B, shard_path, seed0=0, T=0.6, dt_grid="uniform", law="main", opts=None, depth=2, device=0, log_path=None, refine=False, **form):
+def generate_streamed(N, n_batches, B, shard_path, seed0=0, T=0.6, dt_grid="uniform", law="main", opts=None, depth=2, device=0, log_path=None, refine=False, screen=None, **form):
     """The data-generation loop of generate_data/generate_training_data_automated.m:38-219 as a STREAM of batches through one GPU (round 6): the drop states of batch i + 1 are sampled on
     the host and queued (`pipeline.BatchPipeline` over the library's landing_stream_submit / _wait: one context, `depth` launches in flight) while batch i is solved; the converged members of
     every batch that leaves the pipeline are appended to the shard in the reference's layout (training_pairs / append_shard), every member is logged (write_member_log).  Returns the
     counts per status and the number of samples written.  Results per batch are bit-identical to one solve at a time (tests/test_gpu_dataset.py).
     refine=True: the whole chain per batch (SRBM solve, kinodynamic refinement, warm re-solve; `opts` a pipeline options struct, default
-    landing_pipeline_opts_default), shards of [X*; U*; jpos*] -- see _generate_refined."""
+    landing_pipeline_opts_default), shards of [X*; U*; jpos*] -- see _generate_refined.
+    screen (with refine=True): a landing_actuator_screen (rbd.Rbd.actuator_screen()); the shards then hold the members with final status 0 that also pass
+    the actuator audit (landing_pipeline_screened_pairs_batch), the member log gains the audit's summary columns (capi.AUDIT_SUMMARY) and `ok`."""
     import importlib
     problem = importlib.import_module(__package__ + ".problem"); pipeline = importlib.import_module(__package__ + ".pipeline")
     consts = problem.production_constants(law) if dt_grid == "reference" else None
+    if screen is not None and not refine:
+        raise ValueError("the actuator screen audits refined trajectories: refine=True")
     if refine:
-        return _generate_refined(problem, pipeline, consts, N, n_batches, B, shard_path, seed0, T, dt_grid, law, opts, device, log_path)
+        return _generate_refined(problem, pipeline, consts, N, n_batches, B, shard_path, seed0, T, dt_grid, law, opts, device, log_path, screen)
     pipe = pipeline.BatchPipeline(N, depth=depth, device=device, opts=opts, **form)
     meta, counts, written = {}, {}, 0
 
@@ -174,14 +181,15 @@ def generate_streamed(N, n_batches, B, shard_path, seed0=0, T=0.6, dt_grid="unif
     return dict(status_counts=counts, samples_written=written, batches=n_batches)
 
 
-def _generate_refined(problem, pipeline, consts, N, n_batches, B, shard_path, seed0, T, dt_grid, law, opts, device, log_path):
+def _generate_refined(problem, pipeline, consts, N, n_batches, B, shard_path, seed0, T, dt_grid, law, opts, device, log_path, screen=None):
     """generate_streamed(refine=True): the SRBM solve of batch i + 1 is launched on its own stream before batch i is refined on another
     (landing_pipeline_refine_batch; its host loop synchronises its own stream only, and the SRBM solver's workspace is not the refinement's, so the
     two overlap on the GPU).  The SRBM outputs are double-buffered; a warm-up call with one iteration per pass sizes every workspace first, so that
     no growth (and the device-wide synchronisation it needs) lands inside the loop.  Per batch the result is bit-identical to one
     landing_pipeline_batch call.  Shards hold input [9, M] and output [48N + 12, M] = [X*(:); U*(:); jpos*(:)]; counts are of the final status."""
+    import importlib
     import torch
-    chain = pipeline.RefineChain(N, device=device, opts=opts)
+    chain = pipeline.RefineChain(N, device=device, opts=opts, screen=screen)
     dev, o = chain.dev, chain.opts
     f64, i32 = dict(device=dev, dtype=torch.float64), dict(device=dev, dtype=torch.int32)
     s_srbm, s_ref = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
@@ -220,8 +228,12 @@ def _generate_refined(problem, pipeline, consts, N, n_batches, B, shard_path, se
             batches.pop(i)
             if res["n_kept"]:
                 written = append_shard(shard_path, res["pair_in"], res["pair_out"])
+            extra = {"batch": i}
+            if screen is not None:
+                capi = importlib.import_module(__package__ + ".capi")
+                extra.update({n: res["audit"][:, j] for j, n in enumerate(capi.AUDIT_SUMMARY)}, ok=res["audit_ok"])
             if log_path:
-                write_member_log(log_path, res["final_status"], res["iters"].sum(axis=1), res["kkt"], res["f"], extra={"batch": i})
+                write_member_log(log_path, res["final_status"], res["iters"].sum(axis=1), res["kkt"], res["f"], extra=extra)
             for v in res["final_status"]:
                 counts[int(v)] = counts.get(int(v), 0) + 1
     finally:

@@ -75,26 +75,41 @@ def final_status(status3):
 
 class RefineChain:
     """The drop-state chain on one device: a context with the 'mc3D' model (rbd.Rbd) and the library's landing_pipeline_batch /
-    landing_pipeline_refine_batch.  Device tensors in / out (run_device, refine_device: torch tensors, no host copy inside), or numpy (run_host)."""
+    landing_pipeline_refine_batch.  Device tensors in / out (run_device, refine_device: torch tensors, no host copy inside), or numpy (run_host).
+    screen: a landing_actuator_screen (rbd.Rbd.actuator_screen()).  With one, the chain runs without its pair outputs and the pairs are written by
+    landing_pipeline_screened_pairs_batch on the same stream: the members with final status 0 that also pass the actuator audit; the outputs gain
+    audit [B, 8], audit_where [B, 4] and audit_ok [B].  screen=None: the chain's own pair writer, nothing else."""
 
-    def __init__(self, N, device=0, opts=None):
+    def __init__(self, N, device=0, opts=None, screen=None):
         capi = importlib.import_module(__package__ + ".capi"); rbd = importlib.import_module(__package__ + ".rbd")
         self.N, self.dev = N, torch.device("cuda", device)
         self.L = capi.LandingLib(N, device=device)
         self.R = rbd.Rbd(self.L)
         self.opts = opts if opts is not None else self.R.pipeline_opts()
+        self.screen = screen
         self.nxk, self.ngk = 48 * N + 12, 48 + 141 * (N - 1) + 117
 
     def alloc(self, B, lam=False):
         """output tensors of one batch"""
         f64, i32 = dict(device=self.dev, dtype=torch.float64), dict(device=self.dev, dtype=torch.int32)
-        return dict(x=torch.empty(B, self.nxk, **f64), f=torch.empty(B, **f64), kkt=torch.empty(B, 3, **f64), status=torch.empty(B, 3, **i32),
-                    iters=torch.empty(B, 3, **i32), pair_in=torch.empty(B, 9, **f64), pair_out=torch.empty(B, self.nxk, **f64), index=torch.empty(B, **i32),
-                    count=torch.zeros(1, **i32), lam_g=torch.empty(B, self.ngk, **f64) if lam else None)
+        o = dict(x=torch.empty(B, self.nxk, **f64), f=torch.empty(B, **f64), kkt=torch.empty(B, 3, **f64), status=torch.empty(B, 3, **i32),
+                 iters=torch.empty(B, 3, **i32), pair_in=torch.empty(B, 9, **f64), pair_out=torch.empty(B, self.nxk, **f64), index=torch.empty(B, **i32),
+                 count=torch.zeros(1, **i32), lam_g=torch.empty(B, self.ngk, **f64) if lam else None)
+        if self.screen is not None:
+            o.update(audit=torch.empty(B, 8, **f64), audit_where=torch.empty(B, 4, **i32), audit_ok=torch.empty(B, **i32))
+        return o
 
     def _outs(self, o):
-        return dict(d_lam=o["lam_g"].data_ptr() if o["lam_g"] is not None else 0, d_in=o["pair_in"].data_ptr(), d_out=o["pair_out"].data_ptr(),
-                    d_index=o["index"].data_ptr(), d_count=o["count"].data_ptr())
+        lam = dict(d_lam=o["lam_g"].data_ptr() if o["lam_g"] is not None else 0)
+        if self.screen is not None:      # the pairs come from _screened_pairs, behind the chain
+            return lam
+        return dict(lam, d_in=o["pair_in"].data_ptr(), d_out=o["pair_out"].data_ptr(), d_index=o["index"].data_ptr(), d_count=o["count"].data_ptr())
+
+    def _screened_pairs(self, P, o, st):
+        if self.screen is not None:
+            self.R.screened_pairs(P.shape[0], P.data_ptr(), o["x"].data_ptr(), o["status"].data_ptr(), o["audit"].data_ptr(), o["audit_where"].data_ptr(),
+                                  o["audit_ok"].data_ptr(), o["pair_in"].data_ptr(), o["pair_out"].data_ptr(), o["index"].data_ptr(), o["count"].data_ptr(),
+                                  screen=self.screen, stream=st.cuda_stream)
 
     def run_device(self, P, X0, out=None, x_srbm=None, stream=None, opts=None):
         """landing_pipeline_batch on device tensors P [B, np], X0 [B, 36N+12]; returns the output dict (queued on `stream`, not synchronised)"""
@@ -104,6 +119,7 @@ class RefineChain:
         self.R.pipeline_device(B, P.data_ptr(), X0.data_ptr(), opts or self.opts, out["x"].data_ptr(), out["f"].data_ptr(), out["status"].data_ptr(),
                                out["iters"].data_ptr(), out["kkt"].data_ptr(), d_x_srbm=x_srbm.data_ptr() if x_srbm is not None else 0, stream=st.cuda_stream,
                                **self._outs(out))
+        self._screened_pairs(P, out, st)
         return out
 
     def refine_device(self, P, XS, srbm_status=None, srbm_iters=None, out=None, stream=None, opts=None):
@@ -114,6 +130,7 @@ class RefineChain:
         self.R.pipeline_refine_device(B, P.data_ptr(), XS.data_ptr(), opts or self.opts, out["x"].data_ptr(), out["f"].data_ptr(), out["status"].data_ptr(),
                                       out["iters"].data_ptr(), out["kkt"].data_ptr(), d_srbm_status=srbm_status.data_ptr() if srbm_status is not None else 0,
                                       d_srbm_iters=srbm_iters.data_ptr() if srbm_iters is not None else 0, stream=st.cuda_stream, **self._outs(out))
+        self._screened_pairs(P, out, st)
         return out
 
     @staticmethod

@@ -205,6 +205,61 @@ class Rbd:
         self.L._check(self.L.lib.landing_training_pairs_batch(self.L.ctx, B, d_p, d_x_kd, d_status_final, d_in, d_out, d_index, d_count, stream or None),
                       "landing_training_pairs_batch")
 
+    # ---- actuator audit of refined trajectories (include/landing_nlp.h landing_actuator_*; csrc/actuator_kernels.hip) ----
+    def actuator_model(self):
+        """landing_actuator_model_mc3d"""
+        from .capi import ActuatorModel
+        m = ActuatorModel()
+        self.L.lib.landing_actuator_model_mc3d(C.byref(m))
+        return m
+
+    def actuator_screen(self, **limits):
+        """landing_actuator_screen_default (volt_max = 24, drive_only = 1, the other limits off), fields overridden by keyword"""
+        from .capi import ActuatorScreen
+        s = ActuatorScreen()
+        self.L.lib.landing_actuator_screen_default(C.byref(s))
+        for k, v in limits.items():
+            if k not in dict(ActuatorScreen._fields_):
+                raise TypeError("landing_actuator_screen has no field %r" % k)
+            setattr(s, k, v)
+        return s
+
+    def actuator_audit_device(self, B, d_dt, dt_stride, d_x_kd, d_summary, d_where, d_ok, model=None, screen=None, d_tau=0, d_jvel=0, d_volt=0, stream=0):
+        """landing_actuator_audit_batch: device pointers (integers); d_dt + b * dt_stride is member b's grid (0: one grid for all)"""
+        n = lambda v: v or None
+        ref = lambda v: C.byref(v) if v is not None else None
+        self.L._check(self.L.lib.landing_actuator_audit_batch(self.L.ctx, B, n(d_dt), dt_stride, n(d_x_kd), ref(model), ref(screen), n(d_tau), n(d_jvel), n(d_volt),
+                                                              n(d_summary), n(d_where), n(d_ok), n(stream)), "landing_actuator_audit_batch")
+
+    def actuator_audit(self, x_kd, dt, model=None, screen=None, full=True):
+        """landing_actuator_audit_host: numpy x [B, 48N+12] (the refinement's layout) and dt [N] (one grid) or [B, N] -> dict of summary [B, 8]
+        (capi.AUDIT_SUMMARY), where [B, 4], ok [B] and, with full, tau / jvel / volt [B, N, 12]"""
+        from .capi import AUDIT_NSUM
+        N = self.L.N
+        x = np.ascontiguousarray(np.atleast_2d(x_kd), float); dt = np.ascontiguousarray(dt, float)
+        B = x.shape[0]
+        assert x.shape == (B, 48 * N + 12) and dt.shape in ((N,), (B, N))
+        mk = lambda: np.zeros((B, N, 12)) if full else None
+        tau, jvel, volt = mk(), mk(), mk()
+        summ, where, ok = np.zeros((B, AUDIT_NSUM)), np.zeros((B, 4), np.int32), np.zeros(B, np.int32)
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+        P = lambda a: None if a is None else a.ctypes.data_as(dp)
+        ref = lambda v: C.byref(v) if v is not None else None
+        rc = self.L.lib.landing_actuator_audit_host(self.L.ctx, B, P(dt), N if dt.ndim == 2 else 0, P(x), ref(model), ref(screen), P(tau), P(jvel), P(volt), P(summ),
+                                                    where.ctypes.data_as(ip), ok.ctypes.data_as(ip))
+        self.L._check(rc, "landing_actuator_audit_host")
+        out = dict(summary=summ, where=where, ok=ok)
+        if full:
+            out.update(tau=tau, jvel=jvel, volt=volt)
+        return out
+
+    def screened_pairs(self, B, d_p, d_x_kd, d_status3, d_summary, d_where, d_ok, d_in, d_out, d_index, d_count, model=None, screen=None, stream=0):
+        """landing_pipeline_screened_pairs_batch: the chain's pair writer behind the screen (device pointers): the members with final status 0 AND ok"""
+        n = lambda v: v or None
+        ref = lambda v: C.byref(v) if v is not None else None
+        self.L._check(self.L.lib.landing_pipeline_screened_pairs_batch(self.L.ctx, B, n(d_p), n(d_x_kd), n(d_status3), ref(model), ref(screen), n(d_summary), n(d_where),
+                                                                       n(d_ok), n(d_in), n(d_out), n(d_index), n(d_count), n(stream)), "landing_pipeline_screened_pairs_batch")
+
     def pipeline_refine_device(self, B, d_p, d_x_srbm, opts, d_x, d_f, d_status, d_iters, d_kkt, d_lam=0, d_in=0, d_out=0, d_index=0, d_count=0,
                                d_srbm_status=0, d_srbm_iters=0, stream=0):
         """landing_pipeline_refine_batch: pose, refinement, warm re-solve, final choice, pairs behind SRBM solutions already on the device"""
