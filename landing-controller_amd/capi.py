@@ -4,6 +4,9 @@ The library is the product: HIP kernels for gfx950 behind plain-C entry points. 
 loudly (ImportError / RuntimeError) when the library is missing or no GPU is usable -- there is no
 CPU fallback.  ``load(path)`` lets the CPU test-suite bind the host-emulated build of the same
 sources (tests/emu) for logic tests; product code never passes a path.
+
+A new entry point is added to the header, to SIGNATURES below and to a wrapper; tests/test_binding_signatures_cpu.py
+fails until the first two agree.
 """
 import ctypes as C
 import os
@@ -80,20 +83,134 @@ class Args21(C.Structure):
     _fields_ = [(n, _dp) for n in ARGS21]
 
 
-EXPORTS = ["landing_last_error", "landing_form_default", "landing_solver_opts_default", "landing_nx", "landing_ng",
-           "landing_np", "landing_nnz_jac", "landing_nnz_hess", "landing_pattern_jac", "landing_pattern_hess",
-           "landing_create", "landing_destroy", "landing_device_count", "landing_eval_batch", "landing_eval_batch_host",
-           "landing_bounds_batch", "landing_solve_batch", "landing_solve_batch_host", "landing_kernel_name_sweep",
-           "landing_sweep_bytes_per_member", "landing_set_profile_buffer", "landing_debug_workspace", "landing_debug_solver_tables",
-           "landing_pack_args21", "landing_solve_args21", "landing_solve_21",
-           "landing_multi_create", "landing_multi_destroy", "landing_multi_count", "landing_shard_range", "landing_multi_solve_args21",
-           "landing_solve_21_multi", "landing_multi_release_cached",
-           "landing_np_ccc", "landing_ctx_np", "landing_pack_args25", "landing_solve_args25", "landing_riccati_gains_batch", "landing_mpc_shift", "landing_solver_opts_warm", "landing_rbd_set_model", "landing_fb_dynamics_batch",
-           "landing_kinodyn_rows_batch", "landing_kinodyn_nlp_dims", "landing_kinodyn_nlp_eval", "landing_kinodyn_nlp_hess", "landing_leg_ik_batch", "landing_nnz_hess_rc", "landing_pattern_hess_rc",
-           "landing_eval_hess_rc_batch", "landing_eval_hess_rc_batch_host",
-           "landing_stream_create", "landing_stream_destroy", "landing_stream_lanes", "landing_stream_submit", "landing_stream_wait", "landing_stream_sync", "landing_solve_stream_host",
-           "landing_sample_reference_batch", "landing_tracking_gains_batch", "landing_tracking_gains_host",
-           "landing_debug_kd_workspace", "landing_debug_kd_layout", "landing_debug_kd_state"]
+class RbdModel(C.Structure):
+    """landing_rbd_model of include/landing_nlp.h (rbd.quad3d_model fills one)"""
+    _fields_ = [("parent", C.c_int * 18), ("jtype", C.c_int * 18), ("E", (C.c_double * 9) * 18), ("r", (C.c_double * 3) * 18),
+                ("m", C.c_double * 18), ("h", (C.c_double * 3) * 18), ("I", (C.c_double * 6) * 18),
+                ("b_foot", C.c_int * 4), ("foot_r", (C.c_double * 3) * 4), ("l1", C.c_double), ("l2", C.c_double), ("l3", C.c_double), ("l4", C.c_double)]
+
+
+class KinodynParams(C.Structure):
+    """landing_kinodyn_params of include/landing_nlp.h"""
+    _fields_ = [("dt", C.c_double * 64), ("mass", C.c_double), ("Ib", C.c_double * 3), ("Ib_inv", C.c_double * 3), ("mu", C.c_double)]
+
+
+# Entry point -> (restype, argtypes), for every function include/landing_nlp.h declares; load() applies it.  c_void_p: contexts, device addresses
+# and streams (a Python integer passes through whole); typed pointers: host arrays and structs.
+_vp, _ci, _cd, _ll, _ullp = C.c_void_p, C.c_int, C.c_double, C.c_longlong, C.POINTER(C.c_ulonglong)
+_form, _so, _kf, _kp, _po = C.POINTER(LandingForm), C.POINTER(SolverOpts), C.POINTER(KinodynForm), C.POINTER(KinodynParams), C.POINTER(PipelineOpts)
+_am, _sc = C.POINTER(ActuatorModel), C.POINTER(ActuatorScreen)
+_out5, _out6 = [_dp, _dp, _ip, _ip, _dp], [_dp, _dp, _dp, _ip, _ip, _dp]      # x f [lam_g] status iters kkt, host
+_gains = [_cd, _ci, _dp, _cd, _dp, _dp, _dp, _ci]                              # dt_r n Ib3x3 mass Q r_diag F rk4
+_chain = _out6 + [_dp, _dp, _ip]                                               # ... pair_in pair_out n_kept
+SIGNATURES = {
+    # formulation, sizes, patterns, context
+    "landing_form_default": (None, [_form]),
+    "landing_solver_opts_default": (None, [_so]),
+    "landing_solver_opts_warm": (None, [_so]),
+    "landing_pattern_jac": (_ci, [_ci, _llp, _llp]),
+    "landing_pattern_hess": (_ci, [_ci, _llp, _llp]),
+    "landing_pattern_hess_rc": (_ci, [_ci, _llp, _llp]),
+    "landing_ctx_np": (_ll, [_vp]),
+    "landing_create": (_vp, [_ci, _ci, _form]),
+    "landing_destroy": (None, [_vp]),
+    "landing_last_error": (C.c_char_p, []),
+    "landing_device_count": (_ci, []),
+    "landing_kernel_name_sweep": (C.c_char_p, []),
+    # function layer and solver of the SRBM NLP
+    "landing_eval_batch": (_ci, [_vp, _ci] + [_vp] * 11 + [_vp]),
+    "landing_eval_batch_host": (_ci, [_vp, _ci] + [_dp] * 11),
+    "landing_eval_hess_rc_batch": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "landing_eval_hess_rc_batch_host": (_ci, [_vp, _ci, _dp, _dp, _dp, _dp, _dp]),
+    "landing_bounds_batch": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp]),
+    "landing_solve_batch": (_ci, [_vp, _ci, _vp, _vp, _so] + [_vp] * 6 + [_vp]),
+    "landing_solve_batch_host": (_ci, [_vp, _ci, _dp, _dp, _so] + _out6),
+    "landing_pack_args21": (_ci, [_ci, _ci, C.POINTER(Args21), _dp]),
+    "landing_solve_args21": (_ci, [_vp, _ci, C.POINTER(Args21), _so] + _out5),
+    "landing_solve_21": (_ci, [_vp, _ci] + [_dp] * 21 + [_so] + _out5),
+    "landing_pack_args25": (_ci, [_ci, _ci, C.POINTER(Args25), _dp]),
+    "landing_solve_args25": (_ci, [_vp, _ci, C.POINTER(Args25), _so] + _out6),
+    "landing_mpc_shift": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _vp]),
+    # several devices from the C boundary
+    "landing_multi_create": (_vp, [_ci, _ip, _ci, _form]),
+    "landing_multi_destroy": (None, [_vp]),
+    "landing_multi_count": (_ci, [_vp]),
+    "landing_shard_range": (None, [_ci, _ci, _ci, _ip, _ip]),
+    "landing_multi_solve_args21": (_ci, [_vp, _ci, C.POINTER(Args21), _so] + _out6),
+    "landing_solve_21_multi": (_ci, [_ip, _ci, _ci, _ci] + [_dp] * 21 + [_so] + _out6),
+    "landing_multi_release_cached": (None, []),
+    # streaming
+    "landing_stream_create": (_vp, [_vp, _ci]),
+    "landing_stream_destroy": (None, [_vp]),
+    "landing_stream_lanes": (_ci, [_vp]),
+    "landing_stream_submit": (_ll, [_vp, _ci, _vp, _vp, _so] + [_vp] * 6 + [_vp]),
+    "landing_stream_wait": (_ci, [_vp, _ll, _vp]),
+    "landing_stream_sync": (_ci, [_vp, _vp]),
+    "landing_solve_stream_host": (_ci, [_vp, _ci, _ci, _ci, _dp, _dp, _so] + _out6),
+    # tracking _gains
+    "landing_riccati_gains_batch": (_ci, [_vp, _ci, _ci, _vp, _vp, _dp, _cd, _dp, _dp, _dp, _cd, _ci, _vp, _vp, _vp, _vp, _vp]),
+    "landing_sample_reference_batch": (_ci, [_vp, _ci, _vp, _vp, _cd, _ci, _vp, _vp, _vp]),
+    "landing_tracking_gains_batch": (_ci, [_vp, _ci, _vp, _vp, _vp] + _gains + [_vp] * 6 + [_vp]),
+    "landing_tracking_gains_host": (_ci, [_vp, _ci, _dp, _dp, _ip] + _gains + [_dp] * 6),
+    # rigid-body routines and the kinodynamic refinement NLP
+    "landing_rbd_set_model": (_ci, [_vp, C.POINTER(RbdModel)]),
+    "landing_rbd_model_mc3d": (None, [C.POINTER(RbdModel)]),
+    "landing_fb_dynamics_batch": (_ci, [_vp, _ci] + [_vp] * 9 + [_cd, _vp]),
+    "landing_leg_ik_batch": (_ci, [_vp, _ci, _vp, _vp, _dp, _dp, _ci, _vp, _vp, _vp]),
+    "landing_kinodyn_rows_batch": (_ci, [_vp, _ci] + [_vp] * 7 + [_vp]),
+    "landing_kinodyn_nlp_dims": (_ci, [_ci, _llp, _llp]),
+    "landing_kinodyn_nlp_eval": (_ci, [_vp, _ci, _ci, _vp, _kp, _vp, _vp, _vp]),
+    "landing_kinodyn_nlp_hess": (_ci, [_vp, _ci, _ci, _vp, _kp, _vp, _vp, _vp]),
+    "landing_kinodyn_form_default": (None, [_kf]),
+    "landing_kinodyn_form_knitro": (None, [_kf]),
+    "landing_kinodyn_solver_opts_default": (None, [_so]),
+    "landing_kinodyn_solver_opts_warm": (None, [_so]),
+    "landing_kinodyn_bounds": (_ci, [_ci, _ci, _vp] + [_dp] * 14),
+    "landing_kinodyn_solve_batch": (_ci, [_vp, _ci, _ci, _kp] + [_vp] * 4 + [_vp] + [_vp] * 6 + [_vp]),
+    "landing_kinodyn_solve_batch_host": (_ci, [_vp, _ci, _ci, _kp, _dp, _dp, _dp, _dp, _vp] + _out6),
+    "landing_solve_kinodyn_24": (_ci, [_vp, _ci, _ci, _vp] + [_dp] * 24 + [_vp] + _out6),
+    "landing_solve_kinodyn_24_on": (_ci, [_ci, _ci, _ci] + [_dp] * 24 + [_so] + _out6),
+    "landing_solve_kinodyn_24_on_form": (_ci, [_ci, _ci, _ci, _kf] + [_dp] * 24 + [_so] + _out6),
+    "landing_kinodyn_pattern": (_ci, [_vp, _ci, _ci, _llp, _llp, _llp]),
+    "landing_kinodyn_block_nonzeros": (_ci, [_vp, _ip, _ip, C.POINTER(C.c_ubyte)]),
+    "landing_kinodyn_casadi_offsets": (_ci, [_ci, _llp]),
+    "landing_kinodyn_casadi_bounds": (_ci, [_ci, _vp, _dp, _dp, _dp]),
+    "landing_kinodyn_casadi_pattern": (_ci, [_vp, _ci, _ci, C.POINTER(_llp), C.POINTER(_llp), _llp]),
+    "landing_kinodyn_casadi_eval_host": (_ci, [_vp, _ci, _dp, _dp, _dp, _dp] + [_dp] * 7),
+    "landing_kinodyn_casadi_release": (None, [_vp]),
+    # the drop-state _chain and the actuator audit behind it
+    "landing_pipeline_opts_default": (None, [_po]),
+    "landing_pipeline_final_status": (_ci, [_ci, _ci]),
+    "landing_kinodyn_pose_batch": (_ci, [_vp, _ci, _vp, _vp, _po] + [_vp] * 4 + [_vp]),
+    "landing_training_pairs_batch": (_ci, [_vp, _ci] + [_vp] * 7 + [_vp]),
+    "landing_pipeline_refine_batch": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _po] + [_vp] * 10 + [_vp]),
+    "landing_pipeline_batch": (_ci, [_vp, _ci, _vp, _vp, _po, _vp] + [_vp] * 10 + [_vp]),
+    "landing_pipeline_21": (_ci, [_vp, _ci] + [_dp] * 21 + [_po] + _chain),
+    "landing_pipeline_21_on": (_ci, [_ci, _ci, _ci] + [_dp] * 21 + [_po] + _chain),
+    "landing_actuator_model_mc3d": (None, [_am]),
+    "landing_actuator_screen_default": (None, [_sc]),
+    "landing_actuator_audit_batch": (_ci, [_vp, _ci, _vp, _ci, _vp, _am, _sc] + [_vp] * 6 + [_vp]),
+    "landing_actuator_audit_host": (_ci, [_vp, _ci, _dp, _ci, _dp, _am, _sc, _dp, _dp, _dp, _dp, _ip, _ip]),
+    "landing_pipeline_screened_pairs_batch": (_ci, [_vp, _ci, _vp, _vp, _vp, _am, _sc] + [_vp] * 7 + [_vp]),
+    # whole-body SQP
+    "landing_wb_backward": (_ci, [_vp, _ci, _ci, _cd, _cd, _vp, _vp, _vp, _vp, _vp, _dp, _dp, _dp, _vp, _vp, _vp, _vp, _vp]),
+    "landing_wb_rollout": (_ci, [_vp, _ci, _ci, _ci, _vp, _cd, _vp, _vp, _vp, _vp, _vp, _vp, _dp, _dp, _dp, _vp, _vp, _vp, _vp]),
+    "landing_wb_set_integrator": (_ci, [_vp, _ci]),
+    "landing_wb_skip_taken": (_ci, [_vp, _vp]),
+    "landing_wb_select": (_ci, [_vp, _ci, _ci, _ci] + [_vp] * 10),
+    # diagnostics
+    "landing_set_profile_buffer": (_ci, [_vp, _vp]),
+    "landing_debug_workspace": (_ci, [_vp, C.POINTER(_vp), _ullp]),
+    "landing_debug_solver_tables": (_ci, [_vp, _ci, _vp, _ullp]),
+    "landing_debug_kd_workspace": (_ci, [_vp, C.POINTER(_vp), _ullp, _ip, _ip]),
+    "landing_debug_kd_layout": (_ci, [_ci, _ullp, _ullp, _ullp]),
+    "landing_debug_kd_state": (_ci, [_vp, _ci, _dp]),
+}
+SIGNATURES.update({n: (_ll, [_ci]) for n in ("landing_nx", "landing_ng", "landing_np", "landing_np_ccc", "landing_nnz_jac", "landing_nnz_hess", "landing_nnz_hess_rc",
+                                             "landing_sweep_bytes_per_member", "landing_kinodyn_casadi_np")})
+# what only the host-emulation build of the same sources exports (tests/emu); bound where present
+EMU_HOOKS = {"landing_emu_set_fused": (None, [_ci]), "landing_emu_accept_counts": (_ci, [_ci, _ip]),
+             "hip_emu_live_blocks": (_ll, []), "hip_emu_fail_alloc": (_ll, [_ll])}
 
 
 # Sizes the solver kernel's workspace layout is built from (csrc/solver_kernels.hip: RUNC, RIC_STRIDE, RCG, EXIT_REC)
@@ -138,78 +255,53 @@ def load(path=None):
     if not os.path.exists(path):
         raise ImportError(f"{path} not found: build it with __graft_entry__.build() (hipcc, gfx950). No CPU fallback exists.")
     lib = C.CDLL(path)
-    lib.landing_last_error.restype = C.c_char_p
-    lib.landing_kernel_name_sweep.restype = C.c_char_p
-    for n in ("landing_nx", "landing_ng", "landing_np", "landing_np_ccc", "landing_nnz_jac", "landing_nnz_hess", "landing_sweep_bytes_per_member"):
-        getattr(lib, n).restype = C.c_longlong
-        getattr(lib, n).argtypes = [C.c_int]
-    lib.landing_ctx_np.restype = C.c_longlong
-    lib.landing_ctx_np.argtypes = [C.c_void_p]
-    lib.landing_pattern_jac.argtypes = [C.c_int, _llp, _llp]
-    lib.landing_pattern_hess.argtypes = [C.c_int, _llp, _llp]
-    lib.landing_create.restype = C.c_void_p
-    lib.landing_create.argtypes = [C.c_int, C.c_int, C.POINTER(LandingForm)]
-    lib.landing_destroy.argtypes = [C.c_void_p]
-    vp = C.c_void_p
-    lib.landing_eval_batch.argtypes = [vp, C.c_int] + [vp] * 11 + [vp]
-    lib.landing_eval_batch_host.argtypes = [vp, C.c_int] + [_dp] * 11
-    lib.landing_bounds_batch.argtypes = [vp, C.c_int, vp, vp, vp, vp]
-    if hasattr(lib, "landing_eval_hess_rc_batch"):
-        lib.landing_nnz_hess_rc.restype = C.c_longlong; lib.landing_nnz_hess_rc.argtypes = [C.c_int]
-        lib.landing_pattern_hess_rc.argtypes = [C.c_int, _llp, _llp]
-        lib.landing_eval_hess_rc_batch.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
-        lib.landing_eval_hess_rc_batch_host.argtypes = [vp, C.c_int, _dp, _dp, _dp, _dp, _dp]
-    lib.landing_solve_batch.argtypes = [vp, C.c_int, vp, vp, C.POINTER(SolverOpts), vp, vp, vp, vp, vp, vp, vp]
-    lib.landing_set_profile_buffer.argtypes = [vp, vp]
-    lib.landing_debug_solver_tables.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_ulonglong)]
-    lib.landing_solve_batch_host.argtypes = [vp, C.c_int, _dp, _dp, C.POINTER(SolverOpts), _dp, _dp, _dp, _ip, _ip, _dp]
-    lib.landing_pack_args21.argtypes = [C.c_int, C.c_int, C.POINTER(Args21), _dp]
-    lib.landing_solve_args21.argtypes = [vp, C.c_int, C.POINTER(Args21), C.POINTER(SolverOpts), _dp, _dp, _ip, _ip, _dp]
-    lib.landing_riccati_gains_batch.argtypes = [vp, C.c_int, C.c_int, vp, vp, _dp, C.c_double, _dp, _dp, _dp, C.c_double, C.c_int, vp, vp, vp, vp, vp]
-    if hasattr(lib, "landing_tracking_gains_batch"):      # gains straight from a solved batch
-        lib.landing_sample_reference_batch.argtypes = [vp, C.c_int, vp, vp, C.c_double, C.c_int, vp, vp, vp]
-        gains = [C.c_double, C.c_int, _dp, C.c_double, _dp, _dp, _dp, C.c_int]      # dt_r n Ib3x3 mass Q r_diag F rk4
-        lib.landing_tracking_gains_batch.argtypes = [vp, C.c_int, vp, vp, vp] + gains + [vp] * 6 + [vp]
-        lib.landing_tracking_gains_host.argtypes = [vp, C.c_int, _dp, _dp, _ip] + gains + [_dp] * 6
-    if hasattr(lib, "landing_mpc_shift"):
-        lib.landing_mpc_shift.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
-    if hasattr(lib, "landing_solve_args25"):
-        lib.landing_pack_args25.argtypes = [C.c_int, C.c_int, C.POINTER(Args25), _dp]
-        lib.landing_solve_args25.argtypes = [vp, C.c_int, C.POINTER(Args25), C.POINTER(SolverOpts), _dp, _dp, _dp, _ip, _ip, _dp]
-    if hasattr(lib, "landing_multi_create"):
-        lib.landing_multi_create.restype = C.c_void_p
-        lib.landing_multi_create.argtypes = [C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(LandingForm)]
-        lib.landing_multi_destroy.argtypes = [vp]
-        lib.landing_multi_solve_args21.argtypes = [vp, C.c_int, C.POINTER(Args21), C.POINTER(SolverOpts), _dp, _dp, _dp, _ip, _ip, _dp]
-        lib.landing_solve_21_multi.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int] + [_dp] * 21 + [C.POINTER(SolverOpts), _dp, _dp, _dp, _ip, _ip, _dp]
-    lib.landing_solve_21.argtypes = [vp, C.c_int] + [_dp] * 21 + [C.POINTER(SolverOpts), _dp, _dp, _ip, _ip, _dp]
-    if hasattr(lib, "landing_stream_create"):      # streaming entry points (round 6)
-        lib.landing_stream_create.restype = C.c_void_p
-        lib.landing_stream_create.argtypes = [vp, C.c_int]
-        lib.landing_stream_destroy.argtypes = [vp]
-        lib.landing_stream_lanes.argtypes = [vp]
-        lib.landing_stream_submit.restype = C.c_longlong
-        lib.landing_stream_submit.argtypes = [vp, C.c_int, vp, vp, C.POINTER(SolverOpts), vp, vp, vp, vp, vp, vp, vp]
-        lib.landing_stream_wait.argtypes = [vp, C.c_longlong, vp]
-        lib.landing_stream_sync.argtypes = [vp, vp]
-        lib.landing_solve_stream_host.argtypes = [vp, C.c_int, C.c_int, C.c_int, _dp, _dp, C.POINTER(SolverOpts), _dp, _dp, _dp, _ip, _ip, _dp]
-    if hasattr(lib, "landing_pipeline_batch"):      # the drop-state chain
-        po = C.POINTER(PipelineOpts)
-        lib.landing_pipeline_opts_default.argtypes = [po]
-        lib.landing_pipeline_final_status.argtypes = [C.c_int, C.c_int]
-        lib.landing_kinodyn_pose_batch.argtypes = [vp, C.c_int, vp, vp, po] + [vp] * 4 + [vp]
-        lib.landing_training_pairs_batch.argtypes = [vp, C.c_int] + [vp] * 7 + [vp]
-        lib.landing_pipeline_refine_batch.argtypes = [vp, C.c_int, vp, vp, vp, vp, po] + [vp] * 10 + [vp]
-        lib.landing_pipeline_batch.argtypes = [vp, C.c_int, vp, vp, po, vp] + [vp] * 10 + [vp]
-        lib.landing_pipeline_21.argtypes = [vp, C.c_int] + [_dp] * 21 + [po, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _ip]
-    if hasattr(lib, "landing_actuator_audit_batch"):      # the actuator audit and the pair writer behind it
-        am, sc = C.POINTER(ActuatorModel), C.POINTER(ActuatorScreen)
-        lib.landing_actuator_model_mc3d.argtypes = [am]; lib.landing_actuator_model_mc3d.restype = None
-        lib.landing_actuator_screen_default.argtypes = [sc]; lib.landing_actuator_screen_default.restype = None
-        lib.landing_actuator_audit_batch.argtypes = [vp, C.c_int, vp, C.c_int, vp, am, sc] + [vp] * 6 + [vp]
-        lib.landing_actuator_audit_host.argtypes = [vp, C.c_int, _dp, C.c_int, _dp, am, sc, _dp, _dp, _dp, _dp, _ip, _ip]
-        lib.landing_pipeline_screened_pairs_batch.argtypes = [vp, C.c_int, vp, vp, vp, am, sc] + [vp] * 7 + [vp]
+    for name, (restype, argtypes) in SIGNATURES.items():      # a symbol the library lacks raises here: a broken build
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    lib.emu_hooks = [name for name in EMU_HOOKS if hasattr(lib, name)]      # non-empty: the host emulation, whose device memory is host memory
+    for name in lib.emu_hooks:
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = EMU_HOOKS[name]
     return lib
+
+
+def _n(v):
+    """a device address or stream held as an integer, 0 = NULL"""
+    return v or None
+
+
+def _ref(v):
+    """byref of a struct, None = NULL"""
+    return C.byref(v) if v is not None else None
+
+
+def _p(a):
+    return None if a is None else a.ctypes.data_as(_dp)
+
+
+def _pi(a):
+    return None if a is None else a.ctypes.data_as(_ip)
+
+
+def _solve_outputs(B, nx, ng=None):
+    """the host outputs of a solve of B members: (dict x f lam_g status iters kkt, their C pointers in that order); ng = None: lam_g = None / NULL"""
+    out = dict(x=np.zeros((B, nx)), f=np.zeros(B), lam_g=None if ng is None else np.zeros((B, ng)),
+               status=np.zeros(B, np.int32), iters=np.zeros(B, np.int32), kkt=np.zeros((B, 3)))
+    return out, [_p(out["x"]), _p(out["f"]), _p(out["lam_g"]), _pi(out["status"]), _pi(out["iters"]), _p(out["kkt"])]
+
+
+def _block_to_host(lib, ptr, shape, what):
+    """host array `shape` of doubles from a block of the library's device memory (host memory under the emulation)"""
+    out = np.empty(shape)
+    if lib.emu_hooks:
+        C.memmove(out.ctypes.data, ptr, out.nbytes)
+    else:
+        hip = _hip_runtime()
+        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        rc = hip.hipMemcpy(out.ctypes.data, ptr, out.nbytes, 2)      # hipMemcpyDeviceToHost
+        if rc != 0:
+            raise RuntimeError("hipMemcpy of %s failed (%d)" % (what, rc))
+    return out
 
 
 class SolveStream:
@@ -224,44 +316,26 @@ class SolveStream:
         self.lanes = lib.lib.landing_stream_lanes(self.h)
 
     def submit(self, B, d_p, d_x0, opts, d_x, d_f=0, d_lam_g=0, d_status=0, d_iters=0, d_kkt=0, in_stream=0):
-        t = self.L.lib.landing_stream_submit(self.h, B, d_p, d_x0, C.byref(opts), d_x, d_f or None, d_lam_g or None, d_status or None, d_iters or None, d_kkt or None, in_stream or None)
+        t = self.L.lib.landing_stream_submit(self.h, B, d_p, d_x0, C.byref(opts), d_x, _n(d_f), _n(d_lam_g), _n(d_status), _n(d_iters), _n(d_kkt), _n(in_stream))
         if t < 0:
             raise RuntimeError("landing_stream_submit: " + self.L.lib.landing_last_error().decode())
         return t
 
     def wait(self, ticket, stream=0):
-        self.L._check(self.L.lib.landing_stream_wait(self.h, ticket, stream or None), "landing_stream_wait")
+        self.L._check(self.L.lib.landing_stream_wait(self.h, ticket, _n(stream)), "landing_stream_wait")
 
     def sync(self, stream=0):
-        self.L._check(self.L.lib.landing_stream_sync(self.h, stream or None), "landing_stream_sync")
+        self.L._check(self.L.lib.landing_stream_sync(self.h, _n(stream)), "landing_stream_sync")
 
     def close(self):
         if self.h:
             self.L.lib.landing_stream_destroy(self.h); self.h = None
 
 
-def matlab_args25(N, args):
-    """the same for the 25 arguments of the N=41 script (c_init may be missing: inactive)"""
-    keep, a = [], Args25()
+def _matlab_args(names, struct, args):
+    keep, a = [], struct()
     B = np.asarray(args["x0"]).shape[-1] if np.asarray(args["x0"]).ndim > 1 else 1
-    for n in ARGS25:
-        v = args.get(n)
-        if v is None:
-            setattr(a, n, None)
-            continue
-        buf = np.ascontiguousarray(np.asarray(v, float).reshape((-1, B), order="F").T)
-        keep.append(buf)
-        setattr(a, n, buf.ctypes.data_as(_dp))
-    return a, keep, B
-
-
-def matlab_args21(N, args):
-    """dict of the 21 arguments as MATLAB would hold them for a batch of B members -- arrays whose LAST axis is the batch
-    (Xref [12, N+1, B], dt [1, N, B], 6-vectors [6, B], x0 [nx, B], scalars [1, B] ...) -- flattened column-major into the
-    member-major host buffers the C ABI takes.  Returns (Args21, keep-alive list, B)."""
-    keep, a = [], Args21()
-    B = np.asarray(args["x0"]).shape[-1] if np.asarray(args["x0"]).ndim > 1 else 1
-    for n in ARGS21:
+    for n in names:
         v = args.get(n)
         if v is None:
             setattr(a, n, None)
@@ -272,8 +346,16 @@ def matlab_args21(N, args):
     return a, keep, B
 
 
-def _p(a):
-    return None if a is None else a.ctypes.data_as(_dp)
+def matlab_args21(N, args):
+    """dict of the 21 arguments as MATLAB would hold them for a batch of B members -- arrays whose LAST axis is the batch
+    (Xref [12, N+1, B], dt [1, N, B], 6-vectors [6, B], x0 [nx, B], scalars [1, B] ...) -- flattened column-major into the
+    member-major host buffers the C ABI takes.  Returns (Args21, keep-alive list, B)."""
+    return _matlab_args(ARGS21, Args21, args)
+
+
+def matlab_args25(N, args):
+    """the same for the 25 arguments of the N=41 script (c_init may be missing: inactive)"""
+    return _matlab_args(ARGS25, Args25, args)
 
 
 class LandingLib:
@@ -328,7 +410,7 @@ class LandingLib:
         return o
 
     def mpc_shift_device(self, B, d_x_prev, d_state, d_p, d_x0, stream=0):
-        self._check(self.lib.landing_mpc_shift(self.ctx, B, d_x_prev, d_state, d_p, d_x0, stream or None), "landing_mpc_shift")
+        self._check(self.lib.landing_mpc_shift(self.ctx, B, d_x_prev, d_state, d_p, d_x0, _n(stream)), "landing_mpc_shift")
 
     def pattern_jac(self):
         ci = np.zeros(self.nx + 1, np.int64); r = np.zeros(self.nnz_jac, np.int64)
@@ -358,31 +440,23 @@ class LandingLib:
     def workspace_offsets(self):
         return workspace_offsets(self.N, self.nx, self.ng, self.nnz_jac, self.nnz_hess)
 
+    def _workspace(self):
+        """landing_debug_workspace: (address of the solver workspace or None, doubles per member)"""
+        ptr = C.c_void_p(); st = C.c_ulonglong()
+        self._check(self.lib.landing_debug_workspace(self.ctx, C.byref(ptr), C.byref(st)), "landing_debug_workspace")
+        return ptr.value, int(st.value)
+
     def workspace_stride(self):
         """doubles per member of the solver workspace, as the library lays it out"""
-        ptr = C.c_void_p(); st = C.c_ulonglong()
-        self.lib.landing_debug_workspace.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_ulonglong)]
-        self._check(self.lib.landing_debug_workspace(self.ctx, C.byref(ptr), C.byref(st)), "landing_debug_workspace")
-        return int(st.value)
+        return self._workspace()[1]
 
     def debug_workspace(self, B):
         """landing_debug_workspace: the blocks of the first B members of the last solve as a host array [B, stride] (diagnostic; the caller has
         synchronised with that solve -- the host entry points have).  Slice a row with workspace_offsets()."""
-        ptr = C.c_void_p(); st = C.c_ulonglong()
-        self.lib.landing_debug_workspace.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_ulonglong)]
-        self._check(self.lib.landing_debug_workspace(self.ctx, C.byref(ptr), C.byref(st)), "landing_debug_workspace")
-        if not ptr.value:
+        ptr, stride = self._workspace()
+        if not ptr:
             raise RuntimeError("landing_debug_workspace: no solve has run in this context")
-        out = np.empty((B, st.value))
-        if hasattr(self.lib, "landing_emu_set_fused"):      # host emulation: the workspace is host memory
-            C.memmove(out.ctypes.data, ptr.value, out.nbytes)
-        else:
-            hip = _hip_runtime()
-            hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-            rc = hip.hipMemcpy(out.ctypes.data, ptr.value, out.nbytes, 2)      # hipMemcpyDeviceToHost
-            if rc != 0:
-                raise RuntimeError("hipMemcpy of the solver workspace failed (%d)" % rc)
-        return out
+        return _block_to_host(self.lib, ptr, (B, stride), "the solver workspace")
 
     def solver_tables(self):
         """landing_debug_solver_tables: the tables the solver kernel reads, as the context holds them -- dict of ctab, ccomb, rterm (uint64),
@@ -417,24 +491,18 @@ class LandingLib:
         p = np.ascontiguousarray(np.atleast_2d(p), float); x0 = np.ascontiguousarray(np.atleast_2d(x0), float)
         B = p.shape[0]
         opts = opts or self.default_opts()
-        x = np.zeros((B, self.nx)); f = np.zeros(B); lam = np.zeros((B, self.ng))
-        status = np.zeros(B, np.int32); iters = np.zeros(B, np.int32); kkt = np.zeros((B, 3))
-        rc = self.lib.landing_solve_batch_host(self.ctx, B, _p(p), _p(x0), C.byref(opts), _p(x), _p(f), _p(lam),
-                                               status.ctypes.data_as(_ip), iters.ctypes.data_as(_ip), _p(kkt))
-        self._check(rc, "landing_solve_batch_host")
-        return dict(x=x, f=f, lam_g=lam, status=status, iters=iters, kkt=kkt)
+        out, ptrs = _solve_outputs(B, self.nx, self.ng)
+        self._check(self.lib.landing_solve_batch_host(self.ctx, B, _p(p), _p(x0), C.byref(opts), *ptrs), "landing_solve_batch_host")
+        return out
 
     def solve_stream_host(self, p, x0, opts=None, chunk=1024, lanes=2):
         """landing_solve_stream_host: any number of members, cut into chunks that go through a stream of `lanes` launches in flight"""
         p = np.ascontiguousarray(np.atleast_2d(p), float); x0 = np.ascontiguousarray(np.atleast_2d(x0), float)
         B = p.shape[0]
         opts = opts or self.default_opts()
-        x = np.zeros((B, self.nx)); f = np.zeros(B); lam = np.zeros((B, self.ng))
-        status = np.zeros(B, np.int32); iters = np.zeros(B, np.int32); kkt = np.zeros((B, 3))
-        rc = self.lib.landing_solve_stream_host(self.ctx, B, chunk, lanes, _p(p), _p(x0), C.byref(opts), _p(x), _p(f), _p(lam),
-                                                status.ctypes.data_as(_ip), iters.ctypes.data_as(_ip), _p(kkt))
-        self._check(rc, "landing_solve_stream_host")
-        return dict(x=x, f=f, lam_g=lam, status=status, iters=iters, kkt=kkt)
+        out, ptrs = _solve_outputs(B, self.nx, self.ng)
+        self._check(self.lib.landing_solve_stream_host(self.ctx, B, chunk, lanes, _p(p), _p(x0), C.byref(opts), *ptrs), "landing_solve_stream_host")
+        return out
 
     def stream(self, lanes=2):
         """landing_stream_create on this context: SolveStream with submit / wait / sync / close"""
@@ -451,67 +519,62 @@ class LandingLib:
         """the reference's solver-function call, batched: args = dict of the 21 MATLAB-shaped arrays (batch = last axis)"""
         a, keep, B = matlab_args21(self.N, args)
         opts = opts or self.default_opts()
-        x = np.zeros((B, self.nx)); f = np.zeros(B); status = np.zeros(B, np.int32); iters = np.zeros(B, np.int32); kkt = np.zeros((B, 3))
-        outs = (_p(x), _p(f), status.ctypes.data_as(_ip), iters.ctypes.data_as(_ip), _p(kkt))
+        out, ptrs = _solve_outputs(B, self.nx)
+        del out["lam_g"], ptrs[2]      # (this entry point has no multiplier output)
         if spelled_out:
-            rc = self.lib.landing_solve_21(self.ctx, B, *[getattr(a, n) for n in ARGS21], C.byref(opts), *outs)
+            rc = self.lib.landing_solve_21(self.ctx, B, *[getattr(a, n) for n in ARGS21], C.byref(opts), *ptrs)
         else:
-            rc = self.lib.landing_solve_args21(self.ctx, B, C.byref(a), C.byref(opts), *outs)
+            rc = self.lib.landing_solve_args21(self.ctx, B, C.byref(a), C.byref(opts), *ptrs)
         self._check(rc, "landing_solve_args21")
-        return dict(x=x, f=f, status=status, iters=iters, kkt=kkt)
+        return out
 
     def solve_args25(self, args, opts=None):
         """the N=41 script's solver-function call, batched: args = dict of its 25 MATLAB-shaped arrays (batch = last axis)"""
         a, keep, B = matlab_args25(self.N, args)
         opts = opts or self.default_opts()
-        x = np.zeros((B, self.nx)); f = np.zeros(B); lam = np.zeros((B, self.ng)); status = np.zeros(B, np.int32); iters = np.zeros(B, np.int32); kkt = np.zeros((B, 3))
-        rc = self.lib.landing_solve_args25(self.ctx, B, C.byref(a), C.byref(opts), _p(x), _p(f), _p(lam), status.ctypes.data_as(_ip), iters.ctypes.data_as(_ip), _p(kkt))
-        self._check(rc, "landing_solve_args25")
-        return dict(x=x, f=f, lam_g=lam, status=status, iters=iters, kkt=kkt)
+        out, ptrs = _solve_outputs(B, self.nx, self.ng)
+        self._check(self.lib.landing_solve_args25(self.ctx, B, C.byref(a), C.byref(opts), *ptrs), "landing_solve_args25")
+        return out
 
     def solve_args21_multi(self, args, devices, opts=None, one_call=False, want_lam=True):
         """the reference's solver-function call sharded over a device list from the C boundary (landing_multi_solve_args21 /
         landing_solve_21_multi): contiguous shards, one host thread + context per entry of `devices` (an index may repeat)"""
         a, keep, B = matlab_args21(self.N, args)
         opts = opts or self.default_opts()
-        x = np.zeros((B, self.nx)); f = np.zeros(B); status = np.zeros(B, np.int32); iters = np.zeros(B, np.int32); kkt = np.zeros((B, 3))
-        lam = np.zeros((B, self.ng)) if want_lam else None
-        outs = (_p(x), _p(f), _p(lam), status.ctypes.data_as(_ip), iters.ctypes.data_as(_ip), _p(kkt))
+        out, ptrs = _solve_outputs(B, self.nx, self.ng if want_lam else None)
         dev = (C.c_int * len(devices))(*devices)
         if one_call:
-            self.lib.landing_solve_21_multi.restype = C.c_int
-            rc = self.lib.landing_solve_21_multi(dev, len(devices), self.N, B, *[getattr(a, n) for n in ARGS21], C.byref(opts), *outs)
+            rc = self.lib.landing_solve_21_multi(dev, len(devices), self.N, B, *[getattr(a, n) for n in ARGS21], C.byref(opts), *ptrs)
         else:
-            self.lib.landing_multi_create.restype = C.c_void_p
             m = self.lib.landing_multi_create(self.N, dev, len(devices), C.byref(self.form))
             if not m:
                 raise RuntimeError("landing_multi_create: " + self.lib.landing_last_error().decode())
             try:
-                rc = self.lib.landing_multi_solve_args21(C.c_void_p(m), B, C.byref(a), C.byref(opts), *outs)
+                rc = self.lib.landing_multi_solve_args21(m, B, C.byref(a), C.byref(opts), *ptrs)
             finally:
-                self.lib.landing_multi_destroy(C.c_void_p(m))
+                self.lib.landing_multi_destroy(m)
         self._check(rc, "landing_multi_solve_args21")
-        return dict(x=x, f=f, lam_g=lam, status=status, iters=iters, kkt=kkt)
+        return out
 
     def riccati_gains_device(self, B, n, d_xref, d_fref, Ib3x3, mass, Q, r_diag, F, dt, rk4=False, d_P=0, d_K=0, d_A=0, d_B=0, stream=0):
         """landing_riccati_gains_batch: VBL linearisation + Riccati tracking gains along B sampled trajectories (device pointers)"""
         Ib3x3 = np.ascontiguousarray(Ib3x3, float); Q = np.ascontiguousarray(Q, float); F = np.ascontiguousarray(F, float); r = np.ascontiguousarray(r_diag, float)
         rc = self.lib.landing_riccati_gains_batch(self.ctx, B, n, d_xref, d_fref, _p(Ib3x3), float(mass), _p(Q), _p(r), _p(F), float(dt), int(bool(rk4)),
-                                                  d_P or None, d_K or None, d_A or None, d_B or None, stream or None)
+                                                  _n(d_P), _n(d_K), _n(d_A), _n(d_B), _n(stream))
         self._check(rc, "landing_riccati_gains_batch")
 
     def sample_reference_device(self, B, d_x, d_p, dt_r, n, d_xref=0, d_fref=0, stream=0):
         """landing_sample_reference_batch: B solutions (solver layout) onto the uniform Riccati grid of n points, step dt_r, each member along the
         time grid its own p carries (device pointers).  The last interval is never entered: points past the second-to-last knot extrapolate."""
-        rc = self.lib.landing_sample_reference_batch(self.ctx, B, d_x or None, d_p or None, float(dt_r), int(n), d_xref or None, d_fref or None, stream or None)
+        rc = self.lib.landing_sample_reference_batch(self.ctx, B, _n(d_x), _n(d_p), float(dt_r), int(n), _n(d_xref), _n(d_fref), _n(stream))
         self._check(rc, "landing_sample_reference_batch")
 
     def tracking_gains_device(self, B, d_x, d_p, dt_r, n, Ib3x3, mass, Q, r_diag, F, rk4=False, d_status=0, d_P=0, d_K=0, d_A=0, d_B=0, d_xref=0, d_fref=0, stream=0):
         """landing_tracking_gains_batch: resampling + Riccati tracking gains of a solved batch on one stream (device pointers).  With d_status,
         members that did not converge get zeros; d_xref / d_fref = 0 keeps the sampled reference in the context."""
         Ib3x3 = np.ascontiguousarray(Ib3x3, float); Q = np.ascontiguousarray(Q, float); F = np.ascontiguousarray(F, float); r = np.ascontiguousarray(r_diag, float)
-        rc = self.lib.landing_tracking_gains_batch(self.ctx, B, d_x or None, d_p or None, d_status or None, float(dt_r), int(n), _p(Ib3x3), float(mass), _p(Q), _p(r), _p(F),
-                                                   int(bool(rk4)), d_P or None, d_K or None, d_A or None, d_B or None, d_xref or None, d_fref or None, stream or None)
+        rc = self.lib.landing_tracking_gains_batch(self.ctx, B, _n(d_x), _n(d_p), _n(d_status), float(dt_r), int(n), _p(Ib3x3), float(mass), _p(Q), _p(r), _p(F),
+                                                   int(bool(rk4)), _n(d_P), _n(d_K), _n(d_A), _n(d_B), _n(d_xref), _n(d_fref), _n(stream))
         self._check(rc, "landing_tracking_gains_batch")
 
     def tracking_gains_host(self, x, p, dt_r, n, Ib3x3, mass, Q, r_diag, F, rk4=False, status=None, want=("K",)):
@@ -522,21 +585,21 @@ class LandingLib:
         Ib3x3 = np.ascontiguousarray(Ib3x3, float); Q = np.ascontiguousarray(Q, float); F = np.ascontiguousarray(F, float); r = np.ascontiguousarray(r_diag, float)
         shapes = dict(P=(B, n, 24, 24), K=(B, n, 12, 24), A=(B, n, 24, 24), B=(B, n, 24, 12), xref=(B, n, 24), fref=(B, n, 12))
         out = {k: (np.full(shapes[k], np.nan) if k in want else None) for k in shapes}
-        rc = self.lib.landing_tracking_gains_host(self.ctx, B, _p(x), _p(p), None if status is None else status.ctypes.data_as(_ip), float(dt_r), int(n), _p(Ib3x3),
+        rc = self.lib.landing_tracking_gains_host(self.ctx, B, _p(x), _p(p), _pi(status), float(dt_r), int(n), _p(Ib3x3),
                                                   float(mass), _p(Q), _p(r), _p(F), int(bool(rk4)), *[_p(out[k]) for k in ("P", "K", "A", "B", "xref", "fref")])
         self._check(rc, "landing_tracking_gains_host")
         return {k: v for k, v in out.items() if v is not None}
 
     # ---- device-pointer entry points (integers = device addresses, e.g. torch tensor.data_ptr()) --
     def eval_device(self, B, d_x, d_p, d_lam_f=0, d_lam_g=0, d_f=0, d_g=0, d_grad_f=0, d_jac=0, d_hess=0, d_ggx=0, d_ggp=0, stream=0):
-        rc = self.lib.landing_eval_batch(self.ctx, B, d_x, d_p, d_lam_f or None, d_lam_g or None, d_f or None, d_g or None,
-                                         d_grad_f or None, d_jac or None, d_hess or None, d_ggx or None, d_ggp or None, stream or None)
+        rc = self.lib.landing_eval_batch(self.ctx, B, d_x, d_p, _n(d_lam_f), _n(d_lam_g), _n(d_f), _n(d_g),
+                                         _n(d_grad_f), _n(d_jac), _n(d_hess), _n(d_ggx), _n(d_ggp), _n(stream))
         self._check(rc, "landing_eval_batch")
 
     def bounds_device(self, B, d_p, d_lbg, d_ubg, stream=0):
-        self._check(self.lib.landing_bounds_batch(self.ctx, B, d_p, d_lbg, d_ubg, stream or None), "landing_bounds_batch")
+        self._check(self.lib.landing_bounds_batch(self.ctx, B, d_p, d_lbg, d_ubg, _n(stream)), "landing_bounds_batch")
 
     def solve_device(self, B, d_p, d_x0, opts, d_x, d_f=0, d_lam_g=0, d_status=0, d_iters=0, d_kkt=0, stream=0):
-        rc = self.lib.landing_solve_batch(self.ctx, B, d_p, d_x0, C.byref(opts), d_x, d_f or None, d_lam_g or None,
-                                          d_status or None, d_iters or None, d_kkt or None, stream or None)
+        rc = self.lib.landing_solve_batch(self.ctx, B, d_p, d_x0, C.byref(opts), d_x, _n(d_f), _n(d_lam_g),
+                                          _n(d_status), _n(d_iters), _n(d_kkt), _n(stream))
         self._check(rc, "landing_solve_batch")

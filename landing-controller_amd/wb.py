@@ -8,10 +8,10 @@ Host side of include/landing_nlp.h's landing_wb_* entry points: per iteration on
     sqp = WholeBodySQP(lib, rbd, N=40, dt=0.015, Q=..., R=..., QN=...)
     out = sqp.solve(x0, u_init, xref, f_foot, iters=5)        # x [B, N+1, 36], u [B, N, 12], cost history [iters+1, B]
 """
-import ctypes as C
-
 import numpy as np
 import torch
+
+from .capi import _p
 
 
 class WholeBodySQP:
@@ -21,17 +21,11 @@ class WholeBodySQP:
         (landing_wb_select) -- no host synchronisation inside an iteration; False = the round-3 loop (one launch + torch.where merges per step length)"""
         self.L, self.R_, self.N, self.dt, self.dev = lib, rbd, int(N), float(dt), torch.device(device)
         self.fused = bool(fused)
-        lib.lib.landing_wb_set_integrator.argtypes = [C.c_void_p, C.c_int]
         lib._check(lib.lib.landing_wb_set_integrator(lib.ctx, 1 if semi_implicit else 0), "landing_wb_set_integrator")
-        lib.lib.landing_wb_select.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 10
-        lib.lib.landing_wb_skip_taken.argtypes = [C.c_void_p, C.c_void_p]
         self.Q = np.ascontiguousarray(Q, float); self.R = np.ascontiguousarray(R, float); self.QN = np.ascontiguousarray(QN, float)
         assert self.Q.shape == (36,) and self.R.shape == (12,) and self.QN.shape == (36,)
         self.alphas = torch.tensor(list(alphas), dtype=torch.float64, device=self.dev)
-        vp, dp = C.c_void_p, C.POINTER(C.c_double)
-        lib.lib.landing_wb_backward.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp, vp, dp, dp, dp, vp, vp, vp, vp, vp]
-        lib.lib.landing_wb_rollout.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_double, vp, vp, vp, vp, vp, vp, dp, dp, dp, vp, vp, vp, vp]
-        self._w = [a.ctypes.data_as(dp) for a in (self.Q, self.R, self.QN)]
+        self._w = [_p(a) for a in (self.Q, self.R, self.QN)]
 
     def _stream(self):
         return torch.cuda.current_stream().cuda_stream if self.dev.type == "cuda" else None

@@ -10,7 +10,7 @@ import pytest
 
 import actuator_reference as ar
 from conftest import GOLDEN, ROOT, lc
-from test_pipeline_cpu import _header_fields
+from header_decls import _header_fields
 
 PKG = os.path.join(ROOT, "landing-controller_amd")
 EMU = os.path.join(ROOT, "tests", "emu", "liblanding_emu.so")

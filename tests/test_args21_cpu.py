@@ -146,7 +146,6 @@ def test_multi_device_rejects_the_25_argument_formulation_and_null_arguments(lib
     a.mass = None
     x = np.zeros((B, L.nx))
     dev = (C.c_int * 2)(0, 0)
-    L.lib.landing_multi_create.restype = C.c_void_p
     m = L.lib.landing_multi_create(N, dev, 2, C.byref(L.form))
     assert m
     o = L.default_opts()

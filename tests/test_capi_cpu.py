@@ -75,8 +75,7 @@ def test_ccc_dropin_metadata(built):
     """nlp_quad_SRBM_mi355x.so = the NLP of the reference's N=41 script (generate_quadruped_SRBM_CCC.m:340-341): x 1452, its own parameter
     vector p 37N+112 = 1592, g 4172, the Hessian in the extended (running-cost) pattern -- upper triangular, rows sorted"""
     lib = C.CDLL(os.path.join(PKG, "nlp_quad_SRBM_mi355x.so"))
-    main = C.CDLL(os.path.join(PKG, "liblanding_mi355x.so"))
-    main.landing_nnz_hess_rc.restype = C.c_longlong
+    main = lc("capi").load()
     f = lib.nlp_f_sparsity_in; f.restype = C.POINTER(C.c_longlong); f.argtypes = [C.c_longlong]
     assert [f(0)[i] for i in range(2)] == [1452, 1] and [f(1)[i] for i in range(4)] == [1592, 1, 0, 1592]
     h = lib.nlp_hess_l_sparsity_out; h.restype = C.POINTER(C.c_longlong); h.argtypes = [C.c_longlong]
@@ -160,8 +159,6 @@ def test_solver_opts_mirror_matches_the_header():
     assert (w.bound_push, w.bound_frac, w.mu_init, w.restart_period, w.max_iter, w.clip_k, w.fresh_restart, w.factor_fp32) == (1e-4, 1e-4, 1e-4, 0, 14, 0, 0, 0)
     assert (w.dual_step_cap, w.slack_corr, w.watchdog, w.barrier_smax, w.theta_floor, w.feas_phase) == (1.0, 0.9, 3, 1.0, 30.0, 0)
     # the header declares the fields in the same order
-    import re
-    hdr = open(os.path.join(ROOT, "include", "landing_nlp.h")).read()
-    body = hdr[hdr.index("typedef struct {\n  double tol;"):hdr.index("} landing_solver_opts;")]
-    names = re.findall(r"^  (?:int|double) (\w+);", body, flags=re.M)
+    from header_decls import _header_fields
+    names = _header_fields("landing_solver_opts")
     assert names == [n for n, _ in capi.SolverOpts._fields_], names

@@ -25,16 +25,7 @@ def _p(a):
 @pytest.fixture(scope="module")
 def emu():
     subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
-    lib = lc("capi").load(EMU)
-    lib.hip_emu_live_blocks.restype = C.c_longlong
-    lib.hip_emu_fail_alloc.restype = C.c_longlong
-    lib.hip_emu_fail_alloc.argtypes = [C.c_longlong]
-    vp = C.c_void_p
-    lib.landing_kinodyn_pattern.argtypes = [vp, C.c_int, C.c_int, _lp, _lp, _lp]
-    lib.landing_kinodyn_block_nonzeros.argtypes = [vp, _ip, _ip, C.c_void_p]
-    lib.landing_kinodyn_casadi_pattern.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_lp), C.POINTER(_lp), _lp]
-    lib.landing_kinodyn_solve_batch_host.argtypes = [vp, C.c_int, C.c_int, C.POINTER(lc("rbd").KinodynParams)] + [_dp] * 4 + [C.POINTER(lc("capi").SolverOpts)] + [_dp] * 3 + [_ip] * 2 + [_dp]
-    return lib
+    return lc("capi").load(EMU)      # (the table of capi.py declares every entry point and the emulation's counters)
 
 
 RC = dict(QX=[1.0] * 12, Qc=[0.1] * 3, Qf=[0.01] * 3)

@@ -68,7 +68,6 @@ def test_bounds_entry_point_equals_python_mirror():
             rep([-10, -10, -10, -.5, -.5, -.5]), rep([10, 10, 10, .5, .5, .5]), rep(kd.JPOS_MIN), rep(kd.JPOS_MAX), np.ascontiguousarray(kb), np.full(B, 0.4)]
     ng = kd.dims(N)[1]
     lb = np.zeros((B, ng)); ub = np.zeros((B, ng))
-    raw.landing_kinodyn_bounds.argtypes = [C.c_int, C.c_int, C.c_void_p] + [dp] * 14
     assert raw.landing_kinodyn_bounds(N, B, None, *[a.ctypes.data_as(dp) for a in args], lb.ctypes.data_as(dp), ub.ctypes.data_as(dp)) == 0
     for b in range(B):
         l0, u0 = kd.bounds(N, q[b], qd[b], ci[b], kb[b])
@@ -201,8 +200,6 @@ def test_c_model_builder_equals_python_model_and_gateway_compiles(tmp_path):
     raw = lc("capi").load(os.path.join(PKG, "liblanding_mi355x.so"))
     rbd = lc("rbd")
     m = rbd.RbdModel()
-    raw.landing_rbd_model_mc3d.argtypes = [C.POINTER(rbd.RbdModel)]
-    raw.landing_rbd_model_mc3d.restype = None
     raw.landing_rbd_model_mc3d(C.byref(m))
     ref = rbd.quad3d_model()
     for name, _ in rbd.RbdModel._fields_:
@@ -224,11 +221,7 @@ def test_kinodyn_bounds_forms_match_the_two_reference_scripts():
     capi, kd = lc("capi"), lc("kinodyn")
     lib = capi.load()
     N, B = 20, 2
-
-    class Form(C.Structure):
-        _fields_ = [("comp_eps", C.c_double), ("slip_eps", C.c_double), ("fk_band", C.c_double), ("kin_box_x0", C.c_double), ("kin_box_y0", C.c_double),
-                    ("kin_box_y_in", C.c_double), ("kin_box_z_lo", C.c_double), ("kin_box_z_hi", C.c_double), ("tau_max", C.c_double * 3)]
-    fd, fk = Form(), Form()
+    fd, fk = capi.KinodynForm(), capi.KinodynForm()
     lib.landing_kinodyn_form_default(C.byref(fd)); lib.landing_kinodyn_form_knitro(C.byref(fk))
     assert (fd.kin_box_x0, fd.kin_box_y0, fk.kin_box_x0, fk.kin_box_y0) == (0.125, 0.10, 0.125, 0.125)
     for f in ("comp_eps", "slip_eps", "fk_band", "kin_box_y_in", "kin_box_z_lo", "kin_box_z_hi"):

@@ -4,13 +4,13 @@ pairs kernel against dataset.training_pairs, the select rule, the plumbing and a
 against its ctypes mirror, and the MATLAB gateway compiled against tests/stubs/mex.h."""
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT, lc
+from header_decls import _header_fields
 
 PKG = os.path.join(ROOT, "landing-controller_amd")
 EMU = os.path.join(ROOT, "tests", "emu", "liblanding_emu.so")
@@ -186,19 +186,6 @@ def test_pipeline_batch_plumbing_on_the_emulation():
     with pytest.raises(RuntimeError, match="N <= 64"):
         R4.pipeline_device(1, _a(np.zeros(4096)), _a(np.zeros(4096)), None, *[_a(np.zeros(8192)) for _ in range(5)])
     L4.close()
-
-
-def _header_fields(struct_name):
-    src = open(os.path.join(ROOT, "include", "landing_nlp.h")).read()
-    m = re.search(r"typedef struct \{([^{}]*)\} " + struct_name + ";", src)
-    assert m, struct_name
-    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if decl:
-            names += [re.sub(r"\[.*\]", "", v).strip(" *") for v in decl.split(None, 1)[1].split(",")]
-    return names
 
 
 def test_header_options_struct_equals_the_ctypes_mirror(emu):

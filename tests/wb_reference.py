@@ -61,13 +61,6 @@ class WbCalls:
     def __init__(self, L, mem, model=None):
         self.L, self.mem = L, mem
         self.rbd = lc("rbd").Rbd(L, model=model)
-        vp, dp, ci, cd = C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_double
-        lib = L.lib
-        lib.landing_wb_set_integrator.argtypes = [vp, ci]
-        lib.landing_wb_skip_taken.argtypes = [vp, vp]
-        lib.landing_wb_select.argtypes = [vp, ci, ci, ci] + [vp] * 10
-        lib.landing_wb_backward.argtypes = [vp, ci, ci, cd, cd, vp, vp, vp, vp, vp, dp, dp, dp, vp, vp, vp, vp, vp]
-        lib.landing_wb_rollout.argtypes = [vp, ci, ci, ci, vp, cd, vp, vp, vp, vp, vp, vp, dp, dp, dp, vp, vp, vp, vp]
 
     def set_integrator(self, semi):
         self.L._check(self.L.lib.landing_wb_set_integrator(self.L.ctx, 1 if semi else 0), "landing_wb_set_integrator")
