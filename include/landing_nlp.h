@@ -719,7 +719,8 @@ int landing_kinodyn_block_nonzeros(landing_ctx* ctx, int* nnz_mid, int* nnz_last
  *   member blocks (the callers' B, then the portfolio's clone slots).  Member m's block starts at d_ws + m * stride.  LANDING_E_ARG when no such solve has run, or when the
  *   last one failed before all its launches were queued (the view is valid only for a solve that returned 0).
  * landing_debug_kd_layout: for a horizon N, offsets[LANDING_KD_LAYOUT_N] (doubles from the start of a member's block) of the arrays
- *     x, dx, g, s, ds, zL, zU, y, yn, sig, rho, gc          (in this order; x, dx: nx doubles; g .. rho: ng doubles; gc: N x (60 x 60 + 60), see below)
+ *     x, dx, g, s, ds, zL, zU, y, yn, sig, rho, gc, en, ep, wn, wp    (in this order; x, dx: nx doubles; g .. rho: ng doubles; gc: N x (60 x 60 + 60), see below;
+ *     en .. wp: ng doubles, the feasibility phase's violation variables of the lower / upper side of every inequality row and their multipliers)
  *   and, when not NULL, the offset of the member's iteration state and the member stride.  Read off kd_carve itself.  After a solve the block holds x, g, s, zL, zU,
  *   y, sig, rho of the LAST iterate and dx, ds, yn (the defect rows' multipliers; other rows of yn are not meaningful), gc of the last Newton step: per interval k the
  *   inequality rows' J_I' Sigma J_I (60 x 60, row major, over v = (X_k, c_k, f_k, jpos_k, c_k+1)) and J_I' rho (60).  The outputs of the solve overwrite y[0:24].
@@ -728,7 +729,7 @@ int landing_kinodyn_block_nonzeros(landing_ctx* ctx, int* nnz_mid, int* nnz_last
  *   [5] it  iterations counted   [6] nfact  factorisations of the whole solve   [7] nreset   [8] last_reset_it   [9] feas  1 inside the feasibility phase
  *   [10] status   [11] pending  1: the inertia correction waits for the next launch   [12] omt  > 0: clip_k rule in force in the last step   [13] s_corr
  *   [14] done   [15] reg_it  iteration of the last regularised factorisation */
-#define LANDING_KD_LAYOUT_N 12
+#define LANDING_KD_LAYOUT_N 16
 #define LANDING_KD_STATE_N 16
 int landing_debug_kd_workspace(landing_ctx* ctx, double** d_ws, unsigned long long* stride, int* N, int* members);
 int landing_debug_kd_layout(int N, unsigned long long* offsets, unsigned long long* state_offset, unsigned long long* stride);
@@ -901,6 +902,15 @@ int landing_wb_select(landing_ctx* ctx, int B, int N, int nalpha, const double* 
  * wall-clock ticks: eval, error, sigma/rho, backward, forward, dual, line search, accept; then counts of
  * factorisations, trial points, iterations); NULL disables. */
 int landing_set_profile_buffer(landing_ctx* ctx, double* d_prof);
+/* development aid, not an option: cap > 0: no solve of this context -- SRBM or kinodynamic, feasibility phases included -- runs beyond `cap` iterations in
+ * total (the value replaces the solvers' own hard limit of 3 max_iter; an iteration limit in force beyond it is cut back to it); 0 restores the default.
+ * With max_iter = M, feas_phase = 1, feas_jam = 0 and cap = M + 1 + j a member that has not converged after M iterations enters the feasibility phase at x_M
+ * (the entry counts as one iteration) and stops after exactly j steps of the phase, j = 0 right behind the entry state -- as long as M + 1 + j <= 2 M, the
+ * phase's own limit.  Two such runs one apart share their trajectory: tests/test_solver_feas_step_cpu.py and tests/test_gpu_solver_feas_step.py check the phase's
+ * Newton step and update that way against an independent solve of the elastic problem's primal-dual system (tests/elastic_newton_reference.py).  A hand-over
+ * (into the phase, out of it, a restart) counts as an iteration without a step: a member handed back by the phase exactly at the cap reports iters = cap + 1 and
+ * has taken no step beyond the cap.  With no cap set nothing changes. */
+int landing_debug_iter_cap(landing_ctx* ctx, int cap);
 /* diagnostic: device pointer and per-member stride (doubles) of the solver workspace left by the last landing_solve_batch
  * (layout: landing-controller_amd/csrc/solver_kernels.hip, carve(); mirrored for Python by workspace_offsets() in
  * landing-controller_amd/capi.py, which a test holds against this stride).  Member m's block starts at d_ws + m * stride, whatever
@@ -912,7 +922,8 @@ int landing_set_profile_buffer(landing_ctx* ctx, double* d_prof);
  *   [0] mu       barrier parameter the last step was computed with
  *   [1] delta    regularisation delta_w of the last factorisation tried (the successful one, if the step was computed)
  *   [2] alpha    primal step length of the last accepted step          [3] a_du   its dual step length
- *   [4] live     0: the first instance (s, zL, zU, y, sig, rho) holds the iterate; 1: the second one (s2, ...) does
+ *   [4] live + 2 feas   live = 0: the first instance (s, zL, zU, y, sig, rho) holds the iterate; 1: the second one (s2, ...) does;
+ *                feas = 1: the solve ended inside the feasibility phase (the last step, if any, was a step of the elastic problem; en, ep, wn, wp are live)
  *   [5] it       iterations counted (= iters)   [6] omt   > 0: the clip_k rule was in force in the last step   [7] s_corr
  * tests/test_solver_step_cpu.py and tests/test_gpu_solver_step.py use it to check the step against an independent KKT solve. */
 int landing_debug_workspace(landing_ctx* ctx, double** d_ws, unsigned long long* stride);

@@ -200,6 +200,7 @@ SIGNATURES = {
     "landing_wb_select": (_ci, [_vp, _ci, _ci, _ci] + [_vp] * 10),
     # diagnostics
     "landing_set_profile_buffer": (_ci, [_vp, _vp]),
+    "landing_debug_iter_cap": (_ci, [_vp, _ci]),
     "landing_debug_workspace": (_ci, [_vp, C.POINTER(_vp), _ullp]),
     "landing_debug_solver_tables": (_ci, [_vp, _ci, _vp, _ullp]),
     "landing_debug_kd_workspace": (_ci, [_vp, C.POINTER(_vp), _ullp, _ip, _ip]),
@@ -210,11 +211,13 @@ SIGNATURES.update({n: (_ll, [_ci]) for n in ("landing_nx", "landing_ng", "landin
                                              "landing_sweep_bytes_per_member", "landing_kinodyn_casadi_np")})
 # what only the host-emulation build of the same sources exports (tests/emu); bound where present
 EMU_HOOKS = {"landing_emu_set_fused": (None, [_ci]), "landing_emu_accept_counts": (_ci, [_ci, _ip]),
+             "landing_emu_el_row": (None, [_cd] * 8 + [_dp]),
              "hip_emu_live_blocks": (_ll, []), "hip_emu_fail_alloc": (_ll, [_ll])}
 
 
 # Sizes the solver kernel's workspace layout is built from (csrc/solver_kernels.hip: RUNC, RIC_STRIDE, RCG, EXIT_REC)
 WS_RUNC, WS_RIC_STRIDE, WS_RCG, WS_EXIT_REC = 48, 1200, 36, 8
+# ("live" holds live + 2 feas: bit 0 = which instance of the row arrays holds the iterate, bit 1 = the solve ended inside the feasibility phase)
 EXIT_RECORD = ("mu", "delta", "alpha", "a_du", "live", "it", "omt", "s_corr")
 
 

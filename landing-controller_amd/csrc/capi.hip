@@ -134,6 +134,7 @@ struct landing_ctx {
   DevBuf<int> d_edge_map;
   landing::SolverWorkspace ws;
   double* d_prof = nullptr;     // the caller's (landing_set_profile_buffer)
+  int iter_cap = 0;             // development aid (landing_debug_iter_cap): > 0 replaces the solvers' hard iteration limit
   DevBuf<double> d_vbl;
   double* h_vbl = nullptr; hipEvent_t vbl_copied = nullptr;      // pinned staging block of landing_riccati_gains_batch and the event behind its copy
   DevBuf<double> d_gref;      // landing_tracking_gains_batch (gains_capi.inc): [xref B x n x 24 | fref B x n x 12] when the caller keeps neither, grown on demand

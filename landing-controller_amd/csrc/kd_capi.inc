@@ -314,7 +314,7 @@ int landing_kinodyn_solve_batch(landing_ctx* ctx, int B, int N, const landing_ki
     HIP_TRY(ctx->d_kd_done.grow(nflag));
   }
   landing::KdSolveArgs A;
-  A.model = ctx->d_rbd.get(); A.B = BT; A.N = N; A.o = o;
+  A.model = ctx->d_rbd.get(); A.B = BT; A.N = N; A.o = o; A.iter_cap = ctx->iter_cap;
   A.B0 = B; A.F = cloneF > 0 ? cloneF : 1; A.m_lo = 0;
   A.src = ctx->d_kd_done.get() + BT; A.win = S > 0 ? A.src + S : nullptr; A.cloned = A.src + S + B; A.win_prev = A.cloned + B; A.cond_list = A.src + S + 3 * B;
   // the clones' option sets: what decided the outliers of five bench batches in 28 .. 73 iterations (profiles/r05_ab_experiments.txt, tools/dev/kd_variants.py) --
@@ -664,7 +664,7 @@ int landing_debug_kd_layout(int N, unsigned long long* offsets, unsigned long lo
   std::vector<double> block(landing::kd_ws_stride(N));
   double* const base = block.data();
   const landing::KdMem M = landing::kd_carve(N, base);
-  const double* const arr[LANDING_KD_LAYOUT_N] = {M.x, M.dx, M.g, M.s, M.ds, M.zL, M.zU, M.y, M.yn, M.sig, M.rho, M.gc};
+  const double* const arr[LANDING_KD_LAYOUT_N] = {M.x, M.dx, M.g, M.s, M.ds, M.zL, M.zU, M.y, M.yn, M.sig, M.rho, M.gc, M.en, M.ep, M.wn, M.wp};
   for (int i = 0; i < LANDING_KD_LAYOUT_N; ++i) offsets[i] = (unsigned long long)(arr[i] - base);
   if (state_offset) *state_offset = (unsigned long long)(reinterpret_cast<const double*>(M.st) - base);
   if (stride) *stride = (unsigned long long)landing::kd_ws_stride(N);

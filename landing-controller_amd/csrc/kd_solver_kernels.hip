@@ -110,6 +110,7 @@ static_assert(KD_JP_NNZ == KD_JC_NNZ, "one capacity");
 
 struct KdSolveArgs {
   const RbdModel* model; KdNlpParams P; int B, N; landing_solver_opts o;
+  int iter_cap;            // development aid (landing_debug_iter_cap): > 0 replaces the hard iteration limit
   const double* x0;        // [B][nx]
   const double* lb; const double* ub;      // [B][ng]  lbg / ubg (the script's values: kinodyn.py / landing_kinodyn_bounds)
   const double* cost;      // [B][24]  QN (12) | Xref(:, end) (12)   -- the terminal cost of :83-86
@@ -700,6 +701,7 @@ __global__ void __launch_bounds__(KD_THREADS) landing_kd_init_kernel(KdSolveArgs
   KdState& K = KSH.ks;
   if (tid == 0) {
     ipm_init(K, o);
+    if (A.iter_cap > 0) { K.hard_lim = A.iter_cap; if (K.lim > K.hard_lim) K.lim = K.hard_lim; }      // development aid (landing_debug_iter_cap)
     K.fval = 0.0; K.done = 0; K.nfact = 0; K.ntrial = 0; K.reg_it = -1000; K.pending = 0; K.stage = 0;
     for (int i = 0; i < 8; ++i) K.prof[i] = 0.0;
   }

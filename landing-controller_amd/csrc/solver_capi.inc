@@ -332,7 +332,7 @@ int landing_solve_batch(landing_ctx* ctx, int B, const double* d_p, const double
   A.status = d_status; A.iters = d_iters; A.kkt = d_kkt; A.ws = ctx->ws.buf.get(); A.ws_stride = landing::member_stride(ctx->L);
   A.ctab = ctx->ws.d_ctab.get(); A.ctype = ctx->ws.d_ctype.get(); A.c_ml = ctx->ws.c_ml; A.c_mid = ctx->ws.c_mid; A.ccomb = ctx->ws.d_ccomb.get();
   A.rterm = ctx->ws.d_rterm.get(); A.rlen = ctx->ws.rlen;
-  A.prof = ctx->d_prof;
+  A.prof = ctx->d_prof; A.iter_cap = ctx->iter_cap;
   A.edge_map = ctx->d_edge_map.get();
   A.order = nullptr;
   // hard-first order: pointless while every member is resident from the start (2 workgroups on each of the 256 CUs), and the
@@ -351,6 +351,14 @@ int landing_solve_batch(landing_ctx* ctx, int B, const double* d_p, const double
 int landing_set_profile_buffer(landing_ctx* ctx, double* d_prof) {
   if (!ctx) return fail(LANDING_E_ARG, "landing_set_profile_buffer: bad argument");
   ctx->d_prof = d_prof;
+  return 0;
+}
+
+// development aid: total iteration cap of every later solve of the context (SRBM and kinodynamic, phases included); 0 = the default
+int landing_debug_iter_cap(landing_ctx* ctx, int cap) {
+  if (!ctx || cap < 0) return fail(LANDING_E_ARG, "landing_debug_iter_cap: bad argument");
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  ctx->iter_cap = cap;
   return 0;
 }
 

@@ -83,6 +83,14 @@ extern "C" int landing_emu_accept_counts(int m, int* counts) {
   for (int i = 0; i < EMU_ACC_N; ++i) counts[i] = emu_acc[m][i];
   return 0;
 }
+// the row algebra of the feasibility phase on its own (ipm_core.hpp): out = dz, dw, dn, da of el_step and the side's sigma, rho of el_point_side -- a unit check holds
+// them against a dense solve of the side's three equations at states with z + w != rho_pen, which the solvers' trajectories hardly ever visit
+extern "C" void landing_emu_el_row(double sd, double a, double n, double z, double w, double mu, double rho_pen, double ds, double* out) {
+  const ElStep e = el_step(sd, a, n, z, w, mu, rho_pen, ds);
+  ElAcc acc{}; double sg = 0.0, rh = 0.0;
+  el_point_side(acc, sd, a, n, z, w, mu, rho_pen, sg, rh);
+  out[0] = e.dz; out[1] = e.dw; out[2] = e.dn; out[3] = e.da; out[4] = sg; out[5] = rh;
+}
 #else
 #define LANDING_EMU_COUNT(m, what) ((void)0)
 #define LANDING_EMU_FUSED_ON true
@@ -90,6 +98,7 @@ extern "C" int landing_emu_accept_counts(int m, int* counts) {
 
 struct SolveArgs {
   Layout L; int B; landing_solver_opts o; double* prof;
+  int iter_cap;      // development aid (landing_debug_iter_cap): > 0 replaces the hard iteration limit
   const double* p; const double* x0;
   double* x_out; double* f_out; double* lam_out; int* status; int* iters; double* kkt;
   double* ws; size_t ws_stride;
@@ -1257,6 +1266,7 @@ __global__ void __launch_bounds__(SOLVER_THREADS, SOLVER_MIN_WAVES) landing_ipm_
 
   if (lane == 0) {
     ipm_init(K, o);
+    if (A.iter_cap > 0) { K.hard_lim = A.iter_cap; if (K.lim > K.hard_lim) K.lim = K.hard_lim; }      // development aid (landing_debug_iter_cap)
     K.tp = A.prof ? (long long)wall_clock64() : 0;
     S.clip_now = 0; S.jamrun = 0; S.fact_failed = 0; S.first_trial = 0; S.fast = 0;
   }
@@ -1727,7 +1737,7 @@ __global__ void __launch_bounds__(SOLVER_THREADS, SOLVER_MIN_WAVES) landing_ipm_
   if (A.prof && lane == 0) { S.prof[PH_NITER] = (double)K.it; for (int i = 0; i < PH_COUNT; ++i) A.prof[(size_t)m * PH_COUNT + i] = S.prof[i]; }
   if (lane == 0) {      // exit record (EXIT_REC): M still holds the instances as carve() laid them out, S.M the live ones
     double* rec = M.y2 + ng;
-    rec[0] = K.mu; rec[1] = K.delta; rec[2] = K.alpha; rec[3] = K.a_du; rec[4] = (S.M.s == M.s) ? 0.0 : 1.0; rec[5] = (double)K.it; rec[6] = K.omt; rec[7] = K.s_corr;
+    rec[0] = K.mu; rec[1] = K.delta; rec[2] = K.alpha; rec[3] = K.a_du; rec[4] = ((S.M.s == M.s) ? 0.0 : 1.0) + (K.feas ? 2.0 : 0.0); rec[5] = (double)K.it; rec[6] = K.omt; rec[7] = K.s_corr;
   }
 
   // -------------------------------------------------------------------- outputs

@@ -292,7 +292,7 @@ class Rbd:
         return (e[:n0.value, 0], e[:n0.value, 1]), (e[n0.value:, 0], e[n0.value:, 1])
 
     # ---- diagnostics: the workspace the refinement solve leaves behind (include/landing_nlp.h landing_debug_kd_*) ----
-    KD_LAYOUT = ("x", "dx", "g", "s", "ds", "zL", "zU", "y", "yn", "sig", "rho", "gc")
+    KD_LAYOUT = ("x", "dx", "g", "s", "ds", "zL", "zU", "y", "yn", "sig", "rho", "gc", "en", "ep", "wn", "wp")
     KD_STATE = ("mu", "delta", "delta_last", "alpha", "a_du", "it", "nfact", "nreset", "last_reset_it", "feas", "status", "pending", "omt", "s_corr", "done", "reg_it")
     KD_GC = 60 * 60 + 60
 

@@ -65,10 +65,12 @@ def member_view(run, b):
     w, off = run["ws"][b], run["off"]
     raw = lambda n: w[off[n][0]:off[n][0] + off[n][1]]
     rec = dict(zip(lc("capi").EXIT_RECORD, raw("rec")))
-    assert rec["live"] in (0.0, 1.0)
+    assert rec["live"] in (0.0, 1.0, 2.0, 3.0)      # live + 2 feas (include/landing_nlp.h, EXIT RECORD)
+    rec["feas"] = int(rec["live"]) >> 1; rec["live"] = float(int(rec["live"]) & 1)
     live = "2" if rec["live"] else ""
-    v = {n: raw(n) for n in ("dx", "ds", "yn")}
+    v = {n: raw(n) for n in ("dx", "ds", "yn", "en", "ep", "wn", "wp")}
     v.update({n: raw(n + live) for n in ("s", "zL", "zU", "y")})
+    v["g"] = raw("gt" if rec["live"] else "g")
     return v, rec
 
 

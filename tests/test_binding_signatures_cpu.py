@@ -31,7 +31,7 @@ def _kind(t):
 def test_parser_reads_every_prototype_of_the_header():
     """the names followed by `(` anywhere in the header (what test_library_exports_every_declared_symbol looks for) are exactly the parsed prototypes"""
     names = set(re.findall(r"\b(landing_[a-z0-9_]+)\s*\(", open(H.HEADER).read()))
-    assert set(H.prototypes()) == names and len(names) >= 101
+    assert set(H.prototypes()) == names and len(names) >= 102
     assert sorted(H.struct_names()) == sorted(MIRRORS)
 
 
