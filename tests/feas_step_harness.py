@@ -7,10 +7,7 @@ Tolerances: the step is held to newton_reference's bound (16 x the better of two
 that bound PROPAGATED: a direction the kernel eliminates (dn, dzL, dwn, ...) depends linearly on ds, with the slope k the reference reads off the row's own 3 x 3 block,
 so its bound is |k| x (bound of ds), and an updated value v + step * d is held to step * |k| * bound_ds + 4 eps (|v| + |step * d|).
 """
-import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 
@@ -18,6 +15,7 @@ import elastic_newton_reference as er
 import newton_reference as nr
 import solver_step_harness as H
 from conftest import lc
+from emu_support import EMU_LIB, load_runs, pool_map, run_workers, save_runs, worker_main
 
 EPS = np.finfo(float).eps
 PAIR_J = (0, 1, 2, 5, 12, 25)      # pairs (j, j + 1): 0 = the first step of the phase, from the entry state
@@ -184,7 +182,7 @@ def check_config(O, P, opts, M, js, runs, label, entry=True):
             return job, check_entry(O, P[b], opts, M, runs[M], runs[M + 1], b, "%s member %d entry" % (label, b)), None
         reason, ratio = check_pair(O, P[b], opts, runs, M + 1 + j, b, "%s member %d j %d" % (label, b, j))
         return job, reason, ratio
-    out = H._pool_map(one, jobs)
+    out = pool_map(one, jobs)
     worst = {"dx": 0.0, "ds": 0.0, "y": 0.0}; by_j = {j: [] for j in js}; skipped = []; no_entry = []; checked = 0
     for (j, b), reason, ratio in out:
         if j == "entry":
@@ -218,47 +216,21 @@ def problem_of(spec):
 def emu_runs_parallel(spec, members, plan, tmp_dir, rho=None, jobs=None):
     """plan: {M: caps}.  Returns (P, X0 of the chosen members, {M: {cap: run}})"""
     kw, P, X0 = problem_of(spec)
-    todo = list(members)
-    jobs = jobs or min(len(todo), os.cpu_count() or 1, H.REF_THREADS)
-    out_of = lambda b: os.path.join(str(tmp_dir), "feas_emu_%s_N%d_m%d_rho%s.npz" % (spec["form"], spec["N"], b, rho))
-    env = dict(os.environ, OMP_NUM_THREADS="1", OPENBLAS_NUM_THREADS="1")
-    running = []
-    while todo or running:
-        while todo and len(running) < jobs:
-            b = todo.pop(0)
-            text = json.dumps(dict(spec=spec, member=b, plan={str(M): list(c) for M, c in plan.items()}, rho=rho, out=out_of(b)))
-            running.append((subprocess.Popen([sys.executable, os.path.abspath(__file__), text], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT), b))
-        proc, b = running.pop(0)
-        text = proc.communicate()[0]
-        assert proc.returncode == 0, ("emulation run failed", spec, b, text.decode()[-2000:])
-    off = lc("capi").workspace_offsets(spec["N"])
-    parts = [np.load(out_of(b)) for b in members]
-    runs = {}
-    for M, caps in plan.items():
-        runs[M] = {}
-        for cap in caps:
-            g = lambda q, n: q["M%d_c%d_%s" % (M, cap, n)]
-            res = {k: np.concatenate([g(q, k) for q in parts]) for k in ("x", "lam_g", "iters", "status")}
-            runs[M][cap] = dict(res=res, ws=np.concatenate([g(q, "ws") for q in parts]), prof=np.concatenate([g(q, "prof") for q in parts]), off=off)
     members = list(members)
-    return P[members], X0[members], runs
+    todo = [dict(spec=spec, member=b, plan=[(M, cap) for M, caps in plan.items() for cap in caps], rho=rho,
+                 out=os.path.join(str(tmp_dir), "feas_emu_%s_N%d_m%d_rho%s.npz" % (spec["form"], spec["N"], b, rho))) for b in members]
+    runs = load_runs(run_workers(__file__, todo, jobs), ("ws", "prof"))
+    off = lc("capi").workspace_offsets(spec["N"])
+    return P[members], X0[members], {M: {cap: dict(runs[M, cap], off=off) for cap in caps} for M, caps in plan.items()}
 
 
 def _emu_worker(job):
     spec, b = job["spec"], job["member"]
     kw, P, X0 = problem_of(spec)
-    L = lc("capi").LandingLib(spec["N"], lib_path=H.EMU_LIB, **kw)
-    out = {}
-    for M, caps in job["plan"].items():
-        M = int(M)
-        for cap in caps:
-            run = capped_run(L, P[b:b + 1], X0[b:b + 1], feas_opts(L, M, job["rho"]), cap)
-            for n in ("x", "lam_g", "iters", "status"):
-                out["M%d_c%d_%s" % (M, cap, n)] = run["res"][n]
-            out["M%d_c%d_ws" % (M, cap)] = run["ws"]; out["M%d_c%d_prof" % (M, cap)] = run["prof"]
-    np.savez(job["out"], **out)
+    L = lc("capi").LandingLib(spec["N"], lib_path=EMU_LIB, **kw)
+    save_runs(job["out"], {(M, cap): capped_run(L, P[b:b + 1], X0[b:b + 1], feas_opts(L, M, job["rho"]), cap) for M, cap in job["plan"]}, ("ws", "prof"))
     L.close()
 
 
 if __name__ == "__main__":
-    _emu_worker(json.loads(sys.argv[1]))
+    worker_main(_emu_worker)

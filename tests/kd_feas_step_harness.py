@@ -2,10 +2,7 @@
 feas_phase = 1, feas_jam = 0, portfolio off, under landing_debug_iter_cap = M + 1 + j; the row state (s, en, ep, zL, wn, zU, wp), the step (dx, ds, yn) and the
 iteration scalars from the member's workspace block (landing_debug_kd_*); compared with tests/elastic_newton_reference.py.  The SRBM solver's counterpart is
 tests/feas_step_harness.py: the construction, the pairs a run holds and the tolerances are the same (its docstring), and check_update is shared."""
-import json
 import os
-import subprocess
-import sys
 import threading
 
 import numpy as np
@@ -16,6 +13,7 @@ import kd_newton_reference as kr
 import kd_step_harness as KH
 import newton_reference as nr
 from conftest import lc
+from emu_support import EMU_LIB, pool_map, run_workers, worker_main
 
 EPS = np.finfo(float).eps
 _LIB_LOCK = threading.Lock()
@@ -109,7 +107,7 @@ def check_config(probs, opts, M, js, runs, label, factor=nr.TOL_FACTOR):
             return job, check_entry(probs[b], opts, M, runs[M], runs[M + 1], b, "%s member %d entry" % (label, b)), None
         reason, ratio = check_pair(probs[b], opts, runs, M + 1 + j, b, "%s member %d j %d" % (label, b, j), factor=factor)
         return job, reason, ratio
-    out = KH.pool_map(one, jobs)
+    out = pool_map(one, jobs)
     worst = {"dx": 0.0, "ds": 0.0, "y": 0.0}; by_j = {j: [] for j in js}; skipped = []; no_entry = []; checked = 0
     for (j, b), reason, ratio in out:
         if j == "entry":
@@ -131,46 +129,22 @@ def check_config(probs, opts, M, js, runs, label, factor=nr.TOL_FACTOR):
 # ---- the host emulation in parallel: one process per member (kd_step_harness.emu_member), which runs the member alone at every cap
 def emu_runs_parallel(N, members, M, caps, tmp_dir, rho=None, jobs=None):
     """Returns (problems, X0, opts, {cap: run}) of the members, in the order given"""
-    todo = list(members)
-    jobs = jobs or min(len(todo), os.cpu_count() or 1, KH.REF_THREADS)
-    out_of = lambda m: os.path.join(str(tmp_dir), "kd_feas_emu_N%d_M%d_m%d_rho%s.npz" % (N, M, m, rho))
-    env = dict(os.environ, OMP_NUM_THREADS="1", OPENBLAS_NUM_THREADS="1")
-    running = []
-    while todo or running:
-        while todo and len(running) < jobs:
-            m = todo.pop(0)
-            text = json.dumps(dict(N=N, member=m, M=M, caps=list(caps), rho=rho, out=out_of(m)))
-            running.append((subprocess.Popen([sys.executable, os.path.abspath(__file__), text], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT), m))
-        proc, m = running.pop(0)
-        text = proc.communicate()[0]
-        assert proc.returncode == 0, ("emulation run failed", N, M, m, text.decode()[-2000:])
+    todo = [dict(N=N, member=m, M=M, caps=list(caps), rho=rho, out=os.path.join(str(tmp_dir), "kd_feas_emu_N%d_M%d_m%d_rho%s.npz" % (N, M, m, rho))) for m in members]
+    paths = run_workers(__file__, todo, jobs)
     probs, X0 = zip(*[KH.emu_member(dict(N=N, member=m)) for m in members])
-    parts = [np.load(out_of(m)) for m in members]
     with _LIB_LOCK:      # (callers may collect several configurations from threads; the library is opened by one at a time)
-        L = lc("capi").LandingLib(20, lib_path=KH.EMU_LIB); R = lc("rbd").Rbd(L)
-        off, opts, names = R.kinodyn_workspace_layout(N), feas_opts(R, M, rho), R.KD_STATE
+        L = lc("capi").LandingLib(20, lib_path=EMU_LIB); R = lc("rbd").Rbd(L)
+        opts, runs = feas_opts(R, M, rho), KH.load_kd_runs(paths, R, N)
         L.close()
-    runs = {}
-    for cap in caps:
-        g = lambda q, n: q["c%d_%s" % (cap, n)]
-        runs[cap] = dict(res={n: np.concatenate([g(q, n) for q in parts]) for n in ("x", "lam_g", "iters", "status")}, ws=np.concatenate([g(q, "ws") for q in parts]),
-                         rec=[dict(zip(names, g(q, "rec"))) for q in parts], off=off,
-                         Jb=np.concatenate([g(q, "Jb") for q in parts]), Hb=np.concatenate([g(q, "Hb") for q in parts]))
     return list(probs), np.array(X0), opts, runs
 
 
 def _emu_worker(job):
     pr, x0 = KH.emu_member(dict(N=job["N"], member=job["member"]))
-    L = lc("capi").LandingLib(job["N"], lib_path=KH.EMU_LIB); R = lc("rbd").Rbd(L)
-    out = {}
-    for cap in job["caps"]:
-        run = capped_run(R, [pr], x0[None], feas_opts(R, job["M"], job["rho"]), cap)
-        for n in ("x", "lam_g", "iters", "status"):
-            out["c%d_%s" % (cap, n)] = run["res"][n]
-        out["c%d_ws" % cap] = run["ws"]; out["c%d_rec" % cap] = np.array([run["rec"][0][n] for n in R.KD_STATE]); out["c%d_Jb" % cap] = run["Jb"]; out["c%d_Hb" % cap] = run["Hb"]
-    np.savez(job["out"], **out)
+    L = lc("capi").LandingLib(job["N"], lib_path=EMU_LIB); R = lc("rbd").Rbd(L)
+    KH.save_kd_runs(job["out"], R, {cap: capped_run(R, [pr], x0[None], feas_opts(R, job["M"], job["rho"]), cap) for cap in job["caps"]})
     L.close()
 
 
 if __name__ == "__main__":
-    _emu_worker(json.loads(sys.argv[1]))
+    worker_main(_emu_worker)

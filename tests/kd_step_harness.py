@@ -1,18 +1,15 @@
 """What the CPU and the GPU tests of the kinodynamic refinement solver's Newton step share (test helper): running landing_kinodyn_solve_batch for a given
 number of iterations through a library -- the host emulation or the product on the device --, reading dx / ds / yn, the row arrays, gc and the iteration
 scalars from the member's workspace block (landing_debug_kd_*), and comparing them with tests/kd_newton_reference.py."""
-import json
 import os
-import subprocess
-import sys
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
 import kd_newton_reference as kr
 import newton_reference as nr
-from conftest import ROOT, lc
-from solver_step_harness import EMU_LIB, OPTION_SETS, REF_THREADS      # (the option sets of the SRBM step check; "warm" = landing_kinodyn_solver_opts_warm here)
+from conftest import lc
+from emu_support import EMU_LIB, is_emulation, load_runs, pool_map, run_workers, save_runs, worker_main      # (pool_map: for the tests that take it from here)
+from solver_step_harness import OPTION_SETS      # (the option sets of the SRBM step check; "warm" = landing_kinodyn_solver_opts_warm here)
 
 ULP4 = 4 * kr.EPS
 GC_TOL = 8 * kr.EPS      # per entry of gc, times the sum of |terms|.  An entry is a sum of n products in a fixed order; with two roundings per product (one for J_I' rho) it errs
@@ -54,10 +51,6 @@ def step_opts(R, oset, max_iter, delta_floor=None):
     if delta_floor is not None:
         o.delta_floor = delta_floor
     return o
-
-
-def is_emulation(R):
-    return hasattr(R.L.lib, "landing_emu_set_fused")
 
 
 def function_layer(R, pr, X, Y):
@@ -158,14 +151,6 @@ def state_of(run, b):
     return dict(x=run["res"]["x"][b], y=run["res"]["lam_g"][b], s=v["s"], zL=v["zL"], zU=v["zU"])
 
 
-def pool_map(fn, items):
-    items = list(items)
-    if len(items) <= 2:
-        return [fn(i) for i in items]
-    with ThreadPoolExecutor(min(REF_THREADS, os.cpu_count() or 1)) as ex:      # (the oracle and the sparse LU release the GIL)
-        return list(ex.map(fn, items))
-
-
 def check_pair(pr, x0, runs, K, b, label, jac="product", jac_check=False, opts=None, hess_check=False, factor=nr.TOL_FACTOR):
     """The step of iteration K + 1 (run K + 1: dx, ds, yn, gc, the record's mu and delta) against the reference at the iterate run K ended in, with the intermediate
     quantities.  K = 0: run 0 is the start (max_iter = 0), and the state is ALSO restated from the inputs (kd_newton_reference.initial_state) and compared.
@@ -224,33 +209,30 @@ def emu_member(spec):
     return problem_of(N, q, qd, x0s, dtv, 0.75)
 
 
+FIELDS = ("ws", "rec", "Jb", "Hb")
+
+
+def save_kd_runs(path, R, runs):
+    """emu_support.save_runs of kd_run()s, the members' iteration scalars as rows of an array"""
+    save_runs(path, {t: dict(run, rec=np.array([[r[n] for n in R.KD_STATE] for r in run["rec"]])) for t, run in runs.items()}, FIELDS)
+
+
+def load_kd_runs(paths, R, N):
+    """the inverse, over the members' files: {tag: run} as kd_run() returns them"""
+    off = R.kinodyn_workspace_layout(N)
+    return {t: dict(run, rec=[dict(zip(R.KD_STATE, r)) for r in run["rec"]], off=off) for t, run in load_runs(paths, FIELDS).items()}
+
+
 def emu_runs_parallel(specs, tmp_dir, jobs=None):
     """specs: list of dict(N, member, oset, delta_floor, max_iters).  Returns per spec (Problem, x0, opts of the longest run, {max_iter: run})"""
-    todo = sorted(range(len(specs)), key=lambda i: -sum(specs[i]["max_iters"]) * specs[i]["N"])      # longest first
-    jobs = jobs or min(len(todo), os.cpu_count() or 1, 16)
-    out_of = lambda i: os.path.join(str(tmp_dir), "kd_emu_%d.npz" % i)
-    env = dict(os.environ, OMP_NUM_THREADS="1", OPENBLAS_NUM_THREADS="1")
-    running = []
-    while todo or running:
-        while todo and len(running) < jobs:
-            i = todo.pop(0)
-            spec = json.dumps(dict(specs[i], out=out_of(i)))
-            running.append((subprocess.Popen([sys.executable, os.path.abspath(__file__), spec], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT), i))
-        proc, i = running.pop(0)
-        text = proc.communicate()[0]
-        assert proc.returncode == 0, ("emulation run failed", specs[i], text.decode()[-2000:])
+    todo = [dict(spec, out=os.path.join(str(tmp_dir), "kd_emu_%d.npz" % i)) for i, spec in enumerate(specs)]
+    run_workers(__file__, sorted(todo, key=lambda s: -sum(s["max_iters"]) * s["N"]), jobs)      # longest first
     L = lc("capi").LandingLib(20, lib_path=EMU_LIB); R = lc("rbd").Rbd(L)
     out = []
-    for i, spec in enumerate(specs):
+    for spec in todo:
         pr, x0 = emu_member(spec)
-        d = np.load(out_of(i))
-        runs = {}
-        for K in spec["max_iters"]:
-            g = lambda n: d["K%d_%s" % (K, n)]
-            runs[K] = dict(res={n: g(n) for n in ("x", "lam_g", "iters", "status")}, ws=g("ws"), rec=[dict(zip(R.KD_STATE, g("rec")))], off=R.kinodyn_workspace_layout(spec["N"]),
-                           Jb=g("Jb"), Hb=g("Hb"))
         oset = spec["oset"]
-        out.append((pr, x0, step_opts(R, tuple(oset) if isinstance(oset, list) else oset, max(spec["max_iters"]), spec["delta_floor"]), runs))
+        out.append((pr, x0, step_opts(R, tuple(oset) if isinstance(oset, list) else oset, max(spec["max_iters"]), spec["delta_floor"]), load_kd_runs([spec["out"]], R, spec["N"])))
     L.close()
     return out
 
@@ -259,15 +241,9 @@ def _emu_worker(spec):
     pr, x0 = emu_member(spec)
     L = lc("capi").LandingLib(spec["N"], lib_path=EMU_LIB); R = lc("rbd").Rbd(L)
     oset = spec["oset"]; oset = tuple(oset) if isinstance(oset, list) else oset
-    out = {}
-    for K in spec["max_iters"]:
-        run = kd_run(R, [pr], x0[None], step_opts(R, oset, K, spec["delta_floor"]))
-        for n in ("x", "lam_g", "iters", "status"):
-            out["K%d_%s" % (K, n)] = run["res"][n]
-        out["K%d_ws" % K] = run["ws"]; out["K%d_rec" % K] = np.array([run["rec"][0][n] for n in R.KD_STATE]); out["K%d_Jb" % K] = run["Jb"]; out["K%d_Hb" % K] = run["Hb"]
-    np.savez(spec["out"], **out)
+    save_kd_runs(spec["out"], R, {K: kd_run(R, [pr], x0[None], step_opts(R, oset, K, spec["delta_floor"])) for K in spec["max_iters"]})
     L.close()
 
 
 if __name__ == "__main__":
-    _emu_worker(json.loads(sys.argv[1]))
+    worker_main(_emu_worker)

@@ -10,6 +10,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path[:0] = [HERE, os.path.dirname(HERE)]
 import actuator_reference as ar      # noqa: E402
+from emu_support import emu_landing_lib      # noqa: E402
 
 CASES = {"stored": 20, "n2": 2, "n3": 3, "n20": 20, "n64": 64}      # name -> N
 
@@ -25,10 +26,9 @@ def case_inputs(case, golden):
 def emulation_outputs(case, golden, libs=None):
     """the case through the emulated library -> dict of tau, jvel, volt, summary, where, ok"""
     import importlib
-    capi, rbd = importlib.import_module("landing-controller_amd.capi"), importlib.import_module("landing-controller_amd.rbd")
     N, x, dt, stride = case_inputs(case, golden)
-    L = capi.LandingLib(N, lib_path=os.path.join(HERE, "emu", "liblanding_emu.so"))
-    R = rbd.Rbd(L)
+    L = emu_landing_lib(N)
+    R = importlib.import_module("landing-controller_amd.rbd").Rbd(L)
     B = x.shape[0]
     o = dict(tau=np.zeros((B, N, 12)), jvel=np.zeros((B, N, 12)), volt=np.zeros((B, N, 12)), summary=np.zeros((B, 8)), where=np.zeros((B, 4), np.int32), ok=np.zeros(B, np.int32))
     a = lambda k: o[k].ctypes.data
@@ -38,8 +38,6 @@ def emulation_outputs(case, golden, libs=None):
 
 
 if __name__ == "__main__":
-    import subprocess
-    subprocess.run(["make", "-C", os.path.join(os.path.dirname(HERE), "landing-controller_amd", "csrc"), "emu"], check=True, capture_output=True)
     golden = os.path.join(HERE, "golden")
     out = {}
     for case in sorted(CASES):

@@ -1,23 +1,18 @@
 """What the CPU and the GPU tests of the solver kernel's Newton step share (test helper): running landing_ipm_kernel for a given number of
 iterations through a library -- the host emulation or the product on the device --, reading dx / ds / yn, the live row arrays and the exit
 record from the member's workspace block, and comparing them with tests/newton_reference.py."""
-import json
 import os
-import subprocess
-import sys
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
 import newton_reference as nr
-from conftest import ROOT, lc
+from conftest import lc
+from emu_support import EMU_LIB, is_emulation, load_runs, pool_map, run_workers, save_runs, worker_main
 
 RUN_COST = dict(QX=[0, 0, 10, 1, 1, 0, .1, .1, .1, .1, .1, .1], Qc=[1.0, 1.0, 0.5], Qf=[1e-4, 1e-4, 1e-3], f_ref=[0, 0, 20.0])
-EMU_LIB = os.path.join(ROOT, "tests", "emu", "liblanding_emu.so")
 # (bound_push = bound_frac, mu_init); "warm" = landing_solver_opts_warm
 OPTION_SETS = [(1e-2, 0.1), (1e-4, 1e-2), (1e-6, 1e-6), (1e-8, 1e-4), "warm"]
 LATER_K = (1, 2, 5, 12, 25)
-REF_THREADS = 16
 
 
 def step_opts(L, oset, max_iter=1, delta_floor=None):
@@ -28,10 +23,6 @@ def step_opts(L, oset, max_iter=1, delta_floor=None):
     if delta_floor is not None:
         o.delta_floor = delta_floor
     return o
-
-
-def is_emulation(L):
-    return hasattr(L.lib, "landing_emu_set_fused")
 
 
 def kernel_run(L, P, X0, opts):
@@ -91,14 +82,6 @@ def check_step(O, p, st, v, rec, dreg=None, label=""):
     return ratio, bwd, ref
 
 
-def _pool_map(fn, items):
-    items = list(items)
-    if len(items) <= 2:
-        return [fn(i) for i in items]
-    with ThreadPoolExecutor(min(REF_THREADS, os.cpu_count() or 1)) as ex:      # (the oracle and the sparse LU release the GIL)
-        return list(ex.map(fn, items))
-
-
 def first_step_group(L, O, P, X0, opts, label, plain_form):
     """max_iter = 1 from a cold start: every member's step against the reference at initial_state(); the record's mu and delta against
     mu_init and the schedule at the factorisation count.  Returns (worst ratio, factorisation counts, views)."""
@@ -119,7 +102,7 @@ def first_step_group(L, O, P, X0, opts, label, plain_form):
         assert (np.abs(run["res"]["x"][b] - (st["x"] + step)) <= 4 * np.finfo(float).eps * (np.abs(st["x"]) + np.abs(step))).all(), (label, b, "x_1 = x_0 + alpha dx")
         ratio, _, _ = check_step(O, P[b], st, v, rec, label="%s member %d (factorisations %d, delta %.1e)" % (label, b, nfact, rec["delta"]))
         return max(ratio.values())
-    worst = max(_pool_map(one, range(B)))
+    worst = max(pool_map(one, range(B)))
     return worst, run["prof"][:, 8].astype(int), run
 
 
@@ -147,50 +130,34 @@ def later_step_pairs(runs, O, P, label):
         st = dict(x=xk, y=lam, s=vk["s"], zL=vk["zL"], zU=vk["zU"])
         ratio, _, _ = check_step(O, P[b], st, vn, recn, label="%s (mu %.1e delta %.1e alpha %.2e)" % (tag, recn["mu"], recn["delta"], recn["alpha"]))
         return None, max(ratio.values())
-    out = _pool_map(one, jobs)
+    out = pool_map(one, jobs)
     skipped = [s for s, _ in out if s]
     ratios = [r for _, r in out if r is not None]
     return (max(ratios) if ratios else 0.0), len(ratios), skipped
 
 
-# ---- the host emulation in parallel: it keeps the kernel's LDS in static storage, so one process runs one launch at a time; the later-step
-# tests need the same members at nine iteration limits, which are independent processes of this file
+# ---- the host emulation in parallel (emu_support.run_workers): the later-step tests need the same members at nine iteration limits, which are
+# independent processes of this file
 def emu_runs_parallel(N, seed, B, max_iters, tmp_dir, members=None, delta_floor=None, jobs=None):
     """kernel_run() of members `members` (default: all) of make_batch(B, N, 0.6, seed) through the emulation at every iteration limit of
     max_iters (default options but no feasibility phase; delta_floor if given), one process per (limit, member).
     Returns (P, X0, {max_iter: run}) with the chosen members only, in the order given."""
     P, X0, _, _ = lc("problem").make_batch(B, N, 0.6, seed=seed)
     members = list(range(B)) if members is None else list(members)
-    todo = [(K, b) for K in sorted(max_iters, reverse=True) for b in members]      # longest first
-    jobs = jobs or min(len(todo), os.cpu_count() or 1)
-    out_of = lambda K, b: os.path.join(str(tmp_dir), "emu_N%d_s%d_K%d_m%d.npz" % (N, seed, K, b))
-    running = []
-    env = dict(os.environ, OMP_NUM_THREADS="1", OPENBLAS_NUM_THREADS="1")
-    while todo or running:
-        while todo and len(running) < jobs:
-            K, b = todo.pop(0)
-            spec = json.dumps(dict(N=N, seed=seed, B=B, member=b, max_iter=K, delta_floor=delta_floor, out=out_of(K, b)))
-            running.append((subprocess.Popen([sys.executable, os.path.abspath(__file__), spec], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT), K, b))
-        proc, K, b = running.pop(0)
-        text = proc.communicate()[0]
-        assert proc.returncode == 0, ("emulation run failed", N, K, b, text.decode()[-2000:])
-    runs = {}
+    todo = [dict(N=N, seed=seed, B=B, member=b, max_iter=K, delta_floor=delta_floor, out=os.path.join(str(tmp_dir), "emu_N%d_s%d_K%d_m%d.npz" % (N, seed, K, b)))
+            for K in sorted(max_iters, reverse=True) for b in members]      # longest first
+    runs = load_runs(run_workers(__file__, todo, jobs), ("ws", "prof"))
     off = lc("capi").workspace_offsets(N)
-    for K in max_iters:
-        parts = [np.load(out_of(K, b)) for b in members]
-        res = {k: np.concatenate([q[k] for q in parts]) for k in ("x", "lam_g", "iters", "status")}
-        runs[K] = dict(res=res, ws=np.concatenate([q["ws"] for q in parts]), prof=np.concatenate([q["prof"] for q in parts]), off=off)
-    return P[members], X0[members], runs
+    return P[members], X0[members], {K: dict(runs[K], off=off) for K in max_iters}
 
 
 def _emu_worker(spec):
     P, X0, _, _ = lc("problem").make_batch(spec["B"], spec["N"], 0.6, seed=spec["seed"])
     b = spec["member"]
     L = lc("capi").LandingLib(spec["N"], lib_path=EMU_LIB)
-    run = kernel_run(L, P[b:b + 1], X0[b:b + 1], step_opts(L, None, max_iter=spec["max_iter"], delta_floor=spec["delta_floor"]))
-    np.savez(spec["out"], ws=run["ws"], prof=run["prof"], **{k: run["res"][k] for k in ("x", "lam_g", "iters", "status")})
+    save_runs(spec["out"], {spec["max_iter"]: kernel_run(L, P[b:b + 1], X0[b:b + 1], step_opts(L, None, max_iter=spec["max_iter"], delta_floor=spec["delta_floor"]))}, ("ws", "prof"))
     L.close()
 
 
 if __name__ == "__main__":
-    _emu_worker(json.loads(sys.argv[1]))
+    worker_main(_emu_worker)

@@ -3,28 +3,24 @@ host emulation of the same sources (tests/emu; emulated device pointers are host
 utilities_landing/plot_results.m:12-39 and of the header's summary / where / ok rules."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import actuator_reference as ar
 from conftest import GOLDEN, ROOT, lc
+from emu_support import emu_landing_lib
 from header_decls import _header_fields
 
-PKG = os.path.join(ROOT, "landing-controller_amd")
-EMU = os.path.join(ROOT, "tests", "emu", "liblanding_emu.so")
 _libs = {}
 
 
 @pytest.fixture(scope="module")
 def emu():
     """N -> (LandingLib, Rbd) on the emulation, one context per horizon"""
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
-
     def get(N):
         if N not in _libs:
-            L = lc("capi").LandingLib(N, lib_path=EMU)
+            L = emu_landing_lib(N)
             _libs[N] = (L, lc("rbd").Rbd(L))
         return _libs[N]
     yield get
@@ -225,14 +221,14 @@ def test_argument_errors(emu):
     h = lambda v: v.ctypes.data_as(dp)
     assert L.lib.landing_actuator_audit_host(L.ctx, 2, h(dt), 3, h(x), None, None, None, None, None, h(s), w.ctypes.data_as(ip), ok.ctypes.data_as(ip)) == -1
     assert L.lib.landing_actuator_audit_host(L.ctx, 2, h(dt), N, h(x), None, None, None, None, None, None, w.ctypes.data_as(ip), ok.ctypes.data_as(ip)) == -1
-    L2 = capi.LandingLib(N, lib_path=EMU)      # no model
+    L2 = emu_landing_lib(N)      # no model
     assert call(good, L2) == -1 and b"no model" in L2.lib.landing_last_error()
     L2.close()
-    L3 = capi.LandingLib(65, lib_path=EMU)
+    L3 = emu_landing_lib(65)
     rbd.Rbd(L3)
     assert call(good, L3) == -1 and b"N <= 64" in L3.lib.landing_last_error()
     L3.close()
-    L4 = capi.LandingLib(N, lib_path=EMU)      # a tree whose legs are not numbered the quadruped's way: refused as the pipeline refuses it
+    L4 = emu_landing_lib(N)      # a tree whose legs are not numbered the quadruped's way: refused as the pipeline refuses it
     M = rbd.quad3d_model(); M.parent[7] = 6
     rbd.Rbd(L4, model=M)
     assert call(good, L4) == -1 and b"legs" in L4.lib.landing_last_error()
@@ -300,7 +296,7 @@ def test_screened_pairs_against_the_unscreened_writer(emu, stored):
     for i in (0, 1, 2, 5, 6, 7, 8, 9, 10, 11):
         bad = list(a); bad[i] = None
         assert fn(L.ctx, B, *bad) == -1, i
-    L2 = lc("capi").LandingLib(N, lib_path=EMU)
+    L2 = emu_landing_lib(N)
     assert fn(L2.ctx, B, *a) == -1 and b"no model" in L2.lib.landing_last_error()
     L2.close()
 

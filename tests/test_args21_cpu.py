@@ -6,20 +6,17 @@
     landing_solve_batch_host returns for the packed p."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, lc
-
-PKG = os.path.join(ROOT, "landing-controller_amd")
+from conftest import lc
+from emu_support import build_emu, build_product
 
 
 @pytest.fixture(scope="module")
 def libs():
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "all", "emu"], check=True, capture_output=True)
-    return os.path.join(PKG, "liblanding_mi355x.so"), os.path.join(ROOT, "tests", "emu", "liblanding_emu.so")
+    return build_product(), build_emu()
 
 
 def test_pack_args21_equals_python_mirror(libs):

@@ -5,15 +5,14 @@ import ctypes as C
 import glob
 import os
 import re
-import subprocess
 
 import pytest
 
 import header_decls as H
 from conftest import ROOT, lc
+from emu_support import EMU_LIB, build_emu
 
 PKG = os.path.join(ROOT, "landing-controller_amd")
-EMU = os.path.join(ROOT, "tests", "emu", "liblanding_emu.so")
 MIRRORS = dict(landing_form="LandingForm", landing_solver_opts="SolverOpts", landing_args21="Args21", landing_args25="Args25", landing_rbd_model="RbdModel",
                landing_kinodyn_params="KinodynParams", landing_kinodyn_form="KinodynForm", landing_pipeline_opts="PipelineOpts",
                landing_actuator_model="ActuatorModel", landing_actuator_screen="ActuatorScreen")
@@ -45,9 +44,9 @@ def test_table_matches_every_prototype():
 
 
 def test_load_alone_declares_every_entry_point():
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
+    build_emu()
     capi = lc("capi")
-    lib = capi.load(EMU)      # a fresh CDLL: nothing any wrapper class has done to another one shows here
+    lib = capi.load(EMU_LIB)      # a fresh CDLL: nothing any wrapper class has done to another one shows here
     for name in H.prototypes():
         fn, (restype, argtypes) = getattr(lib, name), capi.SIGNATURES[name]
         assert fn.argtypes is not None and list(fn.argtypes) == argtypes and fn.restype is restype, name

@@ -7,19 +7,19 @@
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT, lc
+from emu_support import EMU_LIB, PRODUCT_LIB, build_emu, build_product
 
 PKG = os.path.join(ROOT, "landing-controller_amd")
 
 
 @pytest.fixture(scope="session")
 def built():
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "all", "emu"], check=True, capture_output=True)
+    build_product(); build_emu()
     return True
 
 
@@ -29,7 +29,7 @@ def _declared(header, pat):
 
 
 def test_library_exports_every_declared_symbol(built):
-    lib = C.CDLL(os.path.join(PKG, "liblanding_mi355x.so"))
+    lib = C.CDLL(PRODUCT_LIB)
     names = _declared("landing_nlp.h", r"\b(landing_[a-z0-9_]+)\s*\(")
     assert len(names) >= 20
     for n in names:
@@ -102,7 +102,7 @@ def test_no_device_means_loud_failure(built):
 
 @pytest.fixture(scope="module")
 def emu(built):
-    return os.path.join(ROOT, "tests", "emu", "liblanding_emu.so")
+    return EMU_LIB
 
 
 @pytest.mark.parametrize("N", [20, 40])

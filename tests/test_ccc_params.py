@@ -7,15 +7,13 @@ force part of Uref in the running cost (:81-89), so its NLP has its own paramete
   * the same problem posed with constants of the context (run_cost 1) and through p (run_cost 2) is solved to the same bits;
   * landing_pack_args25 (the script's 25-argument solver function, analysis/eval_SRBM_CCC.m:72-78) = the Python mirror."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, lc
+from conftest import lc
+from emu_support import build_emu, build_product
 
-PKG = os.path.join(ROOT, "landing-controller_amd")
 RC = dict(QX=[0.3, 0.2, 10, 1, 1, 0.4, .1, .2, .1, .3, .1, .2], Qc=[1.0, 0.8, 0.5], Qf=[1e-4, 2e-4, 1e-3], f_ref=[0.5, -0.25, 20.0])
 KB = (0.05, 0.05, 0.27)
 
@@ -61,8 +59,8 @@ def test_oracle_grad_gamma_p_all_entries(oracle_mod):
 
 @pytest.fixture(scope="module")
 def emu():
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "all", "emu"], check=True, capture_output=True)
-    return os.path.join(ROOT, "tests", "emu", "liblanding_emu.so")
+    build_product()
+    return build_emu()
 
 
 def _check_eval(L, O, x, Pc, lam, lam_f):

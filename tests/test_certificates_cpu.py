@@ -6,24 +6,20 @@ price on every violated row (V), complementarity inside the bounds (C), positive
 test, not from either solver.  Here: the checker against a problem solved by hand, the CPU port's certificates on the reference's production problem,
 a control that must FAIL (the stationary-violation exit that rounds 3-5 reported under this status), and the HIP solver kernel itself, compiled for
 the host through tests/emu, with the multipliers it returns."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import certificate_reference as cr
-from conftest import ROOT, lc
+from conftest import lc
+from emu_support import build_emu
 
-PKG = os.path.join(ROOT, "landing-controller_amd")
 RHO, TOL = 1000.0, 1e-6
 N = 20
 
 
 @pytest.fixture(scope="module")
 def emu_lib():
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
-    return os.path.join(ROOT, "tests", "emu", "liblanding_emu.so")
+    return build_emu()
 
 
 def _production(seed):

@@ -4,16 +4,13 @@ the k-th allocation from now fail (tests/emu: hip_emu_live_blocks, hip_emu_fail_
     (the CasADi face's cache included, without landing_kinodyn_casadi_release);
   * with any one of the call's allocations made to fail, the call returns LANDING_E_HIP and the count still returns to its start."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, lc
+from conftest import lc
+from emu_support import build_emu, emu_landing_lib
 
-PKG = os.path.join(ROOT, "landing-controller_amd")
-EMU = os.path.join(ROOT, "tests", "emu", "liblanding_emu.so")
 LANDING_E_HIP = -2
 _dp, _ip, _lp = C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_longlong)
 
@@ -24,8 +21,7 @@ def _p(a):
 
 @pytest.fixture(scope="module")
 def emu():
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
-    return lc("capi").load(EMU)      # (the table of capi.py declares every entry point and the emulation's counters)
+    return lc("capi").load(build_emu())      # (the table of capi.py declares every entry point and the emulation's counters)
 
 
 RC = dict(QX=[1.0] * 12, Qc=[0.1] * 3, Qf=[0.01] * 3)
@@ -130,7 +126,7 @@ CASES = [(eval_batch_host, NS, None), (eval_hess_rc_batch_host, NS, RC), (solve_
 def _run(emu, call, N, run_cost, fail_at):
     """live-block count before the context, rc of the call with allocation `fail_at` failing (0: none), allocations the call made, count after landing_destroy"""
     start = emu.hip_emu_live_blocks()
-    L = lc("capi").LandingLib(N, lib_path=EMU, run_cost=run_cost)
+    L = emu_landing_lib(N, run_cost=run_cost)
     try:
         if N in (NK, NP):
             lc("rbd").Rbd(L)      # (sets the model)

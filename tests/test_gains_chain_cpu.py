@@ -8,15 +8,12 @@ through tests/emu (the same kernel sources compiled for the host).
 
 Tolerance of the interpolation: 1e-13 * max |knot value| per entry (ki * a + (1 - ki) * b is two multiplies and one add, with or without
 contraction a handful of ulps of the larger knot value); held forces are copies and must be bit-equal."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-from conftest import ROOT, lc
+from conftest import lc
+from emu_support import build_emu
 
-PKG = os.path.join(ROOT, "landing-controller_amd")
 N, B = 6, 3
 NX = 36 * N + 12
 DT6 = np.array([0.05, 0.02, 0.02, 0.05, 0.1, 0.2])      # the production pattern (coarse, fine around touch-down, coarse tail) at N = 6
@@ -24,8 +21,7 @@ DT6 = np.array([0.05, 0.02, 0.02, 0.05, 0.1, 0.2])      # the production pattern
 
 @pytest.fixture(scope="module")
 def emu():
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
-    return os.path.join(ROOT, "tests", "emu", "liblanding_emu.so")
+    return build_emu()
 
 
 @pytest.fixture(scope="module")

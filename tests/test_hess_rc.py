@@ -2,19 +2,17 @@
 landing_eval_hess_rc_batch (extended pattern: casadi_s4 + 18 N diagonals) and the running-cost parts of grad_gamma_x /
 grad_gamma_p, against the oracle -- whose own entries are pinned by finite differences of its gradient here."""
 import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from emu_support import build_emu
 from oracle.oracle import Oracle
 
 PKG = "landing-controller_amd"
 capi = importlib.import_module(PKG + ".capi")
 problem = importlib.import_module(PKG + ".problem")
 RC = dict(QX=[0, 0, 10, 1, 1, 0, .1, .1, .1, .1, .1, .1], Qc=[1.0, 1.0, 0.5], Qf=[1e-4, 1e-4, 1e-3], f_ref=[0, 0, 20.0])
-EMU = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu", "liblanding_emu.so")
 
 
 def _inputs(N, B, seed):
@@ -75,8 +73,7 @@ def _check(lib, N, B, seed):
 
 @pytest.fixture(scope="module")
 def emu():
-    subprocess.run(["make", "-C", os.path.join(os.path.dirname(os.path.abspath(capi.__file__)), "csrc"), "emu"], check=True, capture_output=True)
-    return EMU
+    return build_emu()
 
 
 def test_hess_rc_emulated_matches_oracle(emu):

@@ -16,8 +16,6 @@ Worst measured ratio error / max(e_aug, e_cond, 1e-15) on the emulation (bound 1
     N = 20, M = 2    0.24 / 0.24 / 0.014    (1 pair)
     N = 2, M = 27    0.24 / 0.29 / 0.13     (j in {12, 25}, members 0, 1: 4 pairs; run once by hand, not part of the file: three minutes of emulation)
 """
-import os
-import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
 import pytest
@@ -25,9 +23,8 @@ import pytest
 import feas_step_harness as F
 import kd_feas_step_harness as KF
 import kd_step_harness as KH
-from conftest import ROOT
+from emu_support import build_emu
 
-PKG = os.path.join(ROOT, "landing-controller_amd")
 # (N, M, members)
 CASES = [(2, 12, [0, 1, 2]), (3, 12, [0, 1]), (20, 2, [0])]
 
@@ -35,7 +32,7 @@ CASES = [(2, 12, [0, 1, 2]), (3, 12, [0, 1]), (20, 2, [0])]
 @pytest.fixture(scope="module")
 def emu_runs(tmp_path_factory):
     """case -> (problems, X0, opts, {cap: run}); the six member processes of the file run side by side (the threads only wait for them)"""
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
+    build_emu()
     tmp = tmp_path_factory.mktemp("kd_feas_emu")
     with ThreadPoolExecutor(len(CASES)) as ex:
         out = list(ex.map(lambda c: KF.emu_runs_parallel(c[0], c[2], c[1], F.caps_of(c[1], F.pairs_within(c[1])), tmp), CASES))

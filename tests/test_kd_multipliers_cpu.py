@@ -8,21 +8,17 @@ oracle and the kernels, which no kernel-against-oracle test can see, breaks it. 
 terminal reference, a shift by one row, and -- group by group -- 19 of the 27 row groups; the other 8 carry multipliers <= ~1e-5 in this solve and stay
 pinned by feasibility only.  The kernels (CasADi-external face, Hessian blocks) are then checked AT that point through tests/emu, where the contact and
 complementarity rows are active and lam* has the structure of a real solve.  Device counterparts: tests/test_gpu_kd_multipliers.py."""
-import os
-import subprocess
-
 import numpy as np
 
 import kd_reference_kkt as K
-from conftest import ROOT, lc
+from conftest import lc
+from emu_support import emu_landing_lib
 
 N, KKT_TOL, MU = K.N, K.KKT_TOL, K.MU
-EMU = os.path.join(ROOT, "tests", "emu", "liblanding_emu.so")
 
 
 def _emu_lib():
-    subprocess.run(["make", "-C", os.path.join(ROOT, "landing-controller_amd", "csrc"), "emu"], check=True, capture_output=True)
-    return lc("capi").LandingLib(N, lib_path=EMU)
+    return emu_landing_lib(N)
 
 
 def test_reference_multipliers_are_a_kkt_point_under_the_oracle():

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT, lc
+from emu_support import PKG, PRODUCT_LIB, build_product, compile_mex_gateway, emu_landing_lib
 
 PKG = os.path.join(ROOT, "landing-controller_amd")
 N = 20
@@ -20,8 +21,7 @@ N = 20
 
 @pytest.fixture(scope="module")
 def emu():
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
-    L = lc("capi").LandingLib(N, lib_path=os.path.join(ROOT, "tests", "emu", "liblanding_emu.so"))
+    L = emu_landing_lib(N)
     return L, lc("rbd").Rbd(L)
 
 
@@ -56,9 +56,9 @@ def test_batch_oracle_equals_scalar_oracle():
 def test_bounds_entry_point_equals_python_mirror():
     kd, P = lc("kinodyn"), lc("problem")
     lib = lc("capi").LandingLib.__new__(lc("capi").LandingLib)
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "all"], check=True, capture_output=True)
+    build_product()
     import ctypes as C
-    raw = lc("capi").load(os.path.join(PKG, "liblanding_mi355x.so"))
+    raw = lc("capi").load(PRODUCT_LIB)
     _, _, q, qd = P.make_batch(5, N, 0.6, seed=7, consts=P.production_constants("main"), dt_grid="reference")
     B = 5
     dp = C.POINTER(C.c_double)
@@ -95,7 +95,7 @@ def test_emulated_kernels_solve_a_short_horizon_member(emu):
     kd, P = lc("kinodyn"), lc("problem")
     mass, Ib, Ibi, _ = _consts()
     Ns, dtv = 6, np.full(6, 0.05)
-    Ls = lc("capi").LandingLib(Ns, lib_path=os.path.join(ROOT, "tests", "emu", "liblanding_emu.so")); Rs = lc("rbd").Rbd(Ls)
+    Ls = emu_landing_lib(Ns); Rs = lc("rbd").Rbd(Ls)
     q = np.array([0, 0, 0.0, 0.05, 0.15, -0.05]); qd = np.array([0.1, -0.1, 0.05, 0.2, -0.1, -1.0])
     q[2] = 0.35 + abs(min((kd.rot_xyz(q[3:6]) @ np.array([sx * 0.19, sy * 0.1, 0.0]))[2] for sx in (1, -1) for sy in (1, -1))) + abs(dtv[0] * qd[5])
     _, x0s, _, _ = P.make_member(Ns, 0.3, q, qd, P.production_constants("main"), dtv)
@@ -120,7 +120,7 @@ def test_portfolio_reports_the_first_member_of_a_family_that_converges():
     kd, P = lc("kinodyn"), lc("problem")
     mass, Ib, Ibi, _ = _consts()
     Ns, dtv = 6, np.full(6, 0.05)
-    Ls = lc("capi").LandingLib(Ns, lib_path=os.path.join(ROOT, "tests", "emu", "liblanding_emu.so")); Rs = lc("rbd").Rbd(Ls)
+    Ls = emu_landing_lib(Ns); Rs = lc("rbd").Rbd(Ls)
     q = np.array([0, 0, 0.0, 0.05, 0.15, -0.05]); qd = np.array([0.1, -0.1, 0.05, 0.2, -0.1, -1.0])
     q[2] = 0.35 + abs(min((kd.rot_xyz(q[3:6]) @ np.array([sx * 0.19, sy * 0.1, 0.0]))[2] for sx in (1, -1) for sy in (1, -1))) + abs(dtv[0] * qd[5])
     _, x0s, _, _ = P.make_member(Ns, 0.3, q, qd, P.production_constants("main"), dtv)
@@ -196,8 +196,8 @@ def test_c_model_builder_equals_python_model_and_gateway_compiles(tmp_path):
     """landing_rbd_model_mc3d (what C / mex callers use) fills the struct exactly as rbd.quad3d_model does; matlab/landing_refine_mex.c compiles
     against the mex.h stub and links to the product library"""
     import ctypes as C
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "all"], check=True, capture_output=True)
-    raw = lc("capi").load(os.path.join(PKG, "liblanding_mi355x.so"))
+    build_product()
+    raw = lc("capi").load(PRODUCT_LIB)
     rbd = lc("rbd")
     m = rbd.RbdModel()
     raw.landing_rbd_model_mc3d(C.byref(m))
@@ -206,9 +206,7 @@ def test_c_model_builder_equals_python_model_and_gateway_compiles(tmp_path):
         a, b = np.ctypeslib.as_array(getattr(m, name)) if hasattr(getattr(m, name), "_length_") else getattr(m, name), \
                np.ctypeslib.as_array(getattr(ref, name)) if hasattr(getattr(ref, name), "_length_") else getattr(ref, name)
         assert np.allclose(a, b, rtol=1e-13, atol=1e-19), name      # (the inertia about the link origin is formed in another order of operations: last-bit differences)
-    so = os.path.join(str(tmp_path), "refine_gateway.so")
-    subprocess.run(["gcc", "-O1", "-std=c99", "-D_POSIX_C_SOURCE=200809L", "-fPIC", "-shared", "-Wall", "-Werror", "-Wno-unused-function", "-I", os.path.join(ROOT, "tests", "stubs"),
-                    "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "matlab", "landing_refine_mex.c"), "-o", so, "-L", PKG, "-llanding_mi355x", "-Wl,-rpath," + PKG], check=True)
+    so = compile_mex_gateway(tmp_path, "landing_refine_mex.c", None, PKG, "landing_mi355x")
     assert "mexFunction" in subprocess.run(["nm", "-D", so], capture_output=True, text=True).stdout
 
 

@@ -40,18 +40,15 @@ What these tests catch, tried on emulation builds of scratch copies of the tree 
     ds of the terminal rows left out in kd_forward                                     34   every step case
 None of the five goes unnoticed.
 """
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import kd_newton_reference as kr
 import kd_step_harness as H
 import newton_reference as nr
-from conftest import ROOT, lc
+from conftest import lc
+from emu_support import build_emu, emu_landing_lib
 
-PKG = os.path.join(ROOT, "landing-controller_amd")
 HORIZONS = (2, 3, 6)
 FLOORS = (None, 0.0)
 LATER_K = (1, 2, 5)
@@ -80,15 +77,14 @@ LATER += [dict(N=6, member=m, oset=PENDING_OSET, delta_floor=0.0, max_iters=[K, 
 @pytest.fixture(scope="module")
 def emu_runs(tmp_path_factory):
     """every emulation run of this file, one process per (member, option set), all at once: tag -> (Problem, x0, opts, {max_iter: run})"""
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
+    build_emu()
     specs = FIRST + LATER
     res = H.emu_runs_parallel([{k: v for k, v in s.items() if k != "tag"} for s in specs], tmp_path_factory.mktemp("kd_emu"))
     return {s["tag"]: r for s, r in zip(specs, res)}
 
 
 def test_layout_is_the_stride_and_entry_points_refuse_without_a_solve():
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
-    L = lc("capi").LandingLib(20, lib_path=H.EMU_LIB); R = lc("rbd").Rbd(L)
+    L = emu_landing_lib(20); R = lc("rbd").Rbd(L)
     with pytest.raises(Exception):
         R.kinodyn_debug_workspace(1)
     with pytest.raises(Exception):

@@ -2,15 +2,11 @@
 CPU: the shift kernel through tests/emu against a numpy restatement.  GPU: a closed loop of several ticks at batch 64 --
 every tick's solution is a KKT point (<= 1e-6 under the oracle's functions on a sample) and warm ticks need far fewer
 iterations than the cold solve."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-from conftest import ROOT, lc
-
-PKG = os.path.join(ROOT, "landing-controller_amd")
+from conftest import lc
+from emu_support import emu_landing_lib
 
 
 def _shift_ref(N, x, state, p, po):
@@ -22,10 +18,9 @@ def _shift_ref(N, x, state, p, po):
 
 
 def test_mpc_shift_emulated():
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
     Pm = lc("problem")
     N, B = 12, 3
-    L = lc("capi").LandingLib(N, lib_path=os.path.join(ROOT, "tests", "emu", "liblanding_emu.so"))
+    L = emu_landing_lib(N)
     rng = np.random.default_rng(0)
     P, X0, _, _ = Pm.make_batch(B, N, 0.6, seed=1)
     x = rng.normal(size=X0.shape); state = rng.normal(size=(B, 12)); p = P.copy(); x0 = np.zeros_like(x)

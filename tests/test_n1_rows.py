@@ -7,14 +7,13 @@ landing_optimization.m:186-187), leg torques J_f'(-R' f) within tauMax, joint li
 geometry, side sign or inertia shows up here as a violation orders of magnitude above these tolerances (e.g. the production grid
 instead of dt = 0.03: defects of 1.1).  CPU: oracle + the kernel through tests/emu; GPU: landing_kinodyn_rows_batch on the same data."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT, lc
+from conftest import GOLDEN, lc
+from emu_support import emu_landing_lib
 
-PKG = os.path.join(ROOT, "landing-controller_amd")
 DT = np.full(20, 0.03)
 
 
@@ -72,8 +71,7 @@ def _check_rows(out):
 
 
 def test_kinodyn_rows_kernel_on_stored_solutions_emulated():
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
-    L = lc("capi").LandingLib(20, lib_path=os.path.join(ROOT, "tests", "emu", "liblanding_emu.so"))
+    L = emu_landing_lib(20)
     _check_rows(_rows_through(L, "cpu"))
 
 
@@ -127,8 +125,7 @@ def _nlp_check(L, dev, N, B, seed, n_jac=2):
 
 
 def test_kinodyn_nlp_function_layer_emulated():
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
-    L = lc("capi").LandingLib(20, lib_path=os.path.join(ROOT, "tests", "emu", "liblanding_emu.so"))
+    L = emu_landing_lib(20)
     _nlp_check(L, "cpu", N=3, B=2, seed=1, n_jac=1)
 
 
@@ -168,7 +165,7 @@ def _stored_solution_rows(L, dev):
 
 
 def test_kinodyn_nlp_rows_on_stored_solutions_emulated():
-    L = lc("capi").LandingLib(20, lib_path=os.path.join(ROOT, "tests", "emu", "liblanding_emu.so"))
+    L = emu_landing_lib(20)
     _stored_solution_rows(L, "cpu")
 
 
@@ -232,7 +229,7 @@ def _hess_check(L, dev, N, B, seed, oracle_cols):
 
 
 def test_kinodyn_nlp_hessian_emulated():
-    L = lc("capi").LandingLib(20, lib_path=os.path.join(ROOT, "tests", "emu", "liblanding_emu.so"))
+    L = emu_landing_lib(20)
     _hess_check(L, "cpu", N=2, B=1, seed=3, oracle_cols=(4, 26, 38))      # a rotation angle, a vertical force, a hip joint
 
 
@@ -245,7 +242,6 @@ def test_kinodyn_hessian_pair_table_does_not_depend_on_the_first_call_emulated()
     Ib, Ibi = np.asarray(Ib), np.asarray(Ibi)
     N, B = 2, 1
     rng = np.random.default_rng(5)
-    emu = os.path.join(ROOT, "tests", "emu", "liblanding_emu.so")
     def hess(L, R, Ib_, Ibi_):
         nx, ng = R.kinodyn_nlp_dims(N)
         r2 = np.random.default_rng(6)
@@ -255,12 +251,12 @@ def test_kinodyn_hessian_pair_table_does_not_depend_on_the_first_call_emulated()
         H = torch.zeros(B, N, 72, 72, dtype=torch.float64)
         R.kinodyn_nlp_hess(B, N, dx.data_ptr(), dt, mass, Ib_, Ibi_, 0.75, dl.data_ptr(), H.data_ptr(), 0)
         return H.numpy().copy()
-    L1 = lc("capi").LandingLib(20, lib_path=emu); R1 = lc("rbd").Rbd(L1)
+    L1 = emu_landing_lib(20); R1 = lc("rbd").Rbd(L1)
     sym = np.full(3, 0.03)
     Hs = hess(L1, R1, sym, 1.0 / sym)
     assert (Hs[0, :, 6:9, 6:9] == 0.0).all()                      # omega x (I omega) vanishes for a spherical inertia
     H2 = hess(L1, R1, Ib, Ibi)                                    # ... same context, the real inertia
-    L2 = lc("capi").LandingLib(20, lib_path=emu); R2 = lc("rbd").Rbd(L2)
+    L2 = emu_landing_lib(20); R2 = lc("rbd").Rbd(L2)
     H3 = hess(L2, R2, Ib, Ibi)
     assert np.abs(H3[0, :, 6:9, 6:9]).max() > 1e-3 and np.array_equal(H2, H3)
     R1b = lc("rbd").Rbd(L1)                                       # landing_rbd_set_model again: the table is invalidated and rebuilt at the next call
@@ -312,8 +308,7 @@ def _base_forms_check(L, dev, N, B):
 
 
 def test_kinodyn_base_transform_forms_agree_emulated():
-    subprocess.run(["make", "-C", os.path.join(ROOT, "landing-controller_amd", "csrc"), "emu"], check=True, capture_output=True)
-    L = lc("capi").LandingLib(3, lib_path=os.path.join(ROOT, "tests", "emu", "liblanding_emu.so"))
+    L = emu_landing_lib(3)
     _base_forms_check(L, "cpu", N=3, B=2)
     L.close()
 
@@ -433,6 +428,6 @@ def _casadi_face_check(L, N, seed, hess_cols, tol_h):
 
 
 def test_kinodyn_casadi_face_emulated():
-    L = lc("capi").LandingLib(20, lib_path=os.path.join(ROOT, "tests", "emu", "liblanding_emu.so"))
+    L = emu_landing_lib(20)
     _casadi_face_check(L, N=2, seed=11, hess_cols=(3, 7, 30, 40, 60, 75, 100), tol_h=1e-6)
     L.close()

@@ -4,23 +4,20 @@ pairs kernel against dataset.training_pairs, the select rule, the plumbing and a
 against its ctypes mirror, and the MATLAB gateway compiled against tests/stubs/mex.h."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, lc
+from conftest import lc
+from emu_support import EMU_LIB as EMU, build_emu, compile_mex_gateway, emu_landing_lib
 from header_decls import _header_fields
 
-PKG = os.path.join(ROOT, "landing-controller_amd")
-EMU = os.path.join(ROOT, "tests", "emu", "liblanding_emu.so")
 N = 20
 
 
 @pytest.fixture(scope="module")
 def emu():
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
-    L = lc("capi").LandingLib(N, lib_path=EMU)
+    L = emu_landing_lib(N)
     yield L, lc("rbd").Rbd(L)
     L.close()
 
@@ -145,7 +142,7 @@ def _chain(L, R, P, X0, opts, n=None):
 def test_pipeline_batch_plumbing_on_the_emulation():
     """landing_pipeline_batch at N = 3, B = 2, two iterations per pass: every column of status / iters is filled, the count matches the final statuses,
     warm = 0 leaves the re-solve column at -1 / 0; LANDING_E_ARG for mixed dt, N > 64, a context without a model and the N=41 script's context"""
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
+    build_emu()
     capi, rbd, Pm, pl = lc("capi"), lc("rbd"), lc("problem"), lc("pipeline")
     n = 3
     L = capi.LandingLib(n, lib_path=EMU)
@@ -207,11 +204,7 @@ class PipelineGateway:
     tests/stubs/pipeline_mex_driver.c; call() returns the outputs or raises with the text of mexErrMsgTxt"""
 
     def __init__(self, tmp_dir, lib_dir, lib_name):
-        so = os.path.join(str(tmp_dir), "pipeline_gateway_%s.so" % lib_name)
-        subprocess.run(["gcc", "-O1", "-std=c99", "-D_POSIX_C_SOURCE=200809L", "-fPIC", "-shared", "-Wall", "-Werror", "-Wno-unused-function", "-I",
-                        os.path.join(ROOT, "tests", "stubs"), "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "matlab", "landing_pipeline_mex.c"),
-                        os.path.join(ROOT, "tests", "stubs", "pipeline_mex_driver.c"), "-o", so, "-L", lib_dir, "-l" + lib_name, "-Wl,-rpath," + lib_dir], check=True)
-        self.gw = C.CDLL(so)
+        self.gw = C.CDLL(compile_mex_gateway(tmp_dir, "landing_pipeline_mex.c", "pipeline_mex_driver.c", lib_dir, lib_name))
         self.gw.gateway_error.restype = C.c_char_p
 
     def call(self, N, args, names, opts=None, nlhs=7, single=()):
@@ -242,7 +235,7 @@ class PipelineGateway:
 def test_pipeline_gateway_compiles_and_refuses_bad_arguments(tmp_path):
     """matlab/landing_pipeline_mex.c compiles against the mex.h stub with -Wall -Werror; its argument errors come back through the stub driver; on the
     emulation (N = 3, B = 2, two iterations per pass) it returns what landing_pipeline_batch returns for the same drop states"""
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
+    build_emu()
     capi, Pm = lc("capi"), lc("problem")
     gw = PipelineGateway(tmp_path, os.path.dirname(EMU), "landing_emu")
     n = 3

@@ -5,15 +5,11 @@ get_forward_kin_foot.m, get_foot_jacobians_mc.m, landing_optimization.m:152-189)
 CPU: the same sources through tests/emu.  GPU: N=40 knots x members at BASELINE configs[3]'s shape (sampled).
 Tolerances (fp64): H, C, FK, torques 1e-11 relative; qdd 1e-9 (18 x 18 solve, cond ~1e4); finite-difference Jacobians
 1e-5 relative against the oracle's own central differences (same step)."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-from conftest import ROOT, lc
-
-PKG = os.path.join(ROOT, "landing-controller_amd")
+from conftest import lc
+from emu_support import emu_landing_lib
 
 
 def _points(rng, n):
@@ -42,8 +38,7 @@ def _check_dynamics(ro, q, qd, tau, f, H, Cb, qdd, A, Hinv, fd_h, with_f):
 @pytest.mark.parametrize("with_f", [False, True])
 def test_fb_dynamics_emulated(with_f):
     from oracle import rbd_oracle as ro
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
-    L = lc("capi").LandingLib(20, lib_path=os.path.join(ROOT, "tests", "emu", "liblanding_emu.so"))
+    L = emu_landing_lib(20)
     R = lc("rbd").Rbd(L)
     n = 3
     q, qd, tau, f = _points(np.random.default_rng(5), n)
@@ -59,8 +54,7 @@ def test_fb_exact_linearisation_emulated(with_f):
     Richardson-extrapolated central differences (1e-8 relative; the central-difference kernel only reaches 1e-5), with and without
     caller buffers for qdd / H^-1 (the context scratch path)"""
     from oracle import rbd_oracle as ro
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
-    L = lc("capi").LandingLib(20, lib_path=os.path.join(ROOT, "tests", "emu", "liblanding_emu.so"))
+    L = emu_landing_lib(20)
     R = lc("rbd").Rbd(L)
     n = 2
     q, qd, tau, f = _points(np.random.default_rng(7), n)
@@ -91,8 +85,7 @@ def test_model_matches_reference_constants():
 
 def test_kinodyn_rows_emulated():
     from oracle import rbd_oracle as ro
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
-    L = lc("capi").LandingLib(20, lib_path=os.path.join(ROOT, "tests", "emu", "liblanding_emu.so"))
+    L = emu_landing_lib(20)
     R = lc("rbd").Rbd(L)
     rng = np.random.default_rng(2)
     n = 5
@@ -181,8 +174,7 @@ def test_kinodyn_rows_gpu_on_solved_batch():
 def test_leg_ik_emulated_roundtrip():
     """IK of the kinodynamic screen: FK(q6, IK(q6, FK(q6, jpos*))) == FK(q6, jpos*) for joint angles inside the limits"""
     from oracle import rbd_oracle as ro
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
-    L = lc("capi").LandingLib(20, lib_path=os.path.join(ROOT, "tests", "emu", "liblanding_emu.so"))
+    L = emu_landing_lib(20)
     R = lc("rbd").Rbd(L)
     rng = np.random.default_rng(9)
     n = 6

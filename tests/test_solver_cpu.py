@@ -6,21 +6,18 @@
     elimination, filter line search are all exercised without a GPU.
 """
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import certificate_reference as cr
-from conftest import GOLDEN, ROOT, lc
-
-PKG = os.path.join(ROOT, "landing-controller_amd")
+from conftest import GOLDEN, lc
+from emu_support import build_emu, emu_landing_lib
 
 
 @pytest.fixture(scope="module")
 def emu_lib():
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
-    return os.path.join(ROOT, "tests", "emu", "liblanding_emu.so")
+    return build_emu()
 
 
 def test_cpu_port_converges_and_certifies(oracle_mod):
@@ -183,10 +180,9 @@ def test_feasibility_phase_rescues_or_certifies(oracle_mod):
     machinery): on a hard small-horizon batch the emulated kernel follows the CPU port -- members that ended NUMERICAL / MAX_ITER are either
     rescued (KKT <= 1e-6 under the oracle's functions) or certified locally infeasible (status 3: equality rows met, positive violation that
     equals the kernel's report); members that converge without the phase are the same bits with it."""
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
     N, B = 10, 6
     O = oracle_mod.Oracle(N)
-    L = lc("capi").LandingLib(N, lib_path=os.path.join(ROOT, "tests", "emu", "liblanding_emu.so"))
+    L = emu_landing_lib(N)
     P, X0, _, _ = lc("problem").make_batch(B, N, 0.6, seed=3)
     keep = [1, 3, 5]; P, X0, B = P[keep], X0[keep], 3      # (one member of each kind: certified, rescued, converged anyway -- the emulation is slow)
     o = L.default_opts(); o.max_iter = 150

@@ -33,8 +33,6 @@ What these tests catch (each change applied alone to a scratch copy of the emula
 (run on: (a), (b) row algebra + named rho 1000 M in {2, 12, 27}; (c) those three step tests + running cost; (d) running cost; (e) row algebra + named M = 12 at both rho.)
 """
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -42,17 +40,16 @@ import pytest
 import elastic_newton_reference as er
 import feas_step_harness as F
 import solver_step_harness as H
-from conftest import ROOT, lc
+from conftest import lc
+from emu_support import build_emu
 
-PKG = os.path.join(ROOT, "landing-controller_amd")
 EPS = np.finfo(float).eps
 ALL16 = list(range(16))
 
 
 @pytest.fixture(scope="module")
 def emu_lib():
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
-    return H.EMU_LIB
+    return build_emu()
 
 
 def test_row_algebra_against_a_dense_solve(emu_lib):

@@ -11,22 +11,16 @@ np.array_equal, for every member of every case.  The horizons N = 2, 3, 5 (runni
 unroll factor 4: they run its clamped prefetches and its `k < N` guards; four members, 12 iterations each.
 Both instances of the backward loop are run: with the profile buffer set (timed) and unset, with equal outputs.
 (The DPP controls themselves exist on the device only: tests/test_gpu_solver_forward_chain.py.)"""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from emu_support import build_emu
 import make_golden_forward_chain as rec
-
-PKG = os.path.join(ROOT, "landing-controller_amd")
 
 
 @pytest.fixture(scope="module")
 def emu_lib():
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
-    return os.path.join(ROOT, "tests", "emu", "liblanding_emu.so")
+    return build_emu()
 
 
 @pytest.fixture(scope="module")

@@ -14,22 +14,19 @@ iteration limit 25, otherwise the defaults) cover all of it between them:
     test_emulated_kernel_follows_cpu_port); (b) landing_emu_accept_counts() -- counters that exist in the emulation build only -- shows which
     accept path every step took."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, lc
+from conftest import lc
+from emu_support import build_emu
 
-PKG = os.path.join(ROOT, "landing-controller_amd")
 FAST, FAST_CLIP, FIRST_REJECTED, BACKTRACK, CORR, FALLBACK, FEAS = range(7)
 
 
 @pytest.fixture(scope="module")
 def emu_lib():
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
-    return os.path.join(ROOT, "tests", "emu", "liblanding_emu.so")
+    return build_emu()
 
 
 def accept_counts(L, B):

@@ -8,22 +8,16 @@ x, lam_g, iters, status and kkt, np.array_equal, for every member of every case 
 penultimate / last stage type only), a 6-stage horizon stopped at its iteration limit, N = 20 with the defaults, the running-cost form, and
 members that enter the feasibility phase.  The counters of the run itself confirm what the cases are there for: sweeps that failed and were
 repeated with a larger delta_w (delta sits on the diagonal of the re-laid array) and steps inside the feasibility phase."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from emu_support import build_emu
 import make_golden_stage_layout as rec
-
-PKG = os.path.join(ROOT, "landing-controller_amd")
 
 
 @pytest.fixture(scope="module")
 def emu_lib():
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
-    return os.path.join(ROOT, "tests", "emu", "liblanding_emu.so")
+    return build_emu()
 
 
 @pytest.fixture(scope="module")

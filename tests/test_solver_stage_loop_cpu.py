@@ -13,22 +13,16 @@ at the LAST stage (each abandoned sweep attempted exactly one elimination: parti
 of n4 abandon sweeps INSIDE the loop ((partial - F) % N != 0: eliminations that ones and N + 1s cannot add up to).  A sweep abandoned at
 the foot block of stage 0 (partial > N F) does not occur within 16 iterations of these members and is not asserted.
 Both instances of the loop are run: with the profile buffer set (timed) and unset, with equal outputs."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from emu_support import build_emu
 import make_golden_stage_loop as rec
-
-PKG = os.path.join(ROOT, "landing-controller_amd")
 
 
 @pytest.fixture(scope="module")
 def emu_lib():
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
-    return os.path.join(ROOT, "tests", "emu", "liblanding_emu.so")
+    return build_emu()
 
 
 @pytest.fixture(scope="module")

@@ -25,25 +25,21 @@ which is why the emulated-kernel-follows-port tests never saw it.
 Inertia (test_regularised_step_and_inertia): in both cases examined the augmented matrix has the right inertia (n_free, n_rows, 0) at the
 accepted delta and the wrong one at the previous value of the schedule and at delta = 0, so that is asserted.
 """
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import newton_reference as nr
 import solver_step_harness as H
-from conftest import ROOT, lc
+from conftest import lc
+from emu_support import build_emu
 
-PKG = os.path.join(ROOT, "landing-controller_amd")
 RC_CCC = dict(QX=[0.3, 0.2, 10, 1, 1, 0.4, .1, .2, .1, .3, .1, .2], Qc=[1.0, 0.8, 0.5], Qf=[1e-4, 2e-4, 1e-3], f_ref=[0.5, -0.25, 20.0])
 WORST = {}
 
 
 @pytest.fixture(scope="module")
 def emu_lib():
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
-    return H.EMU_LIB
+    return build_emu()
 
 
 def problem(form, N, B, seed, **kw):

@@ -5,22 +5,16 @@ the backward sweep) and rterm with rlen (row products).  tests/golden/solver_tab
 their SHA-256, byte lengths and the ints, and ctype in full, recorded from the emulation library of the commit BEFORE the rewrite.  Every case
 and every table is compared -- none is skipped: the short horizons (2 and 3 stage types, the first middle stage, the first c_mid = 1), the
 long ones (rterm's 16-bit fields) and the two running-cost forms."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from emu_support import build_emu
 import make_golden_solver_tables as rec
-
-PKG = os.path.join(ROOT, "landing-controller_amd")
 
 
 @pytest.fixture(scope="module")
 def emu_lib():
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
-    return os.path.join(ROOT, "tests", "emu", "liblanding_emu.so")
+    return build_emu()
 
 
 @pytest.fixture(scope="module")

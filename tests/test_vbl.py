@@ -5,15 +5,11 @@ The HIP kernel (fp64 matrix cores) against the numpy oracle that restates the re
   * GPU (-m gpu): the product library, batch of trajectories sampled from solved landing NLPs.
 Tolerance: fp64, 1e-10 relative on A, B; 1e-9 relative on P and K after the whole backward sweep (products are
 accumulated in a different order on the matrix cores)."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-from conftest import ROOT, lc
-
-PKG = os.path.join(ROOT, "landing-controller_amd")
+from conftest import lc
+from emu_support import emu_landing_lib
 
 
 def _case(rng, n, B):
@@ -43,8 +39,7 @@ def _check(P, K, A, Bm, xref, fref, Ib, mass, Q, R, F, dt, rk4, vo):
 @pytest.mark.parametrize("rk4", [False, True])
 def test_vbl_emulated_kernel_matches_oracle(rk4):
     from oracle import vbl_oracle as vo
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
-    L = lc("capi").LandingLib(20, lib_path=os.path.join(ROOT, "tests", "emu", "liblanding_emu.so"))
+    L = emu_landing_lib(20)
     rng = np.random.default_rng(3)
     B, n = 2, 7
     xref, fref = _case(rng, n, B)

@@ -4,15 +4,12 @@ oracle of oracle/wb_oracle.py (6 x 6 Pluecker dynamics, Richardson-extrapolated 
 CPU: the kernels through tests/emu on a short horizon, iterate for iterate.  GPU: N = 40 steps of 1 ms, a batch of members: monotone cost,
 agreement of one member with the oracle after one iteration.  Tolerances (fp64): 1e-6 relative on trajectories and costs (the two
 sides differentiate the dynamics differently: forward mode vs extrapolated differences, 1e-8)."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-from conftest import ROOT, lc
+from conftest import lc
+from emu_support import emu_landing_lib
 
-PKG = os.path.join(ROOT, "landing-controller_amd")
 DT = 0.001        # explicit Euler on the leg links (joint-space inertias 5e-4 .. 6e-3 kg m^2 under 24 N foot forces) is unstable beyond ~1.5 ms
 Q = np.concatenate([np.full(3, 200.0), np.full(3, 100.0), np.full(12, 20.0), np.full(18, 0.5)])
 R = np.full(12, 1e-3)
@@ -50,8 +47,7 @@ def test_wb_sqp_emulated_follows_oracle(semi, fused):
     import torch
     from oracle import wb_oracle as wo
     wo.SEMI = semi
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
-    L = lc("capi").LandingLib(20, lib_path=os.path.join(ROOT, "tests", "emu", "liblanding_emu.so"))
+    L = emu_landing_lib(20)
     N, B, iters = 5, 2, 2
     x0, u0, xref, f = _problem(np.random.default_rng(3), B, N)
     S = _sqp(L, "cpu", N, semi_implicit=semi, fused=fused)

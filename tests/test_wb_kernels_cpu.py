@@ -4,21 +4,16 @@ landing_wb_select against a numpy restatement of its rule; the loop of landing-c
 backtracks; the generic-tree path of landing_fb_dynamics_batch / landing_wb_rollout on a renumbered quadruped; and the refusal of foot forces on a
 tree whose legs are not numbered the way the foot code composes them.  Laws, references and checks: tests/wb_reference.py (shared with
 tests/test_gpu_wb_kernels.py, which states the figures measured on the GPU)."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import wb_reference as wr
-from conftest import GOLDEN, ROOT, lc
-
-PKG = os.path.join(ROOT, "landing-controller_amd")
+from conftest import GOLDEN, lc
+from emu_support import emu_landing_lib
 
 
 def _lib():
-    subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "emu"], check=True, capture_output=True)
-    return lc("capi").LandingLib(20, lib_path=os.path.join(ROOT, "tests", "emu", "liblanding_emu.so"))
+    return emu_landing_lib(20)
 
 
 @pytest.fixture(scope="module")
