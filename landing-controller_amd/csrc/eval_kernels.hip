@@ -75,7 +75,20 @@ __device__ __forceinline__ void load_stage(const Layout& L, const double* x, con
 struct RowStore { double* g; __device__ __forceinline__ void put(int r, double v) { g[r] = v; } };
 struct SeqStoreJ { double* q; __device__ __forceinline__ void col() {} __device__ __forceinline__ void end() {} __device__ __forceinline__ void put(int, double v) { *q++ = v; } };
 struct SeqStoreH { double* q; __device__ __forceinline__ void end() {} __device__ __forceinline__ void put(double v) { *q++ = v; } };
-struct LamStage { const double* l; __device__ __forceinline__ double operator()(int r) const { return l[r]; } };
+// The solver's derivative phase reads the multipliers from a copy in LDS (landing_ipm_kernel): stage k at lam_lds_stage(k), the boundary rows at
+// 0..35.  lane = stage, so a read is 40 lanes LAM_LDS_STRIDE doubles apart -- odd, every lane on a bank pair of its own (104, the stride of the
+// workspace array, would put them on four).  The pointer type carries the LDS address space: ds_read, not a flat load.
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef const double __attribute__((address_space(3)))* landing_lds_cptr;
+#else
+typedef const double* landing_lds_cptr;
+#endif
+constexpr int LAM_LDS_STRIDE = 105;
+__host__ __device__ constexpr int lam_lds_stage(int k) { return 36 + LAM_LDS_STRIDE * k; }
+// YP: where the multipliers are read from (const double* = the member's array, landing_lds_cptr = the solver's LDS copy)
+template <class YP>
+struct LamStageAt { YP l; __device__ __forceinline__ double operator()(int r) const { return l[r]; } };
+typedef LamStageAt<const double*> LamStage;
 // the multipliers of a stage addressed by the row numbers of a MIDDLE stage (104 rows); `last`: the lane holds the last stage (80 rows: the six
 // no-slip rows of every foot are absent -> 0, the rows behind them move up).  r is a compile-time constant at every call site.
 struct LamRemap {
@@ -91,8 +104,9 @@ struct LamRemap {
 };
 
 // column-wise accumulation of J^T lam (grad_gamma_x)
-struct DotLam {
-  const double* lam_own; const double* lam_prev; bool first; double* out; double acc; bool open;
+template <class YP>
+struct DotLamAt {
+  YP lam_own; YP lam_prev; bool first; double* out; double acc; bool open;
   __device__ __forceinline__ void col() { if (open) *out++ = acc; acc = 0.0; open = true; }
   __device__ __forceinline__ void end() {}
   __device__ __forceinline__ void put(int r, double v) {
@@ -104,6 +118,7 @@ struct DotLam {
   }
   __device__ __forceinline__ void finish() { if (open) *out++ = acc; open = false; }
 };
+typedef DotLamAt<const double*> DotLam;
 
 // Sequential store of one CCS segment per lane, coalesced through an LDS tile: every lane of the wavefront appends its value to its own
 // tile row; every 16 values the wave writes 16-value runs out row by row, so that one store instruction covers four 128-byte runs instead of 64
@@ -588,28 +603,30 @@ __device__ __noinline__ void eval_task_jac(const Layout& L, const double* x, con
   SeqStoreJ ex{J + L.jx(k)}, eu{J + L.ju(k)};
   srbm::stage_jac(I.z, I.P, k == 0, k == L.N - 1, I.fz_prev, ex, eu);
 }
-__device__ __noinline__ void eval_task_jty(const Layout& L, const double* x, const double* p, int k, const double* y, double* gx) {
+// The two tasks that read multipliers take them as `yown` = the rows of stage k and `yprev` = the rows of stage k - 1 (stage 0: the boundary
+// rows), from the member's array or from the solver's LDS copy (YP).
+template <class YP>
+__device__ __noinline__ void eval_task_jty(const Layout& L, const double* x, const double* p, int k, YP yown, YP yprev, double* gx) {
   StageIn I; load_stage_in(L, x, p, k, I);
   const bool first = (k == 0);
-  const double* lprev = first ? y : y + L.g_stage(k - 1);
-  DotLam ex{y + L.g_stage(k), lprev, first, gx + L.x_X(k), 0.0, false};
-  DotLam eu{y + L.g_stage(k), lprev, first, gx + L.x_U(k), 0.0, false};
+  DotLamAt<YP> ex{yown, yprev, first, gx + L.x_X(k), 0.0, false};
+  DotLamAt<YP> eu{yown, yprev, first, gx + L.x_U(k), 0.0, false};
   srbm::stage_jac(I.z, I.P, first, k == L.N - 1, I.fz_prev, ex, eu);
   ex.finish(); eu.finish();
 }
 // Hessian values of stage k: PART 0 = both column groups, 1 = the X_k columns (29 values), 2 = the U_k columns (148 / 160).  The solver
 // runs 1 and 2 on two waves (round 5; the fourth wave used to idle through the derivative phase)
-template <int PART>
-__device__ __noinline__ void eval_task_hess(const Layout& L, const double* x, const double* p, int k, const double* y, double* H) {
+template <int PART, class YP>
+__device__ __noinline__ void eval_task_hess(const Layout& L, const double* x, const double* p, int k, YP yown, YP yprev, double* H) {
   StageIn I; load_stage_in(L, x, p, k, I);
   const bool first = (k == 0);
   double lps[12];
   for (int i = 0; i < 12; ++i) lps[i] = 0.0;
   if (!first) {
-    const double* lp = y + L.g_stage(k - 1);
+    const YP lp = yprev;
     for (int l = 0; l < 4; ++l) for (int i = 0; i < 3; ++i) lps[3 * l + i] = lp[16 + 12 * l + 2 + i] + lp[16 + 12 * l + 5 + i];
   }
-  LamStage lam{y + L.g_stage(k)};
+  LamStageAt<YP> lam{yown};
   if (PART == 0) { SeqStoreH hx{H + L.hx(k)}, hu{H + L.hu(k)}; srbm::stage_hess(I.z, I.P, first, k == L.N - 1, lam, lps, hx, hu); }
   else if (PART == 1) { SeqStoreH hx{H + L.hx(k)}; NullEmit hu; srbm::stage_hess(I.z, I.P, first, k == L.N - 1, lam, lps, hx, hu); }
   else { NullEmit hx; SeqStoreH hu{H + L.hu(k)}; srbm::stage_hess(I.z, I.P, first, k == L.N - 1, lam, lps, hx, hu); }
@@ -617,8 +634,10 @@ __device__ __noinline__ void eval_task_hess(const Layout& L, const double* x, co
 
 // Jacobian / Hessian nonzeros (CCS order) and gx = grad f + J^T y of one member.
 __device__ __noinline__ void member_eval_jh(const Layout& L, const double* x, const double* p, const double* y,
-                                            double* J, double* H, double* gx, double* tiles = nullptr, const int* edge_map = nullptr, double obj = 1.0) {
+                                            double* J, double* H, double* gx, double* tiles = nullptr, const int* edge_map = nullptr, double obj = 1.0,
+                                            bool lam_lds = false, landing_lds_cptr yl = nullptr) {
   const int N = L.N;      // obj: 1, or 0 in the solver's feasibility phase (no objective)
+  // lam_lds (uniform): the J^T y task and the Hessian tasks read the multipliers from the caller's LDS copy yl (layout: lam_lds_stage)
   for (int i = threadIdx.x; i < 36; i += blockDim.x) J[L.jx(N) + i] = 1.0;
   for (int i = threadIdx.x; i < 12; i += blockDim.x) {
     H[L.hx(N) + i] = obj * 2.0 * p[L.o_QN + i];
@@ -633,10 +652,18 @@ __device__ __noinline__ void member_eval_jh(const Layout& L, const double* x, co
   (void)tiles; (void)edge_map;      // (round 2's tiled write-out of the Jacobian task inside the solver: measured slower, removed)
   for (int task = wave; task < 4; task += nwave)
   for (int k = threadIdx.x & 63; k < N; k += 64) {
-    if (task == 0) eval_task_jac(L, x, p, k, J);
-    else if (task == 1) eval_task_jty(L, x, p, k, y, gx);
-    else if (task == 2) eval_task_hess<1>(L, x, p, k, y, H);
-    else eval_task_hess<2>(L, x, p, k, y, H);
+    if (task == 0) { eval_task_jac(L, x, p, k, J); continue; }
+    if (lam_lds) {
+      const landing_lds_cptr yo = yl + lam_lds_stage(k), yp = k == 0 ? yl : yl + lam_lds_stage(k - 1);
+      if (task == 1) eval_task_jty(L, x, p, k, yo, yp, gx);
+      else if (task == 2) eval_task_hess<1>(L, x, p, k, yo, yp, H);
+      else eval_task_hess<2>(L, x, p, k, yo, yp, H);
+    } else {
+      const double* yo = y + L.g_stage(k); const double* yp = k == 0 ? y : y + L.g_stage(k - 1);
+      if (task == 1) eval_task_jty(L, x, p, k, yo, yp, gx);
+      else if (task == 2) eval_task_hess<1>(L, x, p, k, yo, yp, H);
+      else eval_task_hess<2>(L, x, p, k, yo, yp, H);
+    }
   }
 }
 

@@ -200,6 +200,13 @@ struct Lds {
 // One instance per workgroup (= per NLP).  Namespace scope keeps the LDS address space visible to every
 // phase function (ds_* instructions instead of flat_*).
 __shared__ Lds SH;
+// the derivative phase's copy of the multipliers (landing_ipm_kernel, eval_kernels.hip lam_lds_stage) lies over [G | P | A1 | A^]: horizons up to 44
+constexpr int LAM_LDS_ROOM = 48 * GS + 24 * PS + 2 * XCH + 2 * 12 * YS;
+constexpr int LAM_LDS_NMAX = (LAM_LDS_ROOM - 36) / LAM_LDS_STRIDE;
+static_assert(offsetof(Lds, P) == offsetof(Lds, G) + sizeof(double) * 48 * GS && offsetof(Lds, A1) == offsetof(Lds, P) + sizeof(double) * 24 * PS &&
+              offsetof(Lds, Ah) == offsetof(Lds, A1) + sizeof(double) * 2 * XCH && offsetof(Lds, gam) == offsetof(Lds, G) + sizeof(double) * LAM_LDS_ROOM,
+              "G, P, A1, A^ are one contiguous range");
+static_assert(lam_lds_stage(LAM_LDS_NMAX) <= LAM_LDS_ROOM && LAM_LDS_NMAX == 44, "the copy of the multipliers fits");
 // The member's arrays as they are NOW (the accept step swaps instances, so no phase keeps these pointers across iterations): SH.M by value,
 // every pointer moved to scalar registers -- they are the same for all lanes, and the row passes then address with scalar base + lane offset.
 __device__ __forceinline__ MemberMem live_mem() {
@@ -1283,7 +1290,27 @@ __global__ void __launch_bounds__(SOLVER_THREADS, SOLVER_MIN_WAVES) landing_ipm_
     // tiles in the dead G array -- and is slower: 0.049 vs 0.039 ms alone, 0.094 vs 0.085 under load; every lane then runs the
     // full middle-stage stream and the wave serialises on 24 tile flushes, while the scattered stores of this version drain
     // asynchronously behind the arithmetic of the other two waves)
-    if ((lane & 63) < nst) member_eval_jh(L, M.x, p, M.y, M.J, M.H, M.gx, nullptr, nullptr, K.feas ? 0.0 : 1.0);
+    // The multipliers the J^T y task and the Hessian tasks read come from LDS: [G | P | A1 | A^] are dead here (riccati_backward clears or rewrites
+    // all four before it reads them, row_products was the last reader of the dx copy), and lane = stage reads of the workspace array touch 40 cache
+    // lines per instruction.  One coalesced pass, stage k to lam_lds_stage(k); longer horizons read the workspace as before.
+    const bool lam_lds = N <= LAM_LDS_NMAX;      // (uniform)
+    if (lam_lds) {
+      const landing_gptr yg = (landing_gptr)M.y;
+      double* const yl = S.G;
+      constexpr int YB = 8;
+      for (int rb = lane; rb < ng; rb += NT * YB) {
+        double yv[YB];
+#pragma unroll
+        for (int j = 0; j < YB; ++j) { const int r = rb + j * NT; yv[j] = yg[r < ng ? r : ng - 1]; }
+#pragma unroll
+        for (int j = 0; j < YB; ++j) {
+          const int r = rb + j * NT;
+          if (r < ng) yl[r < 36 ? r : r + (r - 36) / 104 * (LAM_LDS_STRIDE - 104)] = yv[j];
+        }
+      }
+      __syncthreads();
+    }
+    if ((lane & 63) < nst) member_eval_jh(L, M.x, p, M.y, M.J, M.H, M.gx, nullptr, nullptr, K.feas ? 0.0 : 1.0, lam_lds, (landing_lds_cptr)S.G);
     __syncthreads();
     if (L.run_cost && !K.feas) { rc_add_grad(); __syncthreads(); }   // objective gradient of the stage variables (the terminal part is in member_eval_jh)
     PROF_ADD(PH_EVAL, K.tp);
